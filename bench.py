@@ -16,9 +16,16 @@ N.
 A "step" is one GEM iteration (audioModel.py:384-428) on the GPU, inputs
 resident in HBM.  Prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--dry-run]
+A plain run does only what the headline figure needs: set-up, warm-up, the K
+timed steps, the --dump-outputs files if asked for, the result line.  --full
+adds the secondary measurements to the line: the per-kernel HIP-event pass
+(`kernels_ms`), the `roofline` block and the CPU oracle's `cpu_baseline`.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline]] [--dry-run]
 """
 import argparse
+import copy
 import json
 import os
 import sys
@@ -128,6 +135,41 @@ def build_model(seed, device, T=T_FRAMES, J=J_SRC, K=K_NMF):
                             device=device)
     m.makeItConvolutive()
     return m
+
+
+DUMP_BYTES = 60 << 20   # --dump-outputs budget (the files stay below 64 MB in all)
+
+
+def model_outputs(m, order, logliks):
+    """What a caller of the timed path receives, as float64 arrays: the timed
+    steps' logliks and the model's parameters after the last step (as
+    _download leaves them: per spatial component its mixing parameters,
+    complex ones as a trailing (re, im) axis, and FB / FW / TW of its NMF
+    component)."""
+    out = {"loglik": np.asarray(logliks, dtype=np.float64)}
+    for j, keys in enumerate(order):
+        p = np.asarray(m.spat_comps[j]['params'])
+        out["spat%d_params" % j] = (np.stack([p.real, p.imag], axis=-1) if np.iscomplexobj(p)
+                                    else p).astype(np.float64)
+        for k in keys:
+            fac = m.spec_comps[k]['factor'][0]
+            for part in ("FB", "FW", "TW"):
+                out["spec%d_%s" % (k, part)] = np.asarray(fac[part], dtype=np.float64)
+    return out
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """Write arrays as path/<name>.npy.  An array beyond its share of the
+    budget is written as a fixed sample of its flattened elements (sorted
+    indices drawn from RandomState(0), the same for every run of one shape)."""
+    os.makedirs(path, exist_ok=True)
+    share = budget // max(len(arrays), 1)
+    for name, a in sorted(arrays.items()):
+        a = np.ascontiguousarray(a)
+        if a.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).randint(0, a.size, share // a.itemsize))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def psd_schedule(m, n):
@@ -315,7 +357,14 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the per-kernel "
+                         "HIP-event pass (kernels_ms), the roofline block, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU oracle's iteration out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (the timed logliks "
+                         "and rank 0's model parameters after the last step) as DIR/<name>.npy")
     ap.add_argument("--warm-s", type=float, default=1.0,
                     help="untimed GEM iterations for at least this long before the W warm-up "
                          "steps (the GPU clock ramps over the first ~20 iterations)")
@@ -331,6 +380,8 @@ def main(argv=None):
                          "and the clips' allgather around a tiny host stand-in for the clip "
                          "(tests/test_distributed.py); no GPU is touched")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -369,22 +420,22 @@ def main(argv=None):
     order, Ks, conv = m._upload()
     rows_w = psd_schedule(m, max(args.warmup, 1))
     state = {"upl": (order, Ks, conv)}
+    init = copy.deepcopy((m.spat_comps, m.spec_comps))
 
     def run_rows(rows):
         """GEM iterations over the PSD rows; a random TW restart (host RNG)
         is performed and the run resumed, as the product does.  Returns the
-        last iteration's loglik."""
-        done, last = 0, float("nan")
+        iterations' logliks."""
+        done, lls = 0, np.full(len(rows), np.nan)
         while done < len(rows):
             ll, n, mask = eng.run(rows[done:], m.nmfUpdateCoeff)
+            lls[done:done + n] = ll
             done += n
-            if n:
-                last = float(ll[n - 1])
             if mask:
                 m._download(*state["upl"])
                 m._restart_tw(mask, state["upl"][0])
                 state["upl"] = m._upload()
-        return last
+        return lls
 
     # clock ramp: the first ~20 iterations of a process run while the GPU
     # clock rises (tools/ramp_probe.py); iterate untimed until it has settled,
@@ -394,6 +445,12 @@ def main(argv=None):
         t_w = time.perf_counter()
         while time.perf_counter() - t_w < args.warm_s:
             run_rows(rows_r)
+    # the ramp above runs for a time, not for a count: start the W warm-up
+    # and K timed steps from the initial parameters and a fixed host RNG
+    # state again, so that what they compute depends on the arguments alone
+    m.spat_comps, m.spec_comps = init
+    np.random.seed(2)
+    state["upl"] = m._upload()
     if args.warmup:
         run_rows(rows_w[:args.warmup])
 
@@ -407,29 +464,34 @@ def main(argv=None):
     rows = psd_schedule(m, args.steps)
     barrier_sync()
     t0 = time.perf_counter()
-    ll_last = run_rows(rows)
+    lls = run_rows(rows)
     barrier_sync()
     dt_own = time.perf_counter() - t0
     dt = max_over_ranks(dt_own, dist, coll_dev)
-    clips = gather_clips([rank, seed, device, ll_last, dt_own], dist, coll_dev)
+    clips = gather_clips([rank, seed, device, float(lls[-1]), dt_own], dist, coll_dev)
     if world > 1:
         check_clips(clips)
+    if args.dump_outputs and rank == 0:
+        m._download(*state["upl"])
+        dump_outputs(args.dump_outputs, model_outputs(m, state["upl"][0], lls))
 
-    # per-kernel HIP-event timing in the timed loop's own schedule (separate,
-    # untimed pass): the side stream stays forked, each kernel's events sit
-    # on the stream it runs on, and the host syncs once per 32 iterations
-    eng.set_profiling(True)
-    run_rows(psd_schedule(m, PROF_STEPS))
-    times = eng.kernel_times()
-    eng.set_profiling(False)
+    times = {}
+    if args.full:
+        # per-kernel HIP-event timing in the timed loop's own schedule (separate,
+        # untimed pass): the side stream stays forked, each kernel's events sit
+        # on the stream it runs on, and the host syncs once per 32 iterations
+        eng.set_profiling(True)
+        run_rows(psd_schedule(m, PROF_STEPS))
+        times = eng.kernel_times()
+        eng.set_profiling(False)
 
-    if rank == 0:
+    rl = None
+    if rank == 0 and args.full:
         R = sum(m.rank)
         F, T = m.nbFreqsSigRepr, m.nbFramesSigRepr
         work = kernel_work(F, T, args.J, R, args.K)
         itw = iteration_work(F, T, args.J, R, args.K)
         dom = max(times, key=lambda k: times[k][0])
-        rl = None
         pmc = None
         # PMC traffic of THIS configuration's own rocprofv3 passes
         # (tools/gpu_prof.sh; BENCH_ARGS="--J 8" -> profiles/r4_bench_J8K32.json)
@@ -495,6 +557,7 @@ def main(argv=None):
                     > work[k]["flops"] / FP64_MFMA_PEAK else "mfma",
                     "traffic": pmc_bytes(pmc, k)}
                 for k in ("k_estep", "k_tw_contract", "k_fb_contract") if k in times and k in work}
+    if rank == 0:
         out = {
             "metric": "EM iterations/sec (F=2049, T=10000, 2ch, 4src) at 1/2/4/8 MI355X",
             "value": round(job_value(world, args.steps, dt), 4),
@@ -515,12 +578,15 @@ def main(argv=None):
             "control_plane": backend or "none (one process)",
             "clips": [{"rank": int(c[0]), "data_seed": int(c[1]), "device": int(c[2]),
                        "loglik": c[3], "timed_s": round(c[4], 6)} for c in clips],
-            "roofline": rl,
-            "kernels_ms": {k: round(v[0], 4) for k, v in sorted(times.items())},
-            "kernels_schedule": "in situ: %d iterations, side stream forked, HIP events on each "
-                                "kernel's own stream, one host sync per 32 iterations" % PROF_STEPS,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            out.update({
+                "roofline": rl,
+                "kernels_ms": {k: round(v[0], 4) for k, v in sorted(times.items())},
+                "kernels_schedule": "in situ: %d iterations, side stream forked, HIP events on "
+                                    "each kernel's own stream, one host sync per 32 iterations"
+                                    % PROF_STEPS})
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.cpu_T)
         print(json.dumps(out), flush=True)
     if dist is not None:

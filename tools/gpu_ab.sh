@@ -4,7 +4,7 @@
 # (BENCH_ARGS overrides the bench arguments; ROUNDS the repetitions.)
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
-A="${BENCH_ARGS:---steps 200 --warmup 10 --no-cpu-baseline}"
+A="--full ${BENCH_ARGS:---steps 200 --warmup 10 --no-cpu-baseline}"
 for r in $(seq 1 "${ROUNDS:-2}"); do
   for spec in "$@"; do
     name="${spec%%:*}"; envs="${spec#*:}"

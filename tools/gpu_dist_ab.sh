@@ -16,7 +16,7 @@ print(sys.argv[1], d["ms_per_step"], d["value"], d["kernels_ms"]["k_estep"], d["
 PY
 }
 TR="python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29513"
-A="--gpus 1 --steps 100 --warmup 5 --no-cpu-baseline"
+A="--full --gpus 1 --steps 100 --warmup 5 --no-cpu-baseline"
 python -c "import os; print('affinity', len(os.sched_getaffinity(0)), 'cpus', os.cpu_count())"
 for r in 1 2; do
   run plain timeout -k 10 300 python bench.py $A

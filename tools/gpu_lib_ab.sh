@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 for round in 1 2; do
   for lib in "$@"; do
-    FASST_HIP_LIB=$PWD/$lib timeout -k 10 200 python bench.py --steps ${AB_STEPS:-200} --warmup 30 \
+    FASST_HIP_LIB=$PWD/$lib timeout -k 10 200 python bench.py --full --steps ${AB_STEPS:-200} --warmup 30 \
       --no-cpu-baseline > gpurun_out/ab.log 2>&1
     rc=$?; [ $rc -eq 0 ] || { echo "$lib rc=$rc"; tail -5 gpurun_out/ab.log; exit $rc; }
     python - "$lib" <<'PY'

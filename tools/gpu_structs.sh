@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 for jk in ${STRUCTS:-4x64 4x128 8x32 8x128}; do
   J=${jk%x*}; K=${jk#*x}
-  timeout -k 10 300 python bench.py --J $J --K $K --steps ${STEPS:-20} --warmup 3 --warm-s 0.5 --no-cpu-baseline \
+  timeout -k 10 300 python bench.py --full --J $J --K $K --steps ${STEPS:-20} --warmup 3 --warm-s 0.5 --no-cpu-baseline \
     > gpurun_out/st_$jk.json 2> gpurun_out/st_$jk.err || { echo "FAILED $jk"; tail -5 gpurun_out/st_$jk.err; exit 1; }
   python - $jk <<'PY'
 import json, sys
