@@ -222,8 +222,9 @@ def _c3_like(F, T, J, K, rank, iters, seed=0):
     (65, 77, 8, 128, 1, 2),      # J = 8, K = 128
     (33, 40, 5, 70, 2, 2),       # J = 5, K = 70, total rank 10
     (49, 52, 6, 100, [1, 2, 1, 2, 1, 2], 2),  # J = 6, K = 100, mixed ranks
-    # more than 8 sources (the two-pass E-step, k_egen_point / k_egen_stats;
-    # k_wiener's runtime-bounded kMaxJ form)
+    # more than 8 sources (K <= 32: the fused E-step, k_egen_fused; K > 32:
+    # the two-pass one, k_egen_point / k_egen_stats; k_wiener's
+    # runtime-bounded kMaxJ form)
     (49, 60, 12, 8, 1, 2),       # J = 12
     (33, 40, 16, 4, 1, 2),       # J = 16, total rank 16
     (65, 77, 10, 100, 1, 2),     # J = 10, K = 100 (KP = 128)
@@ -237,7 +238,8 @@ def _c3_like(F, T, J, K, rank, iters, seed=0):
     (2049, 1000, 4, 32, 2, 2),
     (2049, 500, 8, 32, 1, 2),
     # the fused many-source E-step (k_egen_fused) at the full F: 129 bin
-    # tiles, the production frame chunks, J = 16 at rank 2 (total rank 32)
+    # tiles, J = 16 at rank 2 (total rank 32); T = 96 is six frame tiles in
+    # one chunk (frame chunking is pinned in test_gpu_estep_matrix.py)
     (2049, 96, 16, 32, 2, 1),
     # ... its KP = 16 form with an odd J, ragged T, rank 1
     (1025, 77, 11, 12, 1, 2),
@@ -310,9 +312,9 @@ def test_k_above_64_every_structure_vs_oracle(what):
 
 @pytest.mark.parametrize("what", ["multi_fw", "lambda_tb"])
 def test_many_sources_every_structure_vs_oracle(what):
-    """J = 10 (the two-pass E-step) with several spectral components per
-    spatial component, free FW, lambdaCorr and time blobs, against the
-    oracle."""
+    """J = 10 at K = 12 (the fused many-source E-step, k_egen_fused<4>) with
+    several spectral components per spatial component, free FW, lambdaCorr
+    and time blobs, against the oracle."""
     m, o, X = _c3_like(49, 60, 10, 12, 1, 2)
     tb = {}
     for mod in (m, o):
