@@ -42,8 +42,10 @@ typedef struct fasst_ctx fasst_ctx;
  * Python loader does, pyfasst_amd/_lib.py).  Revision 2: fasst_source_powers
  * and fasst_sigma_comp take 128-bit column sets (two 64-bit words per
  * spatial component; revision 1 read one word, and fasst_sigma_comp took its
- * mask by value), so a revision-1 caller would pass too short an array. */
-#define FASST_ABI_VERSION 2
+ * mask by value), so a revision-1 caller would pass too short an array.
+ * Revision 3 adds the time-invariant spatial filter (fasst_spatial_filter_*)
+ * and fasst_gcc_phat. */
+#define FASST_ABI_VERSION 3
 int fasst_abi_version(void);
 
 const char *fasst_last_error(void);
@@ -178,6 +180,34 @@ int fasst_set_sources(fasst_ctx *ctx, int nsrc, const int *term_off, const int *
 int fasst_separate_waveforms(fasst_ctx *ctx, const double *psd, const double *window,
                              const double *analysis_window, int wlen, int nfft, int hop,
                              double *y);
+
+/* Time-invariant spatial filter (separate_spatial_filter_comp,
+ * audioModel.py:891-1061): per bin R_n = sum_r a_r a_r^H of every 'conv'
+ * spatial component, R_aa their mean over n, WG_n = R_n inv(R_aa)
+ * (inv_herm_mat_2d with its determinant clamp, tools/signalTools.py:182-196;
+ * compute_Wiener_gain_2d timeInvariant, audioModel.py:1453-1465) divided by
+ * Re(WG_n[0,0] + WG_n[1,1]).  The spectral parameters and the noise PSD play
+ * no part, and neither does fasst_set_sources: there is one output per spatial
+ * component.  All three need a configured context whose components are all
+ * 'conv' (the reference raises NotImplementedError('Mixing params not
+ * convolutive...') on an 'inst' one): otherwise FASST_ERR_UNSUPPORTED.
+ *   gains      WG out complex128 [J][2][2][F]
+ *   images     S out complex128 [J][2][F][T], S[n][c] = sum_c2 WG_n[c][c2] X[c2]
+ *              of the resident STFT (any transform's: fasst_set_stft)
+ *   waveforms  the iSTFT of each image, the gain applied as each frame is
+ *              loaded (the images are never stored); arguments, y layout
+ *              [J][2][len] and len as fasst_separate_waveforms              */
+int fasst_spatial_filter_gains(fasst_ctx *ctx, double *WG);
+int fasst_spatial_filter_images(fasst_ctx *ctx, double *S);
+int fasst_spatial_filter_waveforms(fasst_ctx *ctx, const double *window,
+                                   const double *analysis_window, int wlen, int nfft, int hop,
+                                   double *y);
+
+/* gcc_phat_tdoa_2d (audioModel.py:1316-1324): out float64 [nfft][T] =
+ * irfft(Cx01 / |Cx01|, n = nfft, axis = 0) of the context's observation
+ * (fasst_set_audio / fasst_set_stft / fasst_set_cx); needs nfft/2+1 == F.  A
+ * bin whose cross-spectrum is zero is 0/0 = NaN, as in the reference.        */
+int fasst_gcc_phat(fasst_ctx *ctx, int nfft, double *out);
 
 /* Per-kernel timing with HIP events (used by bench.py for the roofline of
  * the dominant kernel), in the timed loop's own schedule: each pair is

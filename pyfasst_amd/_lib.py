@@ -68,6 +68,11 @@ SIGNATURES = {
                                          ctypes.POINTER(ctypes.c_ulonglong)]),
     "fasst_separate_waveforms": (ctypes.c_int, [_vp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int,
                                                 ctypes.c_int, _dp]),
+    "fasst_spatial_filter_gains": (ctypes.c_int, [_vp, _dp]),
+    "fasst_spatial_filter_images": (ctypes.c_int, [_vp, _dp]),
+    "fasst_spatial_filter_waveforms": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_int, _dp]),
+    "fasst_gcc_phat": (ctypes.c_int, [_vp, ctypes.c_int, _dp]),
     "fasst_stft": (ctypes.c_int, [ctypes.c_int, _dp, ctypes.c_int, _dp, ctypes.c_int,
                                   ctypes.c_int, ctypes.c_int, _dp, _ip]),
     "fasst_istft": (ctypes.c_int, [ctypes.c_int, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int,
@@ -145,8 +150,9 @@ for _name, (_res, _args) in SIGNATURES.items():
     _fn.argtypes = _args
 
 # include/fasst_hip.h FASST_ABI_VERSION these signatures were written against
-# (revision 2: 128-bit column sets in fasst_source_powers / fasst_sigma_comp)
-ABI_VERSION = 2
+# (revision 2: 128-bit column sets in fasst_source_powers / fasst_sigma_comp;
+# revision 3: fasst_spatial_filter_* and fasst_gcc_phat)
+ABI_VERSION = 3
 if lib.fasst_abi_version() != ABI_VERSION:
     raise ImportError("pyfasst_amd: %s has ABI revision %d, this binding expects %d; rebuild it "
                       "(make -C pyfasst_amd/csrc)" % (LIB_PATH, lib.fasst_abi_version(), ABI_VERSION))

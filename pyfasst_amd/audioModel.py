@@ -640,6 +640,106 @@ class FASST(object):
             out.samplerate = self.audioObject.samplerate
             out._write()
 
+    # ---------------------------------------------------------------- spatial filter
+    def _spatial_filter_plan(self):
+        """The reference's refusals (audioModel.py:947-949, :965-966), then the
+        parameters on the device."""
+        if self.audioObject.channels != 2:
+            raise NotImplementedError()
+        for n in range(len(self.spat_comps)):
+            if self.spat_comps[n]['mix_type'] == 'inst':
+                raise NotImplementedError('Mixing params not convolutive...')
+        self._upload()
+
+    def spatial_filter_gains(self):
+        """Time-invariant gains WG[n] = R_n inv(mean_n R_n) / Re trace, [J, 2, 2, F],
+        of the 'conv' mixing parameters (audioModel.py:959-1004)."""
+        self._spatial_filter_plan()
+        return self._engine.spatial_filter_gains()
+
+    def spatial_filter_images(self):
+        """Images S[n, c] = sum_c2 WG[n][c, c2] X[c2], [J, 2, F, T], as the
+        reference forms them before each inverse transform (audioModel.py:1015-1030)."""
+        self._spatial_filter_plan()
+        return self._engine.spatial_filter_images()
+
+    def spatial_filter_waveforms(self):
+        """The iSTFT of spatial_filter_images() with the gains applied as the
+        device iSTFT loads each frame (STFT transform only): [J, channel,
+        sample], trimmed as tft.invertTransform() does."""
+        t = self.tft
+        if getattr(t, 'transformname', None) != 'stft':
+            raise NotImplementedError("the fused spatial filter needs the STFT transform "
+                                      "(use spatial_filter_images() + tft.invertTransform())")
+        self._spatial_filter_plan()
+        Y = self._engine.spatial_filter_waveforms(t.synthWindow, t.window, t.ftlen, t.fthop)
+        return Y[:, :, :t.datalen_init]
+
+    def separate_spatial_filter_comp(self, dir_results=None, suffix=None):
+        """Separate with the spatial filter of the mixing parameters alone, one
+        WAV per spatial component (audioModel.py:891-1061).  With the STFT the
+        gains are applied inside the device iSTFT; other transforms take the
+        device images and tft.invertTransform()."""
+        if dir_results is None:
+            dir_results = '/'.join(self.audioObject.filename.split('/')[:-1])
+        self._spatial_filter_plan()
+        nc = self.audioObject.channels
+        if getattr(self.tft, 'transformname', None) == 'stft':
+            Y = self.spatial_filter_waveforms()
+            S = None
+            nbSources = Y.shape[0]
+        else:
+            S = self._engine.spatial_filter_images()
+            nbSources = S.shape[0]
+        if not hasattr(self, 'files'):
+            self.files = {}
+        self.files['spatial'] = []
+        fileroot = self.audioObject.filename.split('/')[-1][:-4]
+        for n in range(nbSources):
+            if S is None:
+                ndata = Y[n].T
+            else:
+                ndata = []
+                for chan1 in range(nc):
+                    self.tft.transfo = S[n, chan1]
+                    ndata.append(self.tft.invertTransform())
+                    del self.tft.transfo
+                ndata = np.array(ndata).T
+            _suffix = '_spatial'
+            if suffix is not None and n in suffix:
+                _suffix += '_' + suffix[n]
+            outAudioName = (dir_results + '/' + fileroot + '_' + str(n) + '-' +
+                            str(nbSources) + _suffix + '.wav')
+            self.files['spatial'].append(outAudioName)
+            out = ao.AudioObject(filename=outAudioName, mode='w')
+            out._data = np.int16(ndata[:self.audioObject.nframes, :] * self.audioObject._maxdata)
+            out._maxdata = 1
+            out._encoding = 'pcm16'
+            out.samplerate = self.audioObject.samplerate
+            out._write()
+
+    def gcc_phat_tdoa_2d(self):
+        """GCC-PHAT detection function irfft(Cx[1] / |Cx[1]|, n=fsize, axis=0)
+        (audioModel.py:1316-1324): on the device for the STFT, the reference's
+        NumPy expression on Cx for the other transforms (their bins are no
+        half-spectrum of fsize)."""
+        if self.sig_repr_params['transf'] == 'stft' and self._engine is not None:
+            return self._engine.gcc_phat(self.sig_repr_params['fsize'])
+        with np.errstate(invalid='ignore', divide='ignore'):   # 0/0 = NaN, as the reference
+            return np.fft.irfft(self.Cx[1] / np.abs(self.Cx[1]),
+                                n=self.sig_repr_params['fsize'], axis=0)
+
+    def mvdr_2d(self, theta, distanceInterMic=.3):
+        """The reference's method (audioModel.py:1238-1314) cannot run, so there
+        is nothing to reproduce: its steering-vector module uses `np` and
+        `soundCelerity` without defining either (spatial/steering_vectors.py:48-52)
+        and it ends in `ao.filter_stft`, which audioObject does not have.
+        Kept for the class surface."""
+        raise NotImplementedError(
+            "mvdr_2d: the reference's method cannot run (spatial/steering_vectors.py:48-52 "
+            "has neither numpy nor soundCelerity in scope, and audioObject.filter_stft does "
+            "not exist), so no result exists to reproduce; use separate_spatial_filter_comp()")
+
     # ---------------------------------------------------------------- helpers
     def comp_spat_comp_power(self, spat_comp_ind, spec_comp_ind=[], factor_ind=[]):
         """Host-side V = prod_factors (FB.FW).(TW[.TB]) (audioModel.py:430-498);

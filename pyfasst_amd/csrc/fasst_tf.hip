@@ -454,20 +454,180 @@ __global__ __launch_bounds__(64) void k_wiener_src(const WSArgs a) {
   }
 }
 
+// inv_herm_mat_2d (tools/signalTools.py:182-196) of one matrix (d0, o; conj o,
+// d1): the clamped determinant; the inverse is (d1, -o; -conj o, d0) / det
+__device__ __forceinline__ double herm_det_2d(double d0, double d1, double2 o) {
+  const double det = d0 * d1 - (o.x * o.x + o.y * o.y);
+  const double dg = det + kEps;
+  return (dg > 0.0 ? 1.0 : (dg < 0.0 ? -1.0 : 0.0)) * fmax(fabs(det), kEps);
+}
+
 __global__ void k_inv_herm(int n, const double *__restrict__ d, const double2 *__restrict__ off,
                            double *__restrict__ id, double2 *__restrict__ ioff,
                            double *__restrict__ det_out) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const double d0 = d[i], d1 = d[n + i];
     const double2 o = off[i];
-    double det = d0 * d1 - (o.x * o.x + o.y * o.y);
-    const double dg = det + kEps;
-    det = (dg > 0.0 ? 1.0 : (dg < 0.0 ? -1.0 : 0.0)) * fmax(fabs(det), kEps);
+    const double det = herm_det_2d(d0, d1, o);
     ioff[i] = make_double2(-o.x / det, -o.y / det);
     id[i] = d1 / det;
     id[n + i] = d0 / det;
     det_out[i] = det;
   }
+}
+
+// ---- time-invariant spatial filter (separate_spatial_filter_comp,
+// audioModel.py:891-1061) ---------------------------------------------------
+// R_n of spatial component n at bin f (audioModel.py:974-981): the sums over
+// its ranks of |a0|^2, |a1|^2 and a0 conj(a1), in rank order
+__device__ __forceinline__ void spat_cov(const double2 *__restrict__ A, int r0, int r1, int Fp,
+                                         int f, double &al, double &be, double2 &ga) {
+  al = be = 0.0;
+  ga = make_double2(0.0, 0.0);
+  for (int r = r0; r < r1; ++r) {
+    const double2 a0 = A[(size_t)(2 * r) * Fp + f], a1 = A[(size_t)(2 * r + 1) * Fp + f];
+    al += a0.x * a0.x + a0.y * a0.y;
+    be += a1.x * a1.x + a1.y * a1.y;
+    ga.x += a0.x * a1.x + a0.y * a1.y;
+    ga.y += a0.y * a1.x - a0.x * a1.y;
+  }
+}
+
+// One thread per bin: R_aa = mean_n R_n (:983-985), its clamped inverse
+// (:986-988), WG_n = R_n inv(R_aa) (compute_Wiener_gain_2d, :1453-1465) over
+// its real trace (:1003-1004; NumPy divides a complex array by a real one as a
+// product with the reciprocal).  R_n is formed twice rather than kept for up
+// to kMaxJ components.  G [J][2][2][Fp], zero in the padding bins.
+__global__ void k_spatial_gain(const double2 *__restrict__ A, const int *__restrict__ roff, int J,
+                               int F, int Fp, double2 *__restrict__ G) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= Fp) return;
+  if (f >= F) {
+    for (int q = 0; q < 4 * J; ++q) G[(size_t)q * Fp + f] = make_double2(0.0, 0.0);
+    return;
+  }
+  double d0 = 0.0, d1 = 0.0;
+  double2 o = make_double2(0.0, 0.0);
+  for (int n = 0; n < J; ++n) {
+    double al, be;
+    double2 ga;
+    spat_cov(A, roff[n], roff[n + 1], Fp, f, al, be, ga);
+    d0 += al;
+    d1 += be;
+    o.x += ga.x;
+    o.y += ga.y;
+  }
+  d0 = d0 / J;
+  d1 = d1 / J;
+  o = make_double2(o.x / J, o.y / J);
+  const double det = herm_det_2d(d0, d1, o);
+  const double i0 = d1 / det, i1 = d0 / det;
+  const double ior = -o.x / det, ioi = -o.y / det;
+  for (int n = 0; n < J; ++n) {
+    double s0, s1;
+    double2 so;
+    spat_cov(A, roff[n], roff[n + 1], Fp, f, s0, s1, so);
+    // WG00 = so conj(iso) + sd0 isd0 ; WG11 = conj(so conj(iso)) + sd1 isd1
+    const double pr = so.x * ior + so.y * ioi, pi = so.y * ior - so.x * ioi;
+    const double w00r = pr + s0 * i0, w11r = pr + s1 * i1;
+    // WG01 = sd0 iso + so isd1 ; WG10 = conj(so) isd0 + sd1 conj(iso)
+    const double w01r = s0 * ior + so.x * i1, w01i = s0 * ioi + so.y * i1;
+    const double w10r = so.x * i0 + s1 * ior, w10i = -so.y * i0 - s1 * ioi;
+    const double scl = 1.0 / (w00r + w11r);
+    double2 *g = G + (size_t)(4 * n) * Fp + f;
+    g[0] = make_double2(w00r * scl, pi * scl);
+    g[Fp] = make_double2(w01r * scl, w01i * scl);
+    g[2 * (size_t)Fp] = make_double2(w10r * scl, w10i * scl);
+    g[3 * (size_t)Fp] = make_double2(w11r * scl, -pi * scl);
+  }
+}
+
+// one row of a 2x2 gain applied to the two channels: g0 x0 + g1 x1 (:1026-1029)
+__device__ __forceinline__ double2 gain_apply(double2 g0, double2 g1, double2 x0, double2 x1) {
+  return make_double2(g0.x * x0.x - g0.y * x0.y + (g1.x * x1.x - g1.y * x1.y),
+                      g0.x * x0.y + g0.y * x0.x + (g1.x * x1.y + g1.y * x1.x));
+}
+
+// STFT-domain images S [J][2][Tp][Fp] = G_n X: X streamed once, G from cache
+__global__ void k_spatial_images(const double2 *__restrict__ X, const double2 *__restrict__ G,
+                                 int J, int Fp, size_t plane, double2 *__restrict__ S) {
+  for (size_t o = blockIdx.x * (size_t)blockDim.x + threadIdx.x; o < plane;
+       o += (size_t)gridDim.x * blockDim.x) {
+    const int f = (int)(o % Fp);
+    const double2 x0 = X[o], x1 = X[plane + o];
+    for (int q = 0; q < 2 * J; ++q) {
+      const double2 *g = G + (size_t)(2 * q) * Fp + f;
+      S[(size_t)q * plane + o] = gain_apply(g[0], g[Fp], x0, x1);
+    }
+  }
+}
+
+// k_istft_frames of the image g0 X0 + g1 X1, formed as the frame is loaded
+// (g0, g1: one row of one component's gain, [Fp] each; X [2][Tp][ld])
+__global__ __launch_bounds__(256) void k_istft_gain_frames(
+    const double2 *__restrict__ X, size_t plane, int ld, const double2 *__restrict__ g0,
+    const double2 *__restrict__ g1, const double *__restrict__ win, int wlen,
+    const double2 *__restrict__ tw, int N, int logN, double *__restrict__ frames) {
+  extern __shared__ __attribute__((aligned(16))) double2 buf[];
+  const int n = blockIdx.x;
+  const double2 *x0 = X + (size_t)n * ld, *x1 = x0 + plane;
+  const int h = N / 2;
+  for (int i = threadIdx.x; i < N; i += blockDim.x) {
+    const int b = i <= h ? i : N - i;
+    double2 z = gain_apply(g0[b], g1[b], x0[b], x1[b]);
+    if (i == 0 || i == h)
+      z.y = 0.0;
+    else if (i > h)
+      z.y = -z.y;
+    buf[bitrev(i, logN)] = z;
+  }
+  __syncthreads();
+  lds_fft(buf, tw, N, logN);
+  const double invN = 1.0 / (double)N;
+  for (int i = threadIdx.x; i < wlen; i += blockDim.x)
+    frames[(size_t)n * wlen + i] = win[i] * (buf[i].x * invN);
+}
+
+// gcc_phat_tdoa_2d (audioModel.py:1322-1324): one block per frame, the
+// inverse real FFT of Cx01 / |Cx01| (a complex over a real: a product with
+// the reciprocal, so 0 / 0 = NaN) into out [Tp][N]
+__global__ __launch_bounds__(256) void k_gcc_phat(const double *__restrict__ cre,
+                                                  const double *__restrict__ cim, int ld,
+                                                  const double2 *__restrict__ tw, int N, int logN,
+                                                  double *__restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) double2 buf[];
+  const int n = blockIdx.x;
+  const int h = N / 2;
+  for (int i = threadIdx.x; i < N; i += blockDim.x) {
+    const int b = i <= h ? i : N - i;
+    const double re = cre[(size_t)n * ld + b], im = cim[(size_t)n * ld + b];
+    const double scl = 1.0 / hypot(re, im);
+    double2 z = make_double2(re * scl, im * scl);
+    if (i == 0 || i == h)
+      z.y = 0.0;
+    else if (i > h)
+      z.y = -z.y;
+    buf[bitrev(i, logN)] = z;
+  }
+  __syncthreads();
+  lds_fft(buf, tw, N, logN);
+  const double invN = 1.0 / (double)N;
+  for (int i = threadIdx.x; i < N; i += blockDim.x) out[(size_t)n * N + i] = buf[i].x * invN;
+}
+
+// real [T][N] -> [N][T]
+__global__ void k_real_transpose(const double *__restrict__ src, double *__restrict__ dst, int T,
+                                 int N) {
+  __shared__ double tile[16][17];
+  const int i0 = blockIdx.y * 16, t0 = blockIdx.x * 16;
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  {
+    const int t = t0 + ty, i = i0 + tx;
+    tile[ty][tx] = (t < T && i < N) ? src[(size_t)t * N + i] : 0.0;
+  }
+  __syncthreads();
+  const int i = i0 + ty, t = t0 + tx;
+  if (i < N && t < T) dst[(size_t)i * T + t] = tile[tx][ty];
 }
 
 
@@ -541,6 +701,10 @@ static int fft_smem(int N) {
     FASST_HIP(hipFuncSetAttribute((const void *)k_stft_frames,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     FASST_HIP(hipFuncSetAttribute((const void *)k_istft_frames,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    FASST_HIP(hipFuncSetAttribute((const void *)k_istft_gain_frames,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    FASST_HIP(hipFuncSetAttribute((const void *)k_gcc_phat,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   }
   return FASST_OK;
@@ -933,6 +1097,165 @@ int fasst_separate_waveforms(fasst_ctx *c, const double *psd, const double *wind
     FASST_LAUNCH_CHECK();
   }
   FASST_HIP(hipMemcpyAsync(y, dy.p, dy.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  FASST_HIP(hipStreamSynchronize(c->stream));
+  return FASST_OK;
+}
+
+}  // extern "C"
+
+namespace fasst {
+// every component 'conv' (audioModel.py:965-966 raises on an 'inst' one)
+static int need_conv_model(fasst_ctx *c, const char *fn) {
+  if (!c) return FASST_ERR_SHAPE;
+  if (!c->configured || !c->conv) {
+    set_error("%s: %s", fn, c->configured ? "Mixing params not convolutive..."
+                                          : "context not configured");
+    return FASST_ERR_UNSUPPORTED;
+  }
+  return FASST_OK;
+}
+
+// the gains of the context's mixing matrix into G [J][2][2][Fp] (on c->stream)
+static int spatial_gains(fasst_ctx *c, DBuf<int> &droff, DBuf<double2> &G) {
+  int st;
+  if ((st = droff.alloc_uninit(kMaxJ + 1)) || (st = G.alloc_uninit((size_t)c->J * 4 * c->Fp)))
+    return st;
+  FASST_HIP(hipMemcpyAsync(droff.p, c->roff, (c->J + 1) * sizeof(int), hipMemcpyHostToDevice,
+                           c->stream));
+  if ((st = build_inst_A(c))) return st;
+  k_spatial_gain<<<(c->Fp + 255) / 256, 256, 0, c->stream>>>(c->A.p, droff.p, c->J, c->F, c->Fp,
+                                                             G.p);
+  FASST_LAUNCH_CHECK();
+  return FASST_OK;
+}
+}  // namespace fasst
+
+extern "C" {
+
+int fasst_spatial_filter_gains(fasst_ctx *c, double *WG) {
+  int st = need_conv_model(c, "fasst_spatial_filter_gains");
+  if (st) return st;
+  if (!WG) return FASST_ERR_SHAPE;
+  DeviceGuard g(c->device);
+  DBuf<int> droff;
+  DBuf<double2> G;
+  if ((st = spatial_gains(c, droff, G))) return st;
+  FASST_HIP(hipMemcpy2DAsync(WG, c->F * sizeof(double2), G.p, c->Fp * sizeof(double2),
+                             c->F * sizeof(double2), (size_t)c->J * 4, hipMemcpyDeviceToHost,
+                             c->stream));
+  FASST_HIP(hipStreamSynchronize(c->stream));
+  return FASST_OK;
+}
+
+int fasst_spatial_filter_images(fasst_ctx *c, double *S) {
+  int st = need_conv_model(c, "fasst_spatial_filter_images");
+  if (st) return st;
+  if (!S) return FASST_ERR_SHAPE;
+  if (!c->have_X) {
+    set_error("fasst_spatial_filter_images: no STFT available (set_audio / set_stft)");
+    return FASST_ERR_SHAPE;
+  }
+  DeviceGuard g(c->device);
+  const int J = c->J;
+  const size_t plane = (size_t)c->Tp * c->Fp;
+  DBuf<int> droff;
+  DBuf<double2> G, dS, hS;
+  if ((st = spatial_gains(c, droff, G)) || (st = dS.alloc((size_t)J * 2 * plane)) ||
+      (st = hS.alloc((size_t)J * 2 * c->F * c->T)))
+    return st;
+  k_spatial_images<<<2048, 256, 0, c->stream>>>(c->X.p, G.p, J, c->Fp, plane, dS.p);
+  FASST_LAUNCH_CHECK();
+  k_tf_to_ft<<<dim3(c->ntt, c->nft, J * 2), 256, 0, c->stream>>>(dS.p, hS.p, c->F, c->T, c->Fp, c->Tp);
+  FASST_LAUNCH_CHECK();
+  FASST_HIP(hipMemcpyAsync(S, hS.p, hS.n * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+  FASST_HIP(hipStreamSynchronize(c->stream));
+  return FASST_OK;
+}
+
+int fasst_spatial_filter_waveforms(fasst_ctx *c, const double *window,
+                                   const double *analysis_window, int wlen, int nfft, int hop,
+                                   double *y) {
+  int st = need_conv_model(c, "fasst_spatial_filter_waveforms");
+  if (st) return st;
+  if (!window || !y) return FASST_ERR_SHAPE;
+  if ((st = check_fft(nfft, wlen, hop))) return st;
+  if (nfft / 2 + 1 != c->F) {
+    set_error("fasst_spatial_filter_waveforms: nfft=%d gives %d bins, the model has F=%d", nfft,
+              nfft / 2 + 1, c->F);
+    return FASST_ERR_SHAPE;
+  }
+  if (!c->have_X) {
+    set_error("fasst_spatial_filter_waveforms: no STFT available (set_audio / set_stft)");
+    return FASST_ERR_SHAPE;
+  }
+  DeviceGuard g(c->device);
+  if ((st = fft_smem(nfft))) return st;
+  const int J = c->J, T = c->T;
+  const size_t plane = (size_t)c->Tp * c->Fp;
+  const int len_out = hop * (T - 1) + wlen - wlen / 2;  // istft (stft.py:108-129)
+  DBuf<double> dw, daw, dframes, dy;
+  DBuf<int> droff;
+  DBuf<double2> G, dtw;
+  if ((st = dw.alloc(wlen)) || (st = daw.alloc(wlen)) || (st = dtw.alloc(nfft / 2)) ||
+      (st = dframes.alloc_uninit((size_t)T * wlen)) ||
+      (st = dy.alloc_uninit((size_t)J * 2 * len_out)))
+    return st;
+  auto tw = twiddles(nfft, +1);
+  FASST_HIP(hipMemcpyAsync(dw.p, window, (size_t)wlen * sizeof(double), hipMemcpyHostToDevice,
+                           c->stream));
+  FASST_HIP(hipMemcpyAsync(daw.p, analysis_window ? analysis_window : window,
+                           (size_t)wlen * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  FASST_HIP(hipMemcpyAsync(dtw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice,
+                           c->stream));
+  if ((st = spatial_gains(c, droff, G))) return st;
+  // image q = (n, channel): its frames are g0 X0 + g1 X1 of the resident X
+  // rows, formed in the iSTFT's LDS buffer; only waveforms are written
+  for (int q = 0; q < 2 * J; ++q) {
+    const double2 *g0 = G.p + (size_t)(2 * q) * c->Fp;
+    k_istft_gain_frames<<<T, 256, nfft * sizeof(double2), c->stream>>>(
+        c->X.p, plane, c->Fp, g0, g0 + c->Fp, dw.p, wlen, dtw.p, nfft, ilog2(nfft), dframes.p);
+    FASST_LAUNCH_CHECK();
+    k_ola<<<(len_out + 255) / 256, 256, 0, c->stream>>>(dframes.p, T, wlen, hop, dw.p, daw.p,
+                                                        dy.p + (size_t)q * len_out, len_out);
+    FASST_LAUNCH_CHECK();
+  }
+  FASST_HIP(hipMemcpyAsync(y, dy.p, dy.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  FASST_HIP(hipStreamSynchronize(c->stream));
+  return FASST_OK;
+}
+
+int fasst_gcc_phat(fasst_ctx *c, int nfft, double *out) {
+  if (!c || !out) return FASST_ERR_SHAPE;
+  if (ilog2(nfft) < 1 || nfft > 8192 || nfft / 2 + 1 != c->F) {
+    set_error("fasst_gcc_phat: nfft=%d must be a power of two <= 8192 with nfft/2+1 == F=%d", nfft,
+              c->F);
+    return FASST_ERR_SHAPE;
+  }
+  if (!c->cx_ready) {
+    set_error("fasst_gcc_phat: no observation (set_audio / set_stft / set_cx)");
+    return FASST_ERR_SHAPE;
+  }
+  DeviceGuard g(c->device);
+  int st;
+  if ((st = fft_smem(nfft))) return st;
+  const int T = c->T;
+  const size_t plane = (size_t)c->Tp * c->Fp;
+  DBuf<double> d, dt;
+  DBuf<double2> dtw;
+  if ((st = d.alloc_uninit((size_t)T * nfft)) || (st = dt.alloc_uninit((size_t)T * nfft)) ||
+      (st = dtw.alloc(nfft / 2)))
+    return st;
+  auto tw = twiddles(nfft, +1);
+  FASST_HIP(hipMemcpyAsync(dtw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice,
+                           c->stream));
+  // Cx01 is resident whichever way the observation came (k_cx_from_X forms it
+  // from the channel STFTs): planes 2 and 3 of cx
+  k_gcc_phat<<<T, 256, nfft * sizeof(double2), c->stream>>>(c->cx.p + 2 * plane, c->cx.p + 3 * plane,
+                                                           c->Fp, dtw.p, nfft, ilog2(nfft), d.p);
+  FASST_LAUNCH_CHECK();
+  k_real_transpose<<<dim3((T + 15) / 16, (nfft + 15) / 16), 256, 0, c->stream>>>(d.p, dt.p, T, nfft);
+  FASST_LAUNCH_CHECK();
+  FASST_HIP(hipMemcpyAsync(out, dt.p, dt.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }

@@ -234,6 +234,36 @@ class Engine(object):
               "fasst_separate_waveforms")
         return out
 
+    # ------------------------------------------------------------ spatial filter
+    def spatial_filter_gains(self):
+        """Time-invariant gains of the 'conv' mixing parameters: [J, 2, 2, F]."""
+        out = np.empty((len(self.structure[0]), 2, 2, self.F), dtype=np.complex128)
+        check(lib.fasst_spatial_filter_gains(self._h, dptr(out)), "fasst_spatial_filter_gains")
+        return out
+
+    def spatial_filter_images(self):
+        """The gains applied to the resident transform: [J, 2, F, T]."""
+        out = np.empty((len(self.structure[0]), 2, self.F, self.T), dtype=np.complex128)
+        check(lib.fasst_spatial_filter_images(self._h, dptr(out)), "fasst_spatial_filter_images")
+        return out
+
+    def spatial_filter_waveforms(self, window, analysis_window, nfft, hop):
+        """Gain on load + per-image iSTFT on the device: [J, 2, len] float64."""
+        w = np.ascontiguousarray(window, dtype=np.float64)
+        aw = np.ascontiguousarray(analysis_window, dtype=np.float64)
+        n = int(hop) * (self.T - 1) + w.size - w.size // 2
+        out = np.empty((len(self.structure[0]), 2, n))
+        check(lib.fasst_spatial_filter_waveforms(self._h, dptr(w), dptr(aw), w.size, int(nfft),
+                                                 int(hop), dptr(out)),
+              "fasst_spatial_filter_waveforms")
+        return out
+
+    def gcc_phat(self, nfft):
+        """irfft(Cx01 / |Cx01|, n=nfft, axis=0) of the observation: [nfft, T]."""
+        out = np.empty((int(nfft), self.T))
+        check(lib.fasst_gcc_phat(self._h, int(nfft), dptr(out)), "fasst_gcc_phat")
+        return out
+
     # ------------------------------------------------------------ step methods
     def source_powers(self, j0, nj, colmasks=None):
         """V [nj, F, T] of spatial components j0 .. j0+nj-1 (fasst_source_powers)."""

@@ -12,6 +12,10 @@
   --workload wf0    SIMM source dictionary generate_WF0_TR_chirped at config
                     5 (44.1 kHz, NFT 4096, 1092 KLGLOTT88 combs, STFT middle
                     frame): device time per dictionary
+  --workload spatial  the time-invariant spatial filter at C3
+                    (separate_spatial_filter_comp, audioModel.py:891-1061):
+                    per-bin gains + the 2 J iSTFTs with the gain applied on
+                    load (fasst_spatial_filter_waveforms), host-inclusive
   --workload viterbi  melody tracking (_tracking.pyx:11-93) at config 5:
                     S = 1092 F0 states, N = 20000 frames (runViterbi's
                     transitions, stepNotes 16): tracks/s, device time
@@ -142,6 +146,40 @@ def bench_separate(steps, warmup):
             "images_path_ms": round(di * 1e3, 3), "image_bytes_to_host": int(S.nbytes),
             "front_end_ms": round(ds * 1e3, 3), "front_end": "fasst_set_audio: %d x 2 samples -> "
             "resident STFTs + Cx, host-inclusive" % L}
+
+
+def bench_spatial(steps, warmup):
+    """The fused spatial filter at C3: the same 2 J iSTFTs as `separate`, no
+    per-point Wiener pass and no image planes in HBM; the images path
+    (fasst_spatial_filter_images) beside it.  Host-inclusive wall times."""
+    sys.path.insert(0, ROOT)
+    import bench as B
+    m = B.build_model(seed=0, device=0)
+    eng = m._engine
+    m._upload()
+    nfft, hop = 4096, 512
+    w = np.hanning(nfft)
+    for _ in range(max(warmup, 1)):
+        eng.spatial_filter_waveforms(w, w, nfft, hop)
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        Y = eng.spatial_filter_waveforms(w, w, nfft, hop)
+    dt = (time.perf_counter() - t0) / steps
+    eng.spatial_filter_images()
+    t1 = time.perf_counter()
+    for _ in range(steps):
+        S = eng.spatial_filter_images()
+    di = (time.perf_counter() - t1) / steps
+    J = Y.shape[0]
+    return {"metric": "FASST spatial filter (per-bin gains + gain-on-load iSTFT) per clip, "
+                      "host-inclusive",
+            "value": round(dt * 1e3, 3), "unit": "ms", "higher_is_better": False,
+            "steps": steps, "warmup": warmup, "dtype": "f64",
+            "data": "synthetic C3 model (bench.py build_model, seed 0)",
+            "config": {"workload": "J=%d sources x 2 channels, F=%d, T=%d, nfft %d hop %d"
+                                   % (J, m.nbFreqsSigRepr, m.nbFramesSigRepr, nfft, hop)},
+            "waveform_bytes_to_host": int(Y.nbytes),
+            "images_path_ms": round(di * 1e3, 3), "image_bytes_to_host": int(S.nbytes)}
 
 
 def bench_nmf(steps, warmup, F=1025, N=2000, K=64, seed=0):
@@ -344,7 +382,7 @@ def bench_viterbi(steps, warmup, S=1092, N=20000, seed=0):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=("simm", "nmf", "cqt", "viterbi", "wf0", "separate",
-                                           "nnls"),
+                                           "nnls", "spatial"),
                     required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -354,7 +392,8 @@ def main():
     global NO_CPU
     NO_CPU = a.no_cpu_baseline
     fn = {"simm": bench_simm, "nmf": bench_nmf, "cqt": bench_cqt, "viterbi": bench_viterbi,
-          "wf0": bench_wf0, "separate": bench_separate, "nnls": bench_nnls}[a.workload]
+          "wf0": bench_wf0, "separate": bench_separate, "nnls": bench_nnls,
+          "spatial": bench_spatial}[a.workload]
     out = fn(a.steps, a.warmup)
     if NO_CPU:
         out["cpu_baseline"] = None   # not measured (the sample above timed nothing)
