@@ -44,8 +44,9 @@ typedef struct fasst_ctx fasst_ctx;
  * spatial component; revision 1 read one word, and fasst_sigma_comp took its
  * mask by value), so a revision-1 caller would pass too short an array.
  * Revision 3 adds the time-invariant spatial filter (fasst_spatial_filter_*)
- * and fasst_gcc_phat. */
-#define FASST_ABI_VERSION 3
+ * and fasst_gcc_phat.  Revision 4 adds the discrete-state time weights
+ * (fasst_set_tw_constr / fasst_get_tw_constr). */
+#define FASST_ABI_VERSION 4
 int fasst_abi_version(void);
 
 const char *fasst_last_error(void);
@@ -137,6 +138,30 @@ int fasst_set_corr(fasst_ctx *ctx, double lambda, int nseq, const int *seq_j, co
 int fasst_set_tb(fasst_ctx *ctx, int j, int b, int L, const double *TW, const double *TB,
                  int tb_free);
 int fasst_get_tb(fasst_ctx *ctx, int j, int b, double *TW, double *TB);
+
+/* Discrete-state time weights of source j's spectral component (TW_constr,
+ * update_spectral_components audioModel.py:1728-1928): kind 0 = 'NMF' (the
+ * default after fasst_configure), 1 = 'GSMM', 2 = 'SHMM'.  With kind > 0 and
+ * a free TW, the TW step of fasst_run / fasst_spectral_update re-estimates,
+ * per state k alone, the weight TW_all[k, t], takes the Itakura-Saito
+ * divergence of hat_W to that single-state power, decodes one state per frame
+ * (GSMM: argmin with the state priors; SHMM: the reference's Viterbi with the
+ * transition matrix) and leaves TW = TW_all at the decoded state, 0 elsewhere.
+ * TW_all float64 [K][T], or NULL: every row = max_k TW[k, t] of the TW
+ * uploaded by fasst_set_spectral (call it first).  dp float64 [K] (GSMM) or
+ * [K][K] (SHMM), or NULL: 1 / K.  dp_free = TW_DP_frdm_prior == 'free': dp
+ * becomes the decoded state (transition) frequencies after each iteration.
+ * The source must have one spectral component without time blobs, the
+ * context at most 4096 frequency bins (the step keeps a frame tile of hat_W
+ * and a basis column in LDS; FASST_ERR_UNSUPPORTED from this call), and
+ * lambdaCorr must be 0 when the iteration runs (FASST_ERR_UNSUPPORTED).
+ * fasst_configure, fasst_set_blocks with several components and fasst_set_tb
+ * with time blobs on the source drop the constraint.  renormalize_parameters rescales TW, never TW_all.
+ * fasst_get_tw_constr: TW_all [K][T], dp [K] or [K][K], state int [T] (the
+ * last decoded sequence; zeros before the first TW step); any may be NULL. */
+int fasst_set_tw_constr(fasst_ctx *ctx, int j, int kind, const double *TW_all,
+                        const double *dp, int dp_free);
+int fasst_get_tw_constr(fasst_ctx *ctx, int j, double *TW_all, double *dp, int *state);
 
 /* renormalize_parameters (audioModel.py:1980-2040).  restart_mask bit j (or
  * bit per spectral component, fasst_set_blocks) is set when sum(TW) < eps:

@@ -61,6 +61,8 @@ SIGNATURES = {
     "fasst_set_tb": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp,
                                     ctypes.c_int]),
     "fasst_get_tb": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp]),
+    "fasst_set_tw_constr": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_int]),
+    "fasst_get_tw_constr": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, _ip]),
     "fasst_renormalize": (ctypes.c_int, [_vp, _ip]),
     "fasst_run": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_double, _dp, _ip, _ip]),
     "fasst_wiener_images": (ctypes.c_int, [_vp, _dp, _dp, _dp]),
@@ -151,8 +153,9 @@ for _name, (_res, _args) in SIGNATURES.items():
 
 # include/fasst_hip.h FASST_ABI_VERSION these signatures were written against
 # (revision 2: 128-bit column sets in fasst_source_powers / fasst_sigma_comp;
-# revision 3: fasst_spatial_filter_* and fasst_gcc_phat)
-ABI_VERSION = 3
+# revision 3: fasst_spatial_filter_* and fasst_gcc_phat; revision 4:
+# fasst_set_tw_constr / fasst_get_tw_constr)
+ABI_VERSION = 4
 if lib.fasst_abi_version() != ABI_VERSION:
     raise ImportError("pyfasst_amd: %s has ABI revision %d, this binding expects %d; rebuild it "
                       "(make -C pyfasst_amd/csrc)" % (LIB_PATH, lib.fasst_abi_version(), ABI_VERSION))

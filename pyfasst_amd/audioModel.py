@@ -180,6 +180,18 @@ class FASST(object):
         combination the reference's mixing update can run (free 'conv' ones
         only when every component is free 'conv'); any lambdaCorr >= 0 (the
         inter-source correlation penalty, :1484-1719).
+
+        Discrete-state time weights (TW_constr 'GSMM' / 'SHMM', :1728-1928):
+        on a spectral component that is the only one of its spatial component
+        (a constrained component sharing its spatial component with others
+        raises NotImplementedError), with lambdaCorr == 0 (NotImplementedError
+        otherwise) and no time blobs (AttributeError, as the reference :1736-
+        1742), at most 4096 frequency bins (NotImplementedError from the
+        upload: the device step keeps a frame tile of hat_W in LDS, DESIGN.md
+        7.1).  The other spatial components of the model may carry any
+        structure above.  'GMM' and 'HMM' raise NotImplementedError here,
+        before any parameter moves: the reference updates the model and then
+        raises from its first renormalisation (:2015,2038-2040).
         """
         if self.audioObject.channels != 2:
             raise AttributeError("Nb channels " + str(self.audioObject.channels) +
@@ -201,10 +213,32 @@ class FASST(object):
                         np.shape(fac['TW']) != (fac['FB'].shape[1], TB.shape[0]):
                     raise ValueError("time blobs of spectral component %d: TW %s, TB %s"
                                      % (k, np.shape(fac['TW']), TB.shape))
-            if fac.get('TW_constr', 'NMF') != 'NMF':
-                raise NotImplementedError("TW_constr=%s is outside the HIP path" % fac['TW_constr'])
+            constr = fac.get('TW_constr', 'NMF')
+            if constr in ('GMM', 'HMM'):
+                raise NotImplementedError(
+                    "TW_constr=%s: Temporal discrete state mngmt not done yet. (the reference "
+                    "raises this from renormalize_parameters, audioModel.py:2038-2040, after "
+                    "its first update; refused here before any parameter moves)" % constr)
+            if constr not in ('NMF', 'GSMM', 'SHMM'):
+                raise NotImplementedError("TW_constr=%s is outside the HIP path" % constr)
+            if constr != 'NMF' and fac.get('TW_frdm_prior', 'free') == 'free':
+                if len(fac['TB']):
+                    raise AttributeError(
+                        "In this implementation, as in Ozerov's, non-trivial time blobs TB is "
+                        "incompatible with discrete state-based constraints for the time "
+                        "weights TW")
+                if self.lambdaCorr > 0:
+                    raise NotImplementedError("TW_constr=%s with lambdaCorr > 0 is outside the "
+                                              "HIP path" % constr)
         if sorted(owner.keys()) != list(range(J)):
             raise NotImplementedError("every spatial component needs a spectral component")
+        for j, keys in owner.items():
+            if len(keys) > 1 and any(self._tw_constr(self.spec_comps[k]['factor'][0])
+                                     for k in keys):
+                raise NotImplementedError(
+                    "a spectral component with discrete-state time weights must be the only one "
+                    "of its spatial component on the HIP path (spatial component %d has %d)"
+                    % (j, len(keys)))
         conv = [self.spat_comps[j]['mix_type'] == 'conv' for j in range(J)]
         free = [self.spat_comps[j]['frdm_prior'] == 'free' for j in range(J)]
         # update_mix_matrix (:843-863) solves the free 'conv' components with
@@ -223,6 +257,23 @@ class FASST(object):
             ranks.append(p.shape[0] if conv[j] else p.shape[1])
             Ks.append(int(sum(self.spec_comps[k]['factor'][0]['FB'].shape[1] for k in owner[j])))
         return [owner[j] for j in range(J)], ranks, Ks, (all(conv) if len(set(conv)) == 1 else conv)
+
+    @staticmethod
+    def _tw_constr(fac):
+        """'GSMM' / 'SHMM' when the factor's TW step is the discrete-state one
+        (free TW, audioModel.py:1634,1728), else None."""
+        c = fac.get('TW_constr', 'NMF')
+        return c if c in ('GSMM', 'SHMM') and fac.get('TW_frdm_prior', 'free') == 'free' else None
+
+    def _constrained(self, order):
+        """[(spatial component, spectral key, factor, constraint)] of the
+        discrete-state components."""
+        out = []
+        for j, keys in enumerate(order):
+            fac = self.spec_comps[keys[0]]['factor'][0]
+            if len(keys) == 1 and self._tw_constr(fac):
+                out.append((j, keys[0], fac, self._tw_constr(fac)))
+        return out
 
     def _upload(self):
         order, ranks, Ks, conv = self._structure()
@@ -255,6 +306,12 @@ class FASST(object):
             for b, f in enumerate(facs):
                 if len(f['TB']):
                     eng.set_tb(j, b, f['TW'], f['TB'], f.get('TB_frdm_prior') == 'free')
+            constr = self._tw_constr(facs[0]) if len(facs) == 1 else None
+            # TW_all / TW_DP_params when the factor already has them, else the
+            # reference's first-use values formed by the library (:1744-1760)
+            eng.set_tw_constr(j, constr or 'NMF', facs[0].get('TW_all'),
+                              facs[0].get('TW_DP_params'),
+                              facs[0].get('TW_DP_frdm_prior') == 'free')
         if self.lambdaCorr > 0:   # components one at a time in key order (:1479)
             pos = {k: (j, b) for j, keys in enumerate(order) for b, k in enumerate(keys)}
             seq = [pos[k] for k in sorted(self.spec_comps.keys())]
@@ -262,6 +319,27 @@ class FASST(object):
         else:
             eng.set_corr(0.0)
         return order, Ks, conv
+
+    def _download_constr(self, order, iters=1):
+        """After TW steps: TW_all / TW_DP_params into the factor dicts as the
+        reference leaves them (:1744-1760,1809,1902-1924), the last decoded
+        state sequences into self.tw_state_seq[spectral key], and the
+        reference's unconditional print per prior update (:1903)."""
+        for j, k, fac, constr in self._constrained(order):
+            TW_all, dp, state = self._engine.get_tw_constr(j, constr)
+            fac['TW_all'] = TW_all
+            fac['TW_DP_params'] = dp
+            if not hasattr(self, 'tw_state_seq'):
+                self.tw_state_seq = {}
+            self.tw_state_seq[k] = state
+            if fac.get('TW_DP_frdm_prior') == 'free':
+                for _ in range(iters):
+                    print("    Updating the transition probabilities")
+
+    def _warn_constr(self, order):
+        if self._constrained(order):   # the reference's warning (:1729-1731)
+            warnings.warn("The GMM/GSMM/HMM still needs to be adapted " +
+                          "to take into account the different factors. ")
 
     def _download(self, order, Ks, conv, updated_spatial=True):
         eng = self._engine
@@ -344,11 +422,13 @@ class FASST(object):
             return logliks
         rows = np.array(rows, dtype=np.float64)
         order, Ks, conv = self._upload()
+        self._warn_constr(order)
         i0 = 0
         while i0 < self.iter_num:
             ll, done, mask = self._engine.run(rows[i0:], self.nmfUpdateCoeff)
             logliks[i0:i0 + done] = ll
             i0 += done
+            self._download_constr(order, done)
             if mask:
                 self._download(order, Ks, conv)
                 self._restart_tw(mask, order)
@@ -364,8 +444,10 @@ class FASST(object):
         """One GEM iteration with the current noise PSD (audioModel.py:384-428)."""
         order, Ks, conv = self._upload()
         psd = np.asarray(self.noise['PSD'], dtype=np.float64) * np.ones(self.nbFreqsSigRepr)
+        self._warn_constr(order)
         ll, done, mask = self._engine.run(psd[None, :], self.nmfUpdateCoeff)
         self._download(order, Ks, conv)
+        self._download_constr(order, done)
         if mask:
             self._restart_tw(mask, order)
         return ll[0]
@@ -440,8 +522,10 @@ class FASST(object):
         """FB / FW / TW (TB) updates from hat_W [J, F, T] on the device
         (audioModel.py:1469-1978); no renormalisation."""
         order, Ks, conv = self._upload()
+        self._warn_constr(order)
         self._engine.spectral_update(hat_W, self.nmfUpdateCoeff)
         self._download(order, Ks, conv, updated_spatial=False)
+        self._download_constr(order)
 
     def _colmask(self, spat_ind, spec_comp_ind, order):
         keys = spec_comp_ind if len(spec_comp_ind) else order[spat_ind]
@@ -894,3 +978,34 @@ class MultiChanNMFConv(MultiChanNMFInst_FASST):
                 p = np.zeros([self.rank[nspat], nc, self.nbFreqsSigRepr], dtype=complex)
                 p[:] = inst.T[:, :, None]
                 spat_comp['params'] = p
+
+
+class MultiChanHMM(MultiChanNMFConv):
+    """A MultiChanNMFConv whose time weights can be turned into hidden Markov
+    model state sequences (audioModel.py:2510-2549)."""
+
+    def __init__(self, audio, nbComps=3, nbNMFComps=4, spatial_rank=2, **kwargs):
+        super(MultiChanHMM, self).__init__(audio=audio, nbComps=nbComps,
+                                           nbNMFComps=nbNMFComps,
+                                           spatial_rank=spatial_rank, **kwargs)
+
+    def makeItHMM(self):
+        """HMM time constraints (audioModel.py:2525-2532).  The reference's
+        'HMM' cannot complete an iteration (renormalize_parameters raises,
+        :2038-2040); estimation refuses it up front."""
+        for spec_ind, spec_comp in self.spec_comps.items():
+            for fac_ind, factor in spec_comp['factor'].items():
+                factor['TW_constr'] = 'HMM'
+                factor['TW_DP_frdm_prior'] = 'free'
+
+    def makeItSHMM(self):
+        """SHMM time constraints (audioModel.py:2534-2549): transitions
+        9 I + 1, row-normalised, fixed."""
+        for spec_ind, spec_comp in self.spec_comps.items():
+            for fac_ind, factor in spec_comp['factor'].items():
+                nbfaccomps = factor['TW'].shape[0]
+                factor['TW_constr'] = 'SHMM'
+                factor['TW_DP_params'] = 9 * np.eye(nbfaccomps)
+                factor['TW_DP_params'] += 1.
+                factor['TW_DP_params'] /= np.vstack(factor['TW_DP_params'].sum(axis=1))
+                factor['TW_DP_frdm_prior'] = 'fixed'

@@ -71,6 +71,16 @@ struct fasst_ctx {
   int nsrc = 0, toff[fasst::kMaxSlot + 1] = {0}, tj[fasst::kMaxSlot] = {0};
   unsigned long long tmask[fasst::kMaxSlot][2] = {{0}};   // 128-bit column sets
   fasst::DBuf<double2> A, Pinst;
+  // discrete-state time weights (fasst_set_tw_constr, fasst_twc.hip): twc[j] =
+  // 0 NMF, 1 GSMM, 2 SHMM on source j's only spectral component; twc_free[j]:
+  // TW_DP_frdm_prior == 'free'.  twall [J][KP][Tp] = TW_all, twdp [J][KP][KP]
+  // the state prior (GSMM: row 0) / transition matrix, isdiv [J][KP][Tp],
+  // twante [J][Tp][KP] the Viterbi's antecedents, twstate [J][Tp] the last
+  // decoded sequence; allocated by the first constrained source.  anytwc
+  // routes the iteration through the unfused renormalisation
+  int twc[fasst::kMaxJ] = {0}, twc_free[fasst::kMaxJ] = {0}, anytwc = 0;
+  fasst::DBuf<double> twall, twdp, isdiv;
+  fasst::DBuf<int> twante, twstate;
   // work space
   int nchunk_e = 1, tpc_e = 1, nchunk_b = 1, tpc_b = 1, nacc = 0;
   int nsplit_t = 1, fpc_t = 1;  // TW contraction bin chunks
@@ -105,7 +115,7 @@ struct fasst_ctx {
   // per-kernel HIP-event timing (fasst_set_profiling / fasst_kernel_times)
   // (events on the stream each kernel runs on, the side-stream fork kept, a
   // ring of kProfRing iterations between host syncs: the timed schedule)
-  static constexpr int kNK = 15, kProfRing = 32;
+  static constexpr int kNK = 17, kProfRing = 32;
   int prof = 0, pslot = 0;
   hipEvent_t ev0[kNK][kProfRing] = {}, ev1[kNK][kProfRing] = {};
   int used[kNK][kProfRing] = {{0}};

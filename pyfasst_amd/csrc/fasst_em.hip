@@ -24,6 +24,7 @@
 // because the mixing a_r is constant over t.  The t-reductions shrink from
 // R^2 complex products per (f,t) to J(J+1)/2 x 4 + 9J real FMAs.
 #include "fasst_ctx.h"
+#include "fasst_twc.h"
 
 #include <cmath>
 #include <cstring>
@@ -3521,12 +3522,12 @@ __global__ __launch_bounds__(256) void k_tb_renorm(const TBRArgs a) {
 
 // ---------------------------------------------------------------- host side
 enum KernelId {
-  KW = 0, KFWH, KINSTA, KESTEP, KLL, KMIX, KMIXI, KFBC, KFBU, KTWC, KREN, KTWU, KFWU, KROWS, KRTAIL
+  KW = 0, KFWH, KINSTA, KESTEP, KLL, KMIX, KMIXI, KFBC, KFBU, KTWC, KREN, KTWU, KFWU, KROWS, KRTAIL, KTWD, KTWV
 };
 static const char *kKernelNames[fasst_ctx::kNK] = {
     "k_w_from_fb", "k_fwh_t", "k_inst_A", "k_estep", "k_loglik", "k_mix",
     "k_mix_inst", "k_fb_contract", "k_fb_update", "k_tw_contract", "k_renorm", "k_tw_update",
-    "k_fw_update", "k_tw_rowsum", "k_renorm_tail"};
+    "k_fw_update", "k_tw_rowsum", "k_renorm_tail", "k_tw_statediv", "k_tw_decode"};
 
 // per-kernel timing: an event pair around the launch on the stream it runs on
 // (s = nullptr: the main stream), slot = the iteration's place in the ring
@@ -3679,6 +3680,8 @@ int configure_model(fasst_ctx *c, int J, const int *rank, const int *K, const in
       c->tbl[j][b] = c->btb[j][b] = 0;
     }
   c->anytb = 0;
+  for (int j = 0; j < kMaxJ; ++j) c->twc[j] = c->twc_free[j] = 0;
+  c->anytwc = 0;
   c->nsrc = 0;
   c->lambda = 0.0;
   c->nseq = 0;
@@ -3957,7 +3960,7 @@ static int launch_renorm(fasst_ctx *c, int iter) {
 // Every form is tested against the others and the oracle, halted batches
 // included (tests/test_gpu_fast_tail.py).
 static bool fast_tail(const fasst_ctx *c) {
-  if (!c->ftail || c->multi || c->anytb) return false;
+  if (!c->ftail || c->multi || c->anytb || c->anytwc) return false;
   for (int j = 0; j < c->J; ++j)
     if (c->fw_free[j]) return false;
   return true;
@@ -4226,6 +4229,27 @@ static int check_tail_args(const fasst_ctx *c, const UArgs &u, const TUArgs &tu)
   return FASST_ERR_SHAPE;
 }
 
+// source j's TW step is the discrete-state one (fasst_set_tw_constr)
+static inline bool twc_on(const fasst_ctx *c, int j) { return c->twc[j] && c->tw_free[j]; }
+
+// The discrete-state TW step (:1728-1928) of the marked sources, after the
+// FB / FW updates and before W_new replaces W: k_tw_statediv, k_tw_decode.
+// plane_is_hatw: c->hatW holds hat_W (multi_step's first k_multi_prep turned
+// every source's rho into hat_W in place), else the E-step's rho
+static int launch_tw_constr(fasst_ctx *c, double omega, bool plane_is_hatw) {
+  bool any = false;
+  for (int j = 0; j < c->J; ++j) any |= twc_on(c, j);
+  if (!any) return FASST_OK;
+  prof_begin(c, KTWD);
+  int st = launch_tw_statediv(c, omega, plane_is_hatw);
+  prof_end(c, KTWD);
+  if (st) return st;
+  prof_begin(c, KTWV);
+  st = launch_tw_decode(c);
+  prof_end(c, KTWV);
+  return st;
+}
+
 static int multi_step(fasst_ctx *c, double omega, int b, int only_j) {
   const int J = c->J, nkc = c->KP / 16;
   const size_t plane = (size_t)J * c->Tp * c->Fp;
@@ -4330,7 +4354,7 @@ static int multi_step(fasst_ctx *c, double omega, int b, int only_j) {
       mp.kb0[j] = u.kb0[j] = t.kb0[j] = tu.kb0[j] = k0;
       mp.kb1[j] = u.kb1[j] = t.kb1[j] = tu.kb1[j] = k1;
       bb.fb_free[j] = u.fb_free[j] = has && c->bfb[j][b];
-      t.tw_free[j] = has && c->btw[j][b];
+      t.tw_free[j] = has && c->btw[j][b] && !c->twc[j];
       tu.tw_free[j] = t.tw_free[j] && !tbw.tb[j];   // time blobs: k_tb_tw_red / apply
     }
     const dim3 gp(c->nft, J, c->nchunk_b);
@@ -4484,6 +4508,8 @@ static int multi_step(fasst_ctx *c, double omega, int b, int only_j) {
       FASST_LAUNCH_CHECK();
       if (int st = launch_tb_h(c, tbb)) return st;
     }
+    if (c->anytwc && b == 0)   // (a constrained source has one component: block 0)
+      if (int st = launch_tw_constr(c, omega, true)) return st;
     // the step's W = FB FW is the current W of the next step
     FASST_HIP(hipMemcpyAsync(c->Wkf.p, c->Wkf_new.p, (size_t)J * c->KP * c->Fp * sizeof(double),
                              hipMemcpyDeviceToDevice, c->stream));
@@ -4542,6 +4568,11 @@ static int spectral_update(fasst_ctx *c, double omega, bool tail = false) {
   const int nkc = c->KP / 16;
   bool any_fw = false;
   for (int j = 0; j < J; ++j) any_fw |= c->fw_free[j] != 0;
+  if (c->anytwc && c->lambda > 0.0) {
+    set_error("a discrete-state TW (TW_constr GSMM / SHMM) with lambdaCorr > 0 is outside the "
+              "HIP path");
+    return FASST_ERR_UNSUPPORTED;
+  }
   if (c->multi) return multi_spectral(c, omega);
   BArgs b{};
   b.TW = c->TW.p;
@@ -4629,7 +4660,7 @@ static int spectral_update(fasst_ctx *c, double omega, bool tail = false) {
     const bool in = j < J;
     tu.kb0[j] = u.kb0[j] = t.kb0[j] = 0;
     tu.kb1[j] = u.kb1[j] = t.kb1[j] = in ? c->K[j] : 0;
-    t.tw_free[j] = tu.tw_free[j] = in ? c->tw_free[j] : 0;
+    t.tw_free[j] = tu.tw_free[j] = in ? (c->tw_free[j] && !c->twc[j]) : 0;
     u.fb_free[j] = in ? c->fb_free[j] : 0;
   }
   switch (nkc) {
@@ -4711,6 +4742,7 @@ static int spectral_update(fasst_ctx *c, double omega, bool tail = false) {
   k_tw_update<<<dim3(c->ntb, J), 256, prep ? (size_t)c->KP * 64 * sizeof(double) : 0, c->stream>>>(tu);
   prof_end(c, KTWU);
   FASST_LAUNCH_CHECK();
+  if (c->anytwc) return launch_tw_constr(c, omega, false);
   return FASST_OK;
 }
 
@@ -5086,6 +5118,10 @@ int fasst_set_blocks(fasst_ctx *c, int j, int nblk, const int *kb, const int *fb
   bool same = c->nblk[j] == nblk;
   for (int b = 0; same && b <= nblk; ++b) same = c->kb[j][b] == kb[b];
   c->nblk[j] = nblk;
+  if (nblk > 1 && c->twc[j]) {   // a discrete-state TW needs the source's only component
+    c->twc[j] = c->twc_free[j] = c->anytwc = 0;
+    for (int i = 0; i < c->J; ++i) c->anytwc |= c->twc[i] != 0;
+  }
   for (int b = 0; b <= nblk; ++b) c->kb[j][b] = kb[b];
   bool fbf = false, twf = false, fwf = false;
   for (int b = 0; b < nblk; ++b) {
@@ -5183,6 +5219,10 @@ int fasst_set_tb(fasst_ctx *c, int j, int b, int L, const double *TW, const doub
                              hipMemcpyHostToDevice, c->stream));
   c->tbl[j][b] = L;
   c->btb[j][b] = tb_free ? 1 : 0;
+  if (c->twc[j]) {   // time blobs and a discrete-state TW exclude each other (:1736-1742)
+    c->twc[j] = c->twc_free[j] = c->anytwc = 0;
+    for (int i = 0; i < c->J; ++i) c->anytwc |= c->twc[i] != 0;
+  }
   update_multi(c);
   c->halt = nullptr;
   TBArgs a = tb_args(c, b, j, 0, 1.0);   // H = TW TB into the block's rows

@@ -161,6 +161,37 @@ class Engine(object):
         check(lib.fasst_get_tb(self._h, int(j), int(b), dptr(TW), dptr(TB)), "fasst_get_tb")
         return TW, TB
 
+    TW_CONSTR_KINDS = {'NMF': 0, 'GSMM': 1, 'SHMM': 2}
+
+    def set_tw_constr(self, j, constr, TW_all=None, dp=None, dp_free=False):
+        """TW_constr of source j's spectral component (fasst_set_tw_constr):
+        'NMF', 'GSMM' or 'SHMM'; TW_all K x T or None (max_k TW[k, t] in every
+        row), dp the state priors [K] / transitions [K, K] or None (1 / K)."""
+        kind = self.TW_CONSTR_KINDS[constr]
+        K = self.structure[1][j]
+        a = d = None
+        if kind and TW_all is not None:
+            a = np.ascontiguousarray(TW_all, dtype=np.float64)
+            if a.shape != (K, self.T):
+                raise ValueError("TW_all %s for K=%d, T=%d" % (a.shape, K, self.T))
+        if kind and dp is not None:
+            d = np.ascontiguousarray(dp, dtype=np.float64)
+            if d.shape != ((K,) if kind == 1 else (K, K)):
+                raise ValueError("TW_DP_params %s for %s with K=%d" % (d.shape, constr, K))
+        check(lib.fasst_set_tw_constr(self._h, int(j), kind, None if a is None else dptr(a),
+                                      None if d is None else dptr(d), int(bool(dp_free))),
+              "fasst_set_tw_constr")
+
+    def get_tw_constr(self, j, constr):
+        """(TW_all [K, T], TW_DP_params [K] or [K, K], decoded states int32 [T])."""
+        K = self.structure[1][j]
+        a = np.empty((K, self.T))
+        d = np.empty((K,) if self.TW_CONSTR_KINDS[constr] == 1 else (K, K))
+        s = np.zeros(self.T, dtype=np.int32)
+        check(lib.fasst_get_tw_constr(self._h, int(j), dptr(a), dptr(d), iptr(s)),
+              "fasst_get_tw_constr")
+        return a, d, s
+
     def get_spectral(self, j, K):
         FB = np.empty((self.F, K))
         FW = np.empty((K, K))

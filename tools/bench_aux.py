@@ -16,6 +16,10 @@
                     (separate_spatial_filter_comp, audioModel.py:891-1061):
                     per-bin gains + the 2 J iSTFTs with the gain applied on
                     load (fasst_spatial_filter_waveforms), host-inclusive
+  --workload hmm    the C3 model (bench.py build_model) with every source's
+                    time weights SHMM at K = 32 (TW_constr, audioModel.py:
+                    1728-1928): ms per GEM iteration, and the two kernels of
+                    the discrete-state TW step from fasst_kernel_times
   --workload viterbi  melody tracking (_tracking.pyx:11-93) at config 5:
                     S = 1092 F0 states, N = 20000 frames (runViterbi's
                     transitions, stepNotes 16): tracks/s, device time
@@ -180,6 +184,44 @@ def bench_spatial(steps, warmup):
                                    % (J, m.nbFreqsSigRepr, m.nbFramesSigRepr, nfft, hop)},
             "waveform_bytes_to_host": int(Y.nbytes),
             "images_path_ms": round(di * 1e3, 3), "image_bytes_to_host": int(S.nbytes)}
+
+
+def bench_hmm(steps, warmup):
+    """C3 with every source SHMM at K = 32: ms per GEM iteration (device
+    batch, one host sync), then a profiled batch for the per-kernel times."""
+    sys.path.insert(0, ROOT)
+    import bench as B
+    m = B.build_model(seed=0, device=0)
+    for comp in m.spec_comps.values():
+        fac = comp['factor'][0]
+        fac['TW_constr'] = 'SHMM'
+        fac['TW_DP_frdm_prior'] = 'free'
+    eng = m._engine
+    m._upload()
+    F, T = m.nbFreqsSigRepr, m.nbFramesSigRepr
+    rows = np.array([m._annealed_psd(0)] * max(steps, warmup, 1), dtype=np.float64)
+    eng.run(rows[:max(warmup, 1)], 1.0)
+    t0 = time.perf_counter()
+    eng.run(rows[:steps], 1.0)
+    dt = (time.perf_counter() - t0) / steps
+    eng.set_profiling(True)
+    eng.run(rows[:steps], 1.0)
+    kt = eng.kernel_times()
+    eng.set_profiling(False)
+    J, K = len(m.spat_comps), m.nbNMFComps
+    div_ms = kt.get("k_tw_statediv", (0.0, 0))[0]
+    rho_bytes = 8.0 * J * F * T          # one read of rho per source
+    return {"metric": "GEM iteration, every source SHMM (discrete-state TW step)",
+            "value": round(dt * 1e3, 3), "unit": "ms", "higher_is_better": False,
+            "steps": steps, "warmup": warmup, "dtype": "f64",
+            "data": "synthetic C3 model (bench.py build_model, seed 0)",
+            "config": {"workload": "F=%d T=%d J=%d K=%d SHMM, free transitions" % (F, T, J, K)},
+            "k_tw_statediv_ms": round(div_ms, 4),
+            "k_tw_decode_ms": round(kt.get("k_tw_decode", (0.0, 0))[0], 4),
+            "statediv_hbm_fraction": round(rho_bytes / (div_ms * 1e-3) / 8.0e12, 4)
+            if div_ms else None,
+            "statediv_logs": int(J) * int(K) * int(F) * int(T),
+            "kernel_ms": {k: round(v[0], 4) for k, v in sorted(kt.items())}}
 
 
 def bench_nmf(steps, warmup, F=1025, N=2000, K=64, seed=0):
@@ -382,7 +424,7 @@ def bench_viterbi(steps, warmup, S=1092, N=20000, seed=0):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=("simm", "nmf", "cqt", "viterbi", "wf0", "separate",
-                                           "nnls", "spatial"),
+                                           "nnls", "spatial", "hmm"),
                     required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -393,7 +435,7 @@ def main():
     NO_CPU = a.no_cpu_baseline
     fn = {"simm": bench_simm, "nmf": bench_nmf, "cqt": bench_cqt, "viterbi": bench_viterbi,
           "wf0": bench_wf0, "separate": bench_separate, "nnls": bench_nnls,
-          "spatial": bench_spatial}[a.workload]
+          "spatial": bench_spatial, "hmm": bench_hmm}[a.workload]
     out = fn(a.steps, a.warmup)
     if NO_CPU:
         out["cpu_baseline"] = None   # not measured (the sample above timed nothing)
