@@ -45,8 +45,10 @@ typedef struct fasst_ctx fasst_ctx;
  * mask by value), so a revision-1 caller would pass too short an array.
  * Revision 3 adds the time-invariant spatial filter (fasst_spatial_filter_*)
  * and fasst_gcc_phat.  Revision 4 adds the discrete-state time weights
- * (fasst_set_tw_constr / fasst_get_tw_constr). */
-#define FASST_ABI_VERSION 4
+ * (fasst_set_tw_constr / fasst_get_tw_constr).  Revision 5 adds the two-factor
+ * (source / filter) spectral components (fasst_sf_* and fasst_set_factors /
+ * fasst_get_factors). */
+#define FASST_ABI_VERSION 5
 int fasst_abi_version(void);
 
 const char *fasst_last_error(void);
@@ -233,6 +235,52 @@ int fasst_spatial_filter_waveforms(fasst_ctx *ctx, const double *window,
  * (fasst_set_audio / fasst_set_stft / fasst_set_cx); needs nfft/2+1 == F.  A
  * bin whose cross-spectrum is zero is 0/0 = NaN, as in the reference.        */
 int fasst_gcc_phat(fasst_ctx *ctx, int nfft, double *out);
+
+/* ---- two-factor (source / filter) spectral components --------------------
+ * A model whose spectral components have one or two factors, V_j = prod_i
+ * (FB_i.FW_i).TW_i (comp_spat_comp_power, audioModel.py:430-498; the reference's
+ * multiChanSourceF0Filter, :2551-2900), runs on a state of its own beside the
+ * single-factor model above (fasst_sf.hip): the powers are held as F x T
+ * planes on the device and no F x T array crosses to the host during
+ * fasst_sf_run.  Every spatial component has exactly one spectral component;
+ * every factor is TW_constr 'NMF' without time blobs; lambdaCorr is 0.
+ *
+ * fasst_sf_configure replaces any model of the context (fasst_configure* drops
+ * it again): J spatial components, rank[J] (sum <= 16, the explicit-V E-step),
+ * mix_conv[J] (0 'inst', 1 'conv'), nfac[J] in {1, 2}, and per (j, i) at index
+ * 2 j + i: Kb, Kw (FB F x Kb, FW Kb x Kw -- not square in general -- TW Kw x T)
+ * and priors[3 (2 j + i) + {0, 1, 2}] = FB / FW / TW 'free';
+ * alias[3 (2 j + i) + {0, 1, 2}] = -1, or the index 2 j' + i' of an earlier
+ * factor whose FB / FW / TW this factor shares (the reference's source
+ * dictionary is one array in every component and is rescaled in place by
+ * each of them, audioModel.py:2679-2680,2003-2021): one device buffer.
+ * fasst_sf_set_spatial / fasst_sf_get_spatial: params as fasst_set_spatial.
+ * fasst_set_factors / fasst_get_factors: the three matrices of factor i of
+ * component j, row-major float64, caller-owned (get: any may be NULL).
+ * fasst_sf_renormalize / fasst_sf_run: as fasst_renormalize / fasst_run; bit
+ * 2 j + i of restart_mask is factor i of component j: the caller redraws TW,
+ * and for a factor that is not the last divides it by its mean and performs
+ * the whole renormalisation of the next factor with that mean as its energy
+ * (the device left that factor alone; audioModel.py:2003-2036 hands
+ * `global_energy` from factor to factor).
+ * fasst_sf_wiener_images / fasst_sf_separate_waveforms: as fasst_wiener_images
+ * (resident STFT only) / fasst_separate_waveforms with the sources given here:
+ * source n sums the spatial components j with src_of[j] == n (-1: in none);
+ * S out complex128 [nsrc][2][F][T], y out float64 [nsrc][2][len].            */
+int fasst_sf_configure(fasst_ctx *ctx, int J, const int *rank, const int *mix_conv, const int *nfac,
+                       const int *Kb, const int *Kw, const int *priors, const int *alias);
+int fasst_sf_set_spatial(fasst_ctx *ctx, int j, const double *params, int free_);
+int fasst_sf_get_spatial(fasst_ctx *ctx, int j, double *params);
+int fasst_set_factors(fasst_ctx *ctx, int j, int i, const double *FB, const double *FW,
+                      const double *TW);
+int fasst_get_factors(fasst_ctx *ctx, int j, int i, double *FB, double *FW, double *TW);
+int fasst_sf_renormalize(fasst_ctx *ctx, int *restart_mask);
+int fasst_sf_run(fasst_ctx *ctx, int n_iter, const double *psd, double omega, double *logliks,
+                 int *restart_mask, int *iters_done);
+int fasst_sf_wiener_images(fasst_ctx *ctx, const double *psd, int nsrc, const int *src_of, double *S);
+int fasst_sf_separate_waveforms(fasst_ctx *ctx, const double *psd, int nsrc, const int *src_of,
+                                const double *window, const double *analysis_window, int wlen,
+                                int nfft, int hop, double *y);
 
 /* Per-kernel timing with HIP events (used by bench.py for the roofline of
  * the dominant kernel), in the timed loop's own schedule: each pair is

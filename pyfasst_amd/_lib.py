@@ -97,6 +97,16 @@ SIGNATURES = {
                                         _dp, _dp]),
     "fasst_inv_sigma_mix": (ctypes.c_int, [ctypes.c_int] * 4 + [_dp, _dp, _dp, _dp, _dp]),
     "fasst_wiener_gain": (ctypes.c_int, [ctypes.c_int, ctypes.c_long, _dp, _dp, _dp, _dp, _dp]),
+    "fasst_sf_configure": (ctypes.c_int, [_vp, ctypes.c_int, _ip, _ip, _ip, _ip, _ip, _ip, _ip]),
+    "fasst_sf_set_spatial": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_int]),
+    "fasst_sf_get_spatial": (ctypes.c_int, [_vp, ctypes.c_int, _dp]),
+    "fasst_set_factors": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp]),
+    "fasst_get_factors": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp]),
+    "fasst_sf_renormalize": (ctypes.c_int, [_vp, _ip]),
+    "fasst_sf_run": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_double, _dp, _ip, _ip]),
+    "fasst_sf_wiener_images": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _ip, _dp]),
+    "fasst_sf_separate_waveforms": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _ip, _dp, _dp,
+                                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp]),
     # include/fasst_simm.h
     "simm_create": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(_vp)]),
     "simm_destroy": (ctypes.c_int, [_vp]),
@@ -154,8 +164,9 @@ for _name, (_res, _args) in SIGNATURES.items():
 # include/fasst_hip.h FASST_ABI_VERSION these signatures were written against
 # (revision 2: 128-bit column sets in fasst_source_powers / fasst_sigma_comp;
 # revision 3: fasst_spatial_filter_* and fasst_gcc_phat; revision 4:
-# fasst_set_tw_constr / fasst_get_tw_constr)
-ABI_VERSION = 4
+# fasst_set_tw_constr / fasst_get_tw_constr; revision 5: the two-factor model,
+# fasst_sf_* and fasst_set_factors / fasst_get_factors)
+ABI_VERSION = 5
 if lib.fasst_abi_version() != ABI_VERSION:
     raise ImportError("pyfasst_amd: %s has ABI revision %d, this binding expects %d; rebuild it "
                       "(make -C pyfasst_amd/csrc)" % (LIB_PATH, lib.fasst_abi_version(), ABI_VERSION))

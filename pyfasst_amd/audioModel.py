@@ -199,13 +199,16 @@ class FASST(object):
         J = len(self.spat_comps)
         if sorted(self.spat_comps.keys()) != list(range(J)):
             raise NotImplementedError("spatial components must be numbered 0..J-1")
+        if self._is_sf():
+            return self._structure_sf()
         owner = {}
         for k in sorted(self.spec_comps.keys()):
             comp = self.spec_comps[k]
             owner.setdefault(comp['spat_comp_ind'], []).append(k)
             facs = comp['factor']
             if list(facs.keys()) != [0]:
-                raise NotImplementedError("multi-factor spectral components are outside the HIP path")
+                raise NotImplementedError("spectral component %d: factor keys %s (a single factor "
+                                          "has key 0)" % (k, list(facs.keys())))
             fac = facs[0]
             if len(fac['TB']):
                 TB = np.asarray(fac['TB'])
@@ -258,6 +261,197 @@ class FASST(object):
             Ks.append(int(sum(self.spec_comps[k]['factor'][0]['FB'].shape[1] for k in owner[j])))
         return [owner[j] for j in range(J)], ranks, Ks, (all(conv) if len(set(conv)) == 1 else conv)
 
+    # ---------------------------------------------------------------- two factors
+    SF_MAX_K = 128    # Kb, Kw of a factor on the two-factor path
+    SF_MAX_RANK = 16  # total spatial rank: the explicit-V E-step k_suff_stat
+
+    def _is_sf(self):
+        """A model with a multi-factor spectral component: the two-factor
+        (source / filter) path, fasst_sf.hip."""
+        return any(len(c['factor']) > 1 for c in self.spec_comps.values())
+
+    def _structure_sf(self):
+        """The two-factor path: every spatial component has
+        exactly one spectral component of one or two factors (keys 0 or 0, 1),
+        each TW_constr 'NMF' without time blobs, FB F x Kb, FW Kb x Kw (not
+        square in general), TW Kw x T with 1 <= Kb, Kw <= 128, FB / FW / TW
+        independently free or fixed; lambdaCorr == 0; total spatial rank <=
+        16; the spatial components as on the single-factor path.  Anything
+        else raises NotImplementedError here, before any upload.  Returns
+        (order, ranks, None, conv)."""
+        J = len(self.spat_comps)
+        what = "next to a two-factor spectral component"
+        if self.lambdaCorr > 0:
+            raise NotImplementedError("lambdaCorr > 0 %s is outside the HIP path" % what)
+        owner = {}
+        for k in sorted(self.spec_comps.keys()):
+            comp = self.spec_comps[k]
+            owner.setdefault(comp['spat_comp_ind'], []).append(k)
+            keys = list(comp['factor'].keys())
+            if len(keys) >= 3:
+                raise NotImplementedError("spectral component %d has %d factors: the HIP path "
+                                          "takes one or two" % (k, len(keys)))
+            if keys not in ([0], [0, 1]):
+                raise NotImplementedError("spectral component %d: factor keys %s (0 or 0, 1)"
+                                          % (k, keys))
+            for fi, fac in comp['factor'].items():
+                if len(fac['TB']):
+                    raise NotImplementedError("time blobs TB (spectral component %d factor %d) "
+                                              "%s are outside the HIP path" % (k, fi, what))
+                if fac.get('TW_constr', 'NMF') != 'NMF':
+                    raise NotImplementedError("TW_constr=%s (spectral component %d factor %d): "
+                                              "a discrete-state constraint %s is outside the HIP "
+                                              "path" % (fac.get('TW_constr'), k, fi, what))
+                shp = [np.shape(fac[p]) for p in ('FB', 'FW', 'TW')]
+                if any(len(x) != 2 for x in shp) or shp[0][0] != self.nbFreqsSigRepr or \
+                        shp[1][0] != shp[0][1] or shp[2][0] != shp[1][1] or \
+                        shp[2][1] != self.nbFramesSigRepr:
+                    raise ValueError("spectral component %d factor %d: FB %s, FW %s, TW %s for "
+                                     "F=%d, T=%d" % ((k, fi) + tuple(shp) + (
+                                         self.nbFreqsSigRepr, self.nbFramesSigRepr)))
+                if min(shp[1]) < 1 or max(shp[1]) > self.SF_MAX_K:
+                    raise NotImplementedError("spectral component %d factor %d: Kb=%d, Kw=%d "
+                                              "outside 1..%d %s" % ((k, fi) + shp[1] + (
+                                                  self.SF_MAX_K, what)))
+        if sorted(owner.keys()) != list(range(J)):
+            raise NotImplementedError("every spatial component needs a spectral component")
+        for j, keys in owner.items():
+            if len(keys) > 1:
+                raise NotImplementedError("spatial component %d has %d spectral components: %s "
+                                          "every spatial component takes exactly one"
+                                          % (j, len(keys), what))
+        conv = [self.spat_comps[j]['mix_type'] == 'conv' for j in range(J)]
+        free = [self.spat_comps[j]['frdm_prior'] == 'free' for j in range(J)]
+        if any(c and f for c, f in zip(conv, free)) and not all(c and f for c, f in zip(conv, free)):
+            raise ValueError("update_mix_matrix: free 'conv' spatial components next to fixed or "
+                             "'inst' ones (audioModel.py:856-857 solves hat_Rss[f].T of all %d "
+                             "components against the free components' right-hand side only)" % J)
+        ranks = []
+        for j in range(J):
+            p = self.spat_comps[j]['params']
+            ranks.append(p.shape[0] if conv[j] else p.shape[1])
+        # the device walks the components in spatial-component order, the
+        # reference in key order: they differ only when a matrix is shared
+        # (rescaled and updated in place, in order) and the map is not monotone
+        own = [self.spec_comps[k]['spat_comp_ind'] for k in sorted(self.spec_comps.keys())]
+        ids = [id(f[p]) for c in self.spec_comps.values() for f in c['factor'].values()
+               for p in ('FB', 'FW', 'TW') if isinstance(f[p], np.ndarray)]
+        if own != sorted(own) and len(ids) != len(set(ids)):
+            raise NotImplementedError("a matrix shared between factors, with spectral component "
+                                      "keys not in the order of their spatial components, %s is "
+                                      "outside the HIP path" % what)
+        if sum(ranks) > self.SF_MAX_RANK:
+            raise NotImplementedError("total spatial rank %d above %d (the explicit-V E-step) %s"
+                                      % (sum(ranks), self.SF_MAX_RANK, what))
+        return [owner[j] for j in range(J)], ranks, None, conv
+
+    def _refuse_sf(self, name):
+        if self._is_sf():
+            raise NotImplementedError("%s: not available on a model with a two-factor spectral "
+                                      "component (DESIGN.md 7.2)" % name)
+
+    def _upload_sf(self, order, ranks, conv):
+        eng = self._engine
+        factors, alias, seen = [], [], {}
+        for j, keys in enumerate(order):
+            facs = self.spec_comps[keys[0]]['factor']
+            fl, al = [], []
+            for i in sorted(facs.keys()):
+                f = facs[i]
+                fl.append((f['FB'].shape[1], np.shape(f['FW'])[1],
+                           f.get('FB_frdm_prior', 'free') == 'free',
+                           f.get('FW_frdm_prior', 'fixed') == 'free',
+                           f.get('TW_frdm_prior', 'free') == 'free'))
+                # one array object in several factors: one device buffer
+                a = []
+                for q, part in enumerate(('FB', 'FW', 'TW')):
+                    key = (q, id(f[part]))
+                    a.append(seen.get(key, -1) if isinstance(f[part], np.ndarray) else -1)
+                    seen.setdefault(key, 2 * j + i)
+                al.append(tuple(a))
+            factors.append(fl)
+            alias.append(al)
+        key = (tuple(ranks), tuple(conv), repr(factors), repr(alias))
+        if not eng.sf or getattr(eng, '_sf_key', None) != key:
+            eng.sf_configure(ranks, conv, factors, alias)
+            eng._sf_key = key
+        for j, keys in enumerate(order):
+            sc = self.spat_comps[j]
+            eng.sf_set_spatial(j, sc['params'], sc['frdm_prior'] == 'free')
+            facs = self.spec_comps[keys[0]]['factor']
+            for i in sorted(facs.keys()):
+                eng.set_factors(j, i, facs[i]['FB'], facs[i]['FW'], facs[i]['TW'])
+        return order, None, conv
+
+    def _download_sf(self, order, updated_spatial=True):
+        eng = self._engine
+        for j, keys in enumerate(order):
+            sc = self.spat_comps[j]
+            p = eng.sf_get_spatial(j, sc['params'].shape)
+            if not np.iscomplexobj(sc['params']) and not (updated_spatial and
+                                                          sc['frdm_prior'] == 'free'):
+                p = p.real.copy()
+            sc['params'] = p
+            facs = self.spec_comps[keys[0]]['factor']
+            for i in sorted(facs.keys()):
+                for part, val in zip(('FB', 'FW', 'TW'), eng.get_factors(j, i)):
+                    cur = facs[i][part]
+                    if isinstance(cur, np.ndarray) and cur.shape == val.shape \
+                            and cur.dtype == val.dtype and cur.flags.writeable:
+                        cur[...] = val
+                    else:
+                        facs[i][part] = val
+
+    def _renorm_factor_host(self, k, i, fac, ge, divide):
+        """One factor's renormalisation on the host (audioModel.py:2006-2036,
+        no time blobs), on its F x Kb, Kb x Kw and Kw x T matrices: used
+        where the device cannot finish one (after a TW redraw) and for the
+        initial state of multiChanSourceF0Filter.  Returns mean(TW), the
+        `global_energy` the reference hands to the next factor."""
+        fac['FB'] *= ge
+        w = fac['FB'].max(axis=0)
+        w[w == 0] = 1.
+        fac['FB'] /= w
+        fac['FW'] *= np.vstack(w)
+        w = fac['FW'].mean(axis=0)
+        w[w == 0] = 1.
+        fac['FW'] /= w
+        fac['TW'] *= np.vstack(w)
+        if np.sum(fac['TW']) < eps:
+            self._redraw_tw(k, i, fac)
+        ge = fac['TW'].mean()
+        if divide:
+            fac['TW'] /= ge
+        return ge
+
+    def _redraw_tw(self, k, i, fac):
+        fac['TW'] = np.random.randn(*fac['TW'].shape) ** 2
+        fac['TW'] *= 1e3 * eps
+        if self.verbose:
+            print("    renorm: reinitialized TW for spec", k, "factor", i)
+
+    def _restart_tw_sf(self, mask, order):
+        """The random TW restart (audioModel.py:2023-2028) and the rest of the
+        component's renormalisation (:2034-2036), in key-then-factor order;
+        bit 2 j + i of mask is factor i of spatial component j.  The reference
+        hands mean(TW) of a factor to the next one as its energy, so the
+        device leaves the factors after a dead one alone: they are
+        renormalised here, with the mean of the redrawn TW."""
+        spat = {order[j][0]: j for j in range(len(order))}
+        for k in sorted(self.spec_comps.keys()):
+            facs = self.spec_comps[k]['factor']
+            keys = sorted(facs.keys())
+            for n, i in enumerate(keys):
+                if not mask & (1 << (2 * spat[k] + i)):
+                    continue
+                self._redraw_tw(k, i, facs[i])
+                ge = facs[i]['TW'].mean()
+                if i < len(facs) - 1:
+                    facs[i]['TW'] /= ge
+                for i2 in keys[n + 1:]:
+                    ge = self._renorm_factor_host(k, i2, facs[i2], ge, i2 < len(facs) - 1)
+                break
+
     @staticmethod
     def _tw_constr(fac):
         """'GSMM' / 'SHMM' when the factor's TW step is the discrete-state one
@@ -277,6 +471,8 @@ class FASST(object):
 
     def _upload(self):
         order, ranks, Ks, conv = self._structure()
+        if Ks is None:
+            return self._upload_sf(order, ranks, conv)
         eng = self._engine
         eng.configure(ranks, Ks, conv)
         for j in range(len(order)):
@@ -342,6 +538,8 @@ class FASST(object):
                           "to take into account the different factors. ")
 
     def _download(self, order, Ks, conv, updated_spatial=True):
+        if Ks is None:
+            return self._download_sf(order, updated_spatial)
         eng = self._engine
         for j in range(len(order)):
             sc = self.spat_comps[j]
@@ -374,6 +572,8 @@ class FASST(object):
         """Random TW restart of renormalize_parameters (audioModel.py:2023-2028),
         drawn on the host RNG in spectral-component key order; mask has one bit
         per spectral component, spatial component by spatial component."""
+        if self._is_sf():
+            return self._restart_tw_sf(mask, order)
         dead = set()
         bit = 0
         for keys in order:
@@ -470,6 +670,7 @@ class FASST(object):
     def retrieve_subsrc_params(self,):
         """(spat_comp_powers [R, F, T], mix_matrix [R, 2, F], rank_part_ind)
         (audioModel.py:514-578); the powers come from the device."""
+        self._refuse_sf('retrieve_subsrc_params')
         order, Ks, conv = self._upload()
         J = len(order)
         rank_part_ind, total = {}, 0
@@ -520,7 +721,12 @@ class FASST(object):
 
     def update_spectral_components(self, hat_W):
         """FB / FW / TW (TB) updates from hat_W [J, F, T] on the device
-        (audioModel.py:1469-1978); no renormalisation."""
+        (audioModel.py:1469-1978); no renormalisation.  NotImplementedError on
+        a model with a two-factor spectral component, as retrieve_subsrc_params,
+        compute_sigma_comp_2d and comp_spat_cmps_powers: the piecewise steps
+        exist for the single-factor path only (estim_param_a_post_model,
+        GEM_iteration, renormalize_parameters and the separation run)."""
+        self._refuse_sf('update_spectral_components')
         order, Ks, conv = self._upload()
         self._warn_constr(order)
         self._engine.spectral_update(hat_W, self.nmfUpdateCoeff)
@@ -540,6 +746,7 @@ class FASST(object):
     def compute_sigma_comp_2d(self, spat_ind, spec_comp_ind):
         """(sigma_comp_diag [2, F, T], sigma_comp_off [F, T]) of one spatial
         component's spectral components (audioModel.py:1327-1372)."""
+        self._refuse_sf('compute_sigma_comp_2d')
         order, Ks, conv = self._upload()
         return self._engine.sigma_comp(spat_ind, self._colmask(spat_ind, spec_comp_ind, order))
 
@@ -629,6 +836,9 @@ class FASST(object):
     def separated_images(self, spec_comp_ind=None):
         """STFT-domain Wiener images S[n, c] = sum_c2 WG_n[c, c2] X[c2], as the
         reference computes before its iSTFT (audioModel.py:1136-1214)."""
+        if self._is_sf():
+            src_of, psd = self._separation_plan_sf(spec_comp_ind)
+            return self._engine.sf_wiener_images(psd, src_of)
         src_spat, psd = self._separation_plan(spec_comp_ind)
         S = self._engine.wiener_images(psd)
         return S[src_spat]
@@ -642,9 +852,36 @@ class FASST(object):
         if getattr(t, 'transformname', None) != 'stft':
             raise NotImplementedError("device-resident separation needs the STFT transform "
                                       "(use separated_images() + tft.invertTransform())")
+        if self._is_sf():
+            src_of, psd = self._separation_plan_sf(spec_comp_ind)
+            Y = self._engine.sf_separate_waveforms(psd, src_of, t.synthWindow, t.window, t.ftlen,
+                                                   t.fthop)
+            return Y[:, :, :t.datalen_init]
         src_spat, psd = self._separation_plan(spec_comp_ind)
         Y = self._engine.separate_waveforms(psd, t.synthWindow, t.window, t.ftlen, t.fthop)
         return Y[src_spat][:, :, :t.datalen_init]
+
+    def _separation_plan_sf(self, spec_comp_ind):
+        """Two-factor model: upload, and (src_of, last annealed PSD), src_of[j]
+        = the source that spatial component j's spectral component belongs to
+        (-1: none).  The per-bin Wiener filter runs from the V_j planes with
+        the formulas of compute_sigma_comp_2d / compute_inv_sigma_mix_2d /
+        compute_Wiener_gain_2d (audioModel.py:1327-1467)."""
+        if spec_comp_ind is None:
+            spec_comp_ind = {n: [n] for n in range(len(self.spec_comps))}
+        order, Ks, conv = self._upload()
+        spat = {keys[0]: j for j, keys in enumerate(order)}
+        src_of = [-1] * len(order)
+        for n in range(len(spec_comp_ind)):
+            for k in spec_comp_ind[n]:
+                if src_of[spat[k]] not in (-1, n):
+                    raise NotImplementedError("a spectral component in two separation sources "
+                                              "is outside the two-factor path")
+                src_of[spat[k]] = n
+        if max(src_of) != len(spec_comp_ind) - 1:
+            raise ValueError("separation sources must each hold a spectral component")
+        psd = np.asarray(self.noise['PSD'], dtype=np.float64) * np.ones(self.nbFreqsSigRepr)
+        return src_of, psd
 
     def _separation_plan(self, spec_comp_ind):
         """Set the engine's separation sources; return (output order, last
@@ -728,6 +965,7 @@ class FASST(object):
     def _spatial_filter_plan(self):
         """The reference's refusals (audioModel.py:947-949, :965-966), then the
         parameters on the device."""
+        self._refuse_sf('separate_spatial_filter_comp')
         if self.audioObject.channels != 2:
             raise NotImplementedError()
         for n in range(len(self.spat_comps)):
@@ -848,6 +1086,7 @@ class FASST(object):
         accepted and unused, as there).  Each component's power comes from
         the device (fasst_source_powers on the uploaded parameters) and the
         sum runs on the host in the list's order."""
+        self._refuse_sf('comp_spat_cmps_powers')
         self._upload()
         V = 0
         for i in spat_comp_ind:
@@ -1009,3 +1248,179 @@ class MultiChanHMM(MultiChanNMFConv):
                 factor['TW_DP_params'] += 1.
                 factor['TW_DP_params'] /= np.vstack(factor['TW_DP_params'].sum(axis=1))
                 factor['TW_DP_frdm_prior'] = 'fixed'
+
+
+class multiChanSourceF0Filter(FASST):
+    """Multichannel source / filter model (audioModel.py:2551-3014): nbComps - 1
+    components whose power is a source factor (the F0 comb dictionary, TW free)
+    times a filter factor (Hann bumps, FW nbFilterComps x nbFilterWeigs and TW
+    free), and one residual NMF component.  Runs on the two-factor path
+    (fasst_sf.hip); the dictionaries are built on the GPU.
+
+    On the device every factor has Kb, Kw <= 128 (FASST._structure_sf).  The
+    reference's default F0 range and step (minF0=39, maxF0=2000,
+    stepnoteF0=16) give a source dictionary of 1093 columns: the model can be
+    constructed (its initial renormalisation runs on the host), but
+    estim_param_a_post_model() and the separation refuse it by name; choose
+    minF0 / maxF0 / stepnoteF0 so that the dictionary has at most 128
+    columns.  A model with `sparsity` set raises
+    NotImplementedError from estim_param_a_post_model(): the reference's
+    schedule needs a host step between iterations and a median filter the
+    package does not have.  initSpecCompsWithLabelAndFiles, initializeFreeMats
+    and the multichanLead subclass are outside the scope."""
+
+    def __init__(self, audio, nbComps=3, nbNMFResComps=1, nbFilterComps=20, nbFilterWeigs=[4, ],
+                 minF0=39, maxF0=2000, minF0search=80, maxF0search=800, stepnoteF0=16,
+                 chirpPerF0=1, spatial_rank=1, sparsity=None, **kwargs):
+        from .SeparateLeadStereo import separateLeadFunctions as slf
+        super(multiChanSourceF0Filter, self).__init__(audio=audio, **kwargs)
+        self.comp_transf_Cx()
+        self.sourceParams = {'minF0': minF0, 'maxF0': maxF0, 'stepnoteF0': stepnoteF0,
+                             'chirpPerF0': chirpPerF0, 'minF0search': minF0search,
+                             'maxF0search': maxF0search, }
+        self.nbComps = nbComps
+        self.nbNMFResComps = nbNMFResComps
+        self.nbFilterComps = nbFilterComps
+        if len(nbFilterWeigs) < self.nbComps - 1:
+            self.nbFilterWeigs = [nbFilterWeigs[0], ] * self.nbComps
+        else:
+            self.nbFilterWeigs = nbFilterWeigs
+        self.spatial_rank = np.atleast_1d(spatial_rank)
+        if self.spatial_rank.size < self.nbComps:
+            self.spatial_rank = [self.spatial_rank[0], ] * self.nbComps
+        # the source dictionary, shared by every component (:2616-2637)
+        self.F0Table, WF0, trfoBis = slf.generate_WF0_TR_chirped(
+            transform=self.tft, minF0=minF0, maxF0=maxF0, stepNotes=stepnoteF0, Ot=0.5,
+            perF0=chirpPerF0, depthChirpInSemiTone=0.5, loadWF0=True, verbose=self.verbose,
+            device=self.device)
+        WF0 = np.array(WF0, dtype=np.float64)
+        for nwf0comp in range(WF0.shape[1]):   # low-energy bins to eps (:2627-2629)
+            indLowEnergy = np.where(WF0[:, nwf0comp] < WF0[:, nwf0comp].max() * 1e-4)
+            WF0[indLowEnergy, nwf0comp] = eps
+        self.sourceFreqComps = np.ascontiguousarray(
+            np.hstack([WF0[:self.nbFreqsSigRepr], np.vstack(np.ones(self.nbFreqsSigRepr))]))
+        del WF0
+        self.nbSourceComps = self.sourceFreqComps.shape[1]
+        self.sourceFreqWeights = np.eye(self.nbSourceComps)
+        self.filterFreqComps = slf.generateHannBasis(
+            numberFrequencyBins=self.nbFreqsSigRepr, sizeOfFourier=self.sig_repr_params['fsize'],
+            Fs=self.audioObject.samplerate, frequencyScale='linear',
+            numberOfBasis=self.nbFilterComps)
+        self.sparsity = sparsity
+        self._initialize_structures()
+
+    def _initialize_structures(self, seed=None):
+        """Initial parameters, the reference's draw order on the global
+        np.random stream (audioModel.py:2650-2772).  The source dictionary and
+        its weights are ONE array in every source / filter component, as in
+        the reference, whose renormalisation rescales them in place component
+        after component: the device keeps one buffer for them too."""
+        np.random.seed(seed)
+        self.rank = self.spatial_rank
+        nc = self.audioObject.channels
+        sparsity = self.sparsity
+        self.spat_comps = {}
+        self.spec_comps = {}
+        F, T = self.nbFreqsSigRepr, self.nbFramesSigRepr
+
+        def factor(FB, FW, TW, fb, fw):
+            return {'FB': FB, 'FW': FW, 'TW': TW, 'TB': [], 'FB_frdm_prior': fb,
+                    'FW_frdm_prior': fw, 'TW_frdm_prior': 'free', 'TB_frdm_prior': [],
+                    'TW_constr': 'NMF'}
+        for j in range(self.nbComps - 1):
+            self.spat_comps[j] = {'time_dep': 'indep', 'mix_type': 'inst', 'frdm_prior': 'free'}
+            self.spat_comps[j]['params'] = np.random.randn(nc, self.rank[j])
+            if nc == 2:
+                self.spat_comps[j]['params'] = (
+                    np.array([np.sin((j + 1) * np.pi / (2. * (self.nbComps))) +
+                              np.random.randn(self.rank[j]) * np.sqrt(0.01),
+                              np.cos((j + 1) * np.pi / (2. * (self.nbComps))) +
+                              np.random.randn(self.rank[j]) * np.sqrt(0.01)]))
+            self.spec_comps[j] = {'spat_comp_ind': j, 'factor': {}}
+            TW0 = 0.75 * np.abs(np.random.randn(self.nbSourceComps, T)) + 0.25
+            self.spec_comps[j]['factor'][0] = factor(self.sourceFreqComps, self.sourceFreqWeights,
+                                                     TW0, 'fixed', 'fixed')
+            FW1 = 0.75 * np.abs(np.random.randn(self.nbFilterComps, self.nbFilterWeigs[j])) + 0.25
+            TW1 = 0.75 * np.abs(np.random.randn(self.nbFilterWeigs[j], T)) + 0.25
+            self.spec_comps[j]['factor'][1] = factor(self.filterFreqComps, FW1, TW1, 'fixed',
+                                                     'free')
+        self.resSpatialRank = self.rank[-1]
+        j = self.nbComps - 1
+        self.spat_comps[j] = {'time_dep': 'indep', 'mix_type': 'inst', 'frdm_prior': 'free'}
+        self.spat_comps[j]['params'] = np.random.randn(nc, self.resSpatialRank)
+        self.spec_comps[j] = {'spat_comp_ind': j, 'factor': {}}
+        FB = 0.75 * np.abs(np.random.randn(F, self.nbNMFResComps)) + 0.25
+        TW = 0.75 * np.abs(np.random.randn(self.nbNMFResComps, T)) + 0.25
+        self.spec_comps[j]['factor'][0] = factor(FB, np.eye(self.nbNMFResComps), TW, 'free',
+                                                 'fixed')
+        if sparsity is None or len(sparsity) not in (1, self.nbComps):
+            for j in range(self.nbComps):
+                self.spec_comps[j]['sparsity'] = False
+        elif len(sparsity) == self.nbComps:
+            for j in range(self.nbComps):
+                self.spec_comps[j]['sparsity'] = sparsity[j]
+        else:
+            for j in range(self.nbComps):
+                self.spec_comps[j]['sparsity'] = sparsity[0]
+        self._renormalize_host()
+
+    def _renormalize_host(self):
+        """renormalize_parameters (audioModel.py:1980-2040) of the initial
+        state, on the host: a few F x Kb, Kb x Kw and Kw x T matrices, once.
+        It keeps the constructor usable for any dictionary size (the device
+        path takes Kb, Kw <= 128 and says so when the estimation starts) and
+        applies the reference's in-place rescaling of the shared source
+        dictionary as written."""
+        energy = {}
+        for j, sc in self.spat_comps.items():
+            energy[j] = np.mean(np.abs(sc['params']) ** 2)
+            sc['params'] /= np.sqrt(energy[j])
+        for k, comp in self.spec_comps.items():
+            ge = energy[comp['spat_comp_ind']]
+            nfac = len(comp['factor'])
+            for i, fac in comp['factor'].items():
+                ge = self._renorm_factor_host(k, i, fac, ge, i < nfac - 1)
+
+    def setSpecCompFB(self, compNb, FB, FB_frdm_prior='fixed', ):
+        """audioModel.py:2858-2876"""
+        speccomp = self.spec_comps[compNb]['factor'][0]
+        if self.nbFreqsSigRepr != FB.shape[0]:
+            raise AttributeError("Size of provided FB is not consistent" + " with inner attributes")
+        speccomp['FB'] = np.copy(FB)
+        ncomp = FB.shape[1]
+        speccomp['FW'] = np.eye(ncomp)
+        speccomp['TW'] = 0.75 * np.abs(np.random.randn(ncomp, self.nbFramesSigRepr)) + 0.25
+        speccomp['FB_frdm_prior'] = FB_frdm_prior
+
+    def makeItConvolutive(self):
+        """audioModel.py:2910-2931"""
+        nc = self.audioObject.channels
+        for nspat, (spat_ind, spat_comp) in enumerate(self.spat_comps.items()):
+            if spat_comp['mix_type'] != 'inst':
+                warnings.warn("Spatial component %d " % spat_ind +
+                              "already not instantaneous, skipping...")
+            else:
+                spat_comp['mix_type'] = 'conv'
+                inst = spat_comp['params']
+                p = np.zeros([self.rank[nspat], nc, self.nbFreqsSigRepr], dtype=complex)
+                p[:] = np.atleast_2d(inst.T)[:, :, None]
+                spat_comp['params'] = p
+
+    def estim_param_a_post_model(self, ):
+        """audioModel.py:2933-2979 for sparsity=None (reweigh_sparsity_constraint
+        then does nothing): the base class's iterations on the GPU."""
+        if any(sc.get('sparsity') for sc in self.spec_comps.values()):
+            raise NotImplementedError(
+                "multiChanSourceF0Filter with a sparsity constraint: the schedule "
+                "(reweigh_sparsity_constraint, audioModel.py:2981-3014) needs a host step "
+                "between the device iterations and a median filter this package does not have")
+        return super(multiChanSourceF0Filter, self).estim_param_a_post_model()
+
+    def reweigh_sparsity_constraint(self, sigma):
+        """audioModel.py:2981-3014: nothing to do for components without a
+        sparsity constraint (the only ones this class estimates); with one,
+        NotImplementedError (the reference's median filter is not in this
+        package)."""
+        if any(sc.get('sparsity') for sc in self.spec_comps.values()):
+            raise NotImplementedError("reweigh_sparsity_constraint: the sparsity schedule is "
+                                      "outside this package (DESIGN.md 7)")

@@ -18,8 +18,13 @@
 #pragma once
 #include "fasst_common.h"
 
+struct fasst_sf_model;   // two-factor spectral components (fasst_sf.h)
+
 struct fasst_ctx {
   int device = 0;
+  // a model with two-factor (source / filter) spectral components keeps its
+  // whole state here (fasst_sf.hip), beside the single-factor state below
+  fasst_sf_model *sf = nullptr;
   hipStream_t stream = nullptr;
   // side stream: the small per-iteration prep kernels ((FW.TW)^T, TW row sums)
   // run there, forked at the iteration start and joined before their first
@@ -115,7 +120,8 @@ struct fasst_ctx {
   // per-kernel HIP-event timing (fasst_set_profiling / fasst_kernel_times)
   // (events on the stream each kernel runs on, the side-stream fork kept, a
   // ring of kProfRing iterations between host syncs: the timed schedule)
-  static constexpr int kNK = 17, kProfRing = 32;
+  // (slots kSfSlot0 ..: the kernels of fasst_sf.hip, launch counts only)
+  static constexpr int kNK = 26, kSfSlot0 = 17, kProfRing = 32;
   int prof = 0, pslot = 0;
   hipEvent_t ev0[kNK][kProfRing] = {}, ev1[kNK][kProfRing] = {};
   int used[kNK][kProfRing] = {{0}};
@@ -127,4 +133,5 @@ namespace fasst {
 int configure_model(fasst_ctx *c, int J, const int *rank, const int *K, const int *convj);
 int build_inst_A(fasst_ctx *c);
 int launch_w_old(fasst_ctx *c);  // Wkf = FB.FW
+void sf_release(fasst_ctx *c);   // drop the two-factor model (fasst_sf.hip)
 }  // namespace fasst

@@ -3527,7 +3527,9 @@ enum KernelId {
 static const char *kKernelNames[fasst_ctx::kNK] = {
     "k_w_from_fb", "k_fwh_t", "k_inst_A", "k_estep", "k_loglik", "k_mix",
     "k_mix_inst", "k_fb_contract", "k_fb_update", "k_tw_contract", "k_renorm", "k_tw_update",
-    "k_fw_update", "k_tw_rowsum", "k_renorm_tail", "k_tw_statediv", "k_tw_decode"};
+    "k_fw_update", "k_tw_rowsum", "k_renorm_tail", "k_tw_statediv", "k_tw_decode",
+    "k_sf_gemm", "k_sf_prod", "k_sf_ratio", "k_sf_update", "k_sf_renorm", "k_sf_wiener",
+    "k_sf_other", "k_sf_hatw", "k_sf_energy"};
 
 // per-kernel timing: an event pair around the launch on the stream it runs on
 // (s = nullptr: the main stream), slot = the iteration's place in the ring
@@ -3622,6 +3624,7 @@ int configure_model(fasst_ctx *c, int J, const int *rank, const int *K, const in
     set_error("J=%d outside the HIP path (1..%d sources)", J, kMaxJ);
     return FASST_ERR_UNSUPPORTED;
   }
+  sf_release(c);   // a single-factor model replaces a two-factor one
   int R = 0, kmax = 0;
   for (int j = 0; j < J; ++j) {
     if (rank[j] < 1 || K[j] < 1) {
@@ -4957,6 +4960,7 @@ int fasst_destroy(fasst_ctx *c) {
     DeviceGuard g(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->aux) (void)hipStreamSynchronize(c->aux);
+    sf_release(c);
     if (c->h_flags) (void)hipHostFree(c->h_flags);
     if (c->h_ll) (void)hipHostFree(c->h_ll);
     c->cx.release();

@@ -1,0 +1,796 @@
+// Two-factor (source / filter) spectral components on the device: the "planar"
+// GEM path.  V_j = prod_i P_{j,i}, P_{j,i} = (FB_i.FW_i).TW_i, every power an
+// F x T plane (comp_spat_comp_power, audioModel.py:430-498; the multi-factor
+// branches of update_spectral_components :1469-1727 and renormalize_parameters
+// :1980-2040).  Kept beside the single-factor kernels of fasst_em.hip: a model
+// without a two-factor component never reaches this file.
+//
+// Per GEM iteration (sf_iteration):
+//   powers    W = FB.FW, P = W.TW on the FP64 MFMA GEMM (k_gemm, 16x16x4),
+//             V_j by k_sf_prod
+//   E-step    k_suff_stat on the resident planes (rank r reads plane vmap[r])
+//   mixing    k_mix_solve_inst / k_mix_solve_conv, hat_W_j = mean_r hat_Ws
+//   spectral  per source, per factor: `other` once (k_sf_other), then per free
+//             matrix k_sf_ratio (other / V and hat_W other / V^2 from the resident
+//             planes, nothing else written), the contraction on the MFMA GEMM
+//             (split-K slabs summed in fixed order) and k_sf_update
+//   renorm    k_sf_energy per source, k_sf_renorm per factor (the energy handed
+//             from factor to factor as the reference does)
+// Every reduction has a fixed order: two runs are bit-equal.
+#include "fasst_sf.h"
+#include "fasst_fft.h"
+#include "fasst_gemm.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace fasst {
+
+enum { KSF_GEMM = fasst_ctx::kSfSlot0, KSF_PROD, KSF_RATIO, KSF_UPDATE, KSF_RENORM, KSF_WIENER, KSF_OTHER,
+       KSF_HATW, KSF_ENERGY };
+static inline void sf_count(fasst_ctx *c, int id) {
+  if (c->prof) c->prof_cnt[id] += 1;
+}
+
+static int sf_grid(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 16384); }
+
+// V = P0 (one factor) or P0 P1
+__global__ void k_sf_prod(const double *__restrict__ P0, const double *__restrict__ P1,
+                          double *__restrict__ V, size_t n) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    V[i] = P1 ? P0[i] * P1[i] : P0[i];
+}
+
+// other = max(prod of the other factors, eps); a one-factor component: its own
+// power, Po = that plane either way
+__global__ void k_sf_other(const double *__restrict__ Po, double *__restrict__ other, size_t n) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    other[i] = fmax(Po[i], kEps);
+}
+
+// Vj = max(Ps Po, eps) (Po == nullptr: one factor): rd = other (1 / Vj),
+// rn = hat_W / Vj^2 other  (audioModel.py:1544-1573, lambdaCorr == 0)
+__global__ void k_sf_ratio(const double *__restrict__ Ps, const double *__restrict__ Po,
+                           const double *__restrict__ other, const double *__restrict__ hatW,
+                           double *__restrict__ rn, double *__restrict__ rd, size_t n) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const double v = fmax(Po ? Ps[i] * Po[i] : Ps[i], kEps), o = other[i];
+    rd[i] = o * (1.0 / v);
+    rn[i] = hatW[i] / (v * v) * o;
+  }
+}
+
+// P[r][c] *= (num / max(den, eps))^omega; tr: num / den are stored [cols][rows]
+__global__ void k_sf_update(double *__restrict__ P, int rows, int cols, const double *__restrict__ num,
+                            const double *__restrict__ den, int tr, double omega) {
+  const size_t n = (size_t)rows * cols;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t q = tr ? (i % cols) * (size_t)rows + i / cols : i;
+    const double g = num[q] / fmax(den[q], kEps);
+    P[i] *= omega == 1.0 ? g : pow(g, omega);
+  }
+}
+
+// hat_W_j = mean over the ranks of source j of hat_Ws (audioModel.py:414-416)
+__global__ void k_sf_hatw(const double *__restrict__ ws, double *__restrict__ hatW, int r0, int nr,
+                          size_t n) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    double s = 0.0;
+    for (int r = 0; r < nr; ++r) s += ws[(size_t)(r0 + r) * n + i];
+    hatW[i] = s / (double)nr;
+  }
+}
+
+__device__ __forceinline__ double sf_block_sum(double x, double *s_red) {
+  s_red[threadIdx.x] = x;
+  __syncthreads();
+  for (int w = blockDim.x / 2; w > 0; w >>= 1) {
+    if (threadIdx.x < w) s_red[threadIdx.x] += s_red[threadIdx.x + w];
+    __syncthreads();
+  }
+  const double r = s_red[0];
+  __syncthreads();
+  return r;
+}
+
+// renormalize_parameters, the spatial half (:1993-1999), one block per source:
+// energy = mean |params|^2 ('inst': the C x r matrix, bin 0 of its constant
+// rows; 'conv': r x C x F), params /= sqrt(energy)
+__global__ __launch_bounds__(256) void k_sf_energy(double2 *__restrict__ mix, int F, const int *__restrict__ roff,
+                                                   const int *__restrict__ conv, double *__restrict__ energy) {
+  __shared__ double s_red[256];
+  const int j = blockIdx.x, r0 = roff[j], r1 = roff[j + 1], cv = conv[j];
+  const int nf = cv ? F : 1;
+  const size_t n = (size_t)(r1 - r0) * 2 * nf;
+  double s = 0.0;
+  for (size_t i = threadIdx.x; i < n; i += 256) {
+    const double2 z = mix[(size_t)r0 * 2 * F + (i / nf) * F + i % nf];
+    s += z.x * z.x + z.y * z.y;
+  }
+  const double e = sf_block_sum(s, s_red) / (double)n;
+  const double q = sqrt(e);
+  for (size_t i = threadIdx.x; i < (size_t)(r1 - r0) * 2 * F; i += 256) {
+    double2 z = mix[(size_t)r0 * 2 * F + i];
+    z.x /= q;
+    z.y /= q;
+    mix[(size_t)r0 * 2 * F + i] = z;
+  }
+  if (threadIdx.x == 0) energy[j] = e;
+}
+
+// renormalize_parameters of one factor (:2003-2036), one block: FB *= energy;
+// column max of FB -> FW; column mean of FW -> TW; sum(TW) < eps: restart flag
+// (the host redraws and finishes); else TW /= mean(TW) unless the last factor.
+// The reference reuses one variable down the factors: *energy is the spatial
+// energy for factor 0 and the previous factor's mean(TW) (*ge_out of its
+// launch) after that.  A previous factor that needs a restart (*prev_flag)
+// leaves this one to the host, which alone knows the redrawn mean.
+// scal: max(Kb, Kw) doubles of scratch
+__global__ __launch_bounds__(256) void k_sf_renorm(double *__restrict__ FB, double *__restrict__ FW,
+                                                   double *__restrict__ TW, int F, int Kb, int Kw, int T,
+                                                   const double *__restrict__ energy, int last,
+                                                   double *__restrict__ scal, int *__restrict__ flag,
+                                                   const int *__restrict__ prev_flag,
+                                                   double *__restrict__ ge_out) {
+  __shared__ double s_red[256];
+  const int tid = threadIdx.x;
+  if (prev_flag && *prev_flag) return;
+  const double e = *energy;
+  for (int k = tid; k < Kb; k += 256) {
+    double m = -INFINITY;
+    for (int f = 0; f < F; ++f) {
+      const double v = FB[(size_t)f * Kb + k] * e;
+      FB[(size_t)f * Kb + k] = v;
+      m = fmax(m, v);
+    }
+    if (m == 0.0) m = 1.0;
+    for (int f = 0; f < F; ++f) FB[(size_t)f * Kb + k] /= m;
+    scal[k] = m;
+  }
+  __syncthreads();
+  for (int i = tid; i < Kb * Kw; i += 256) FW[i] *= scal[i / Kw];
+  __syncthreads();
+  for (int k = tid; k < Kw; k += 256) {   // (scal's column maxima were consumed above)
+    double s = 0.0;
+    for (int b = 0; b < Kb; ++b) s += FW[(size_t)b * Kw + k];
+    double w2 = s / (double)Kb;
+    if (w2 == 0.0) w2 = 1.0;
+    for (int b = 0; b < Kb; ++b) FW[(size_t)b * Kw + k] /= w2;
+    scal[k] = w2;
+  }
+  __syncthreads();
+  const size_t n = (size_t)Kw * T;
+  double s = 0.0;
+  for (size_t i = tid; i < n; i += 256) {
+    const double v = TW[i] * scal[i / T];
+    TW[i] = v;
+    s += v;
+  }
+  const double tot = sf_block_sum(s, s_red);
+  const int dead = tot < kEps ? 1 : 0;
+  const double ge = tot / (double)n;
+  if (tid == 0) {
+    *flag = dead;
+    *ge_out = ge;
+  }
+  if (dead || last) return;
+  for (size_t i = tid; i < n; i += 256) TW[i] /= ge;
+}
+
+// Per-bin Wiener images from the V_j planes (compute_sigma_comp_2d :1327-1372,
+// compute_inv_sigma_mix_2d :1374-1394, compute_Wiener_gain_2d :1396-1467):
+// source n sums the spatial components j with src_of[j] == n.  X [2][Tp][Fp]
+// frame-major; S[(n 2 + c) splane + f sf + t st]
+struct SfWArgs {
+  const double *V;       // [J][F][T]
+  const double2 *mix;    // [R][2][F]
+  const double *psd;
+  const double2 *X;
+  double2 *S;
+  int F, T, Fp, Tp, J, nsrc;
+  int roff[kMaxJ + 1], src_of[kMaxJ];
+  size_t splane, sf, st;
+};
+
+__global__ __launch_bounds__(256) void k_sf_wiener(const SfWArgs a) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
+  if (t >= a.T) return;
+  const size_t FT = (size_t)a.F * a.T, i = (size_t)f * a.T + t;
+  double c0[kMaxJ], c1[kMaxJ], cr[kMaxJ], ci[kMaxJ];
+  for (int j = 0; j < a.J; ++j) {
+    double r0 = 0.0, r1 = 0.0, orr = 0.0, oi = 0.0;
+    for (int r = a.roff[j]; r < a.roff[j + 1]; ++r) {
+      const double2 a0 = a.mix[((size_t)r * 2 + 0) * a.F + f], a1 = a.mix[((size_t)r * 2 + 1) * a.F + f];
+      r0 += a0.x * a0.x + a0.y * a0.y;
+      r1 += a1.x * a1.x + a1.y * a1.y;
+      orr += a0.x * a1.x + a0.y * a1.y;
+      oi += a0.y * a1.x - a0.x * a1.y;
+    }
+    const double v = a.V[(size_t)j * FT + i];
+    c0[j] = r0 * v;
+    c1[j] = r1 * v;
+    cr[j] = orr * v;
+    ci[j] = oi * v;
+  }
+  double d0 = 0.0, d1 = 0.0, orr = 0.0, oi = 0.0;
+  for (int n = 0; n < a.nsrc; ++n)
+    for (int j = 0; j < a.J; ++j)
+      if (a.src_of[j] == n) {
+        d0 += c0[j];
+        d1 += c1[j];
+        orr += cr[j];
+        oi += ci[j];
+      }
+  const double p = a.psd[f];
+  d0 += p;
+  d1 += p;
+  double det = d0 * d1 - (orr * orr + oi * oi);
+  const double dg = det + kEps;
+  det = (dg > 0.0 ? 1.0 : (dg < 0.0 ? -1.0 : 0.0)) * fmax(fabs(det), kEps);
+  const double i0 = d1 / det, i1 = d0 / det, ior = -orr / det, ioi = -oi / det;
+  const double2 x0 = a.X[(size_t)t * a.Fp + f], x1 = a.X[((size_t)a.Tp + t) * a.Fp + f];
+  for (int n = 0; n < a.nsrc; ++n) {
+    double s0 = 0.0, s1 = 0.0, sr = 0.0, si = 0.0;
+    for (int j = 0; j < a.J; ++j)
+      if (a.src_of[j] == n) {
+        s0 += c0[j];
+        s1 += c1[j];
+        sr += cr[j];
+        si += ci[j];
+      }
+    // so conj(iso)
+    const double wr = sr * ior + si * ioi, wi = si * ior - sr * ioi;
+    const double g00r = wr + s0 * i0, g00i = wi, g11r = wr + s1 * i1, g11i = -wi;
+    const double g01r = s0 * ior + sr * i1, g01i = s0 * ioi + si * i1;
+    const double g10r = sr * i0 + s1 * ior, g10i = -si * i0 - s1 * ioi;
+    const double2 y0 = make_double2(g00r * x0.x - g00i * x0.y + g01r * x1.x - g01i * x1.y,
+                                    g00r * x0.y + g00i * x0.x + g01r * x1.y + g01i * x1.x);
+    const double2 y1 = make_double2(g10r * x0.x - g10i * x0.y + g11r * x1.x - g11i * x1.y,
+                                    g10r * x0.y + g10i * x0.x + g11r * x1.y + g11i * x1.x);
+    a.S[(size_t)(2 * n) * a.splane + f * a.sf + t * a.st] = y0;
+    a.S[(size_t)(2 * n + 1) * a.splane + f * a.sf + t * a.st] = y1;
+  }
+}
+
+// ------------------------------------------------------------------ host side
+void sf_release(fasst_ctx *c) {
+  if (!c || !c->sf) return;
+  DeviceGuard g(c->device);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  delete c->sf;
+  c->sf = nullptr;
+}
+
+static int need_sf(fasst_ctx *c, int j, int i = 0) {
+  if (!c || !c->sf) {
+    set_error("no two-factor model configured (fasst_sf_configure)");
+    return FASST_ERR_SHAPE;
+  }
+  if (j < 0 || j >= c->sf->J || i < 0 || i >= c->sf->nfac[j]) {
+    set_error("component %d factor %d out of range", j, i);
+    return FASST_ERR_SHAPE;
+  }
+  return FASST_OK;
+}
+
+// C = A.B on the MFMA GEMM (row-major, dense)
+static int sf_mm(fasst_ctx *c, const double *A, const double *B, double *C, int M, int N, int K) {
+  const double *Bs[1] = {B};
+  double *Cs[1] = {C};
+  sf_count(c, KSF_GEMM);
+  return gemm<false, false, 1>(c->stream, A, K, Bs, N, Cs, N, M, N, K, c->sf->work.p);
+}
+
+// W = FB.FW (unless only TW moved: w == false), P = W.TW of factor (j, i)
+static int sf_power(fasst_ctx *c, int j, int i, bool w = true) {
+  SfFactor &x = c->sf->fac[j][i];
+  int st;
+  if (w && (st = sf_mm(c, x.fb, x.fw, x.W.p, c->F, x.Kw, x.Kb))) return st;
+  return sf_mm(c, x.W.p, x.tw, x.P.p, c->F, c->T, x.Kw);
+}
+
+static int sf_source_power(fasst_ctx *c, int j) {
+  fasst_sf_model *m = c->sf;
+  const size_t FT = (size_t)c->F * c->T;
+  sf_count(c, KSF_PROD);
+  k_sf_prod<<<sf_grid(FT), 256, 0, c->stream>>>(m->fac[j][0].P.p, m->nfac[j] > 1 ? m->fac[j][1].P.p : nullptr,
+                                                m->V.p + (size_t)j * FT, FT);
+  FASST_LAUNCH_CHECK();
+  return FASST_OK;
+}
+
+static int sf_all_powers(fasst_ctx *c) {
+  int st;
+  for (int j = 0; j < c->sf->J; ++j) {
+    for (int i = 0; i < c->sf->nfac[j]; ++i)
+      if ((st = sf_power(c, j, i))) return st;
+    if ((st = sf_source_power(c, j))) return st;
+  }
+  return FASST_OK;
+}
+
+static int sf_ratio(fasst_ctx *c, int j, int i) {
+  fasst_sf_model *m = c->sf;
+  const size_t FT = (size_t)c->F * c->T;
+  sf_count(c, KSF_RATIO);
+  k_sf_ratio<<<sf_grid(FT), 256, 0, c->stream>>>(m->fac[j][i].P.p, m->nfac[j] > 1 ? m->fac[j][1 - i].P.p : nullptr,
+                                                 m->other.p, m->hatW.p + (size_t)j * FT, m->rn.p, m->rd.p, FT);
+  FASST_LAUNCH_CHECK();
+  return FASST_OK;
+}
+
+static int sf_apply(fasst_ctx *c, double *P, int rows, int cols, const double *num, const double *den,
+                    int tr, double omega) {
+  sf_count(c, KSF_UPDATE);
+  k_sf_update<<<sf_grid((size_t)rows * cols), 256, 0, c->stream>>>(P, rows, cols, num, den, tr, omega);
+  FASST_LAUNCH_CHECK();
+  return FASST_OK;
+}
+
+// update_spectral_components of source j (audioModel.py:1509-1727, lambdaCorr
+// == 0, TB empty): factors in order, FB then FW then TW
+static int sf_spectral_update(fasst_ctx *c, int j, double omega) {
+  fasst_sf_model *m = c->sf;
+  const int F = c->F, T = c->T;
+  const size_t FT = (size_t)F * T;
+  int st;
+  // a matrix shared with another source may have moved since the iteration's
+  // powers were formed; without one they stand
+  if (m->shared[j])
+    for (int i = 0; i < m->nfac[j]; ++i)
+      if ((st = sf_power(c, j, i))) return st;
+  for (int i = 0; i < m->nfac[j]; ++i) {
+    SfFactor &x = m->fac[j][i];
+    const int Kb = x.Kb, Kw = x.Kw;
+    // the power is refreshed after a step only when a later step of this
+    // source reads it (the next iteration and the separation form their own)
+    const bool more = i < m->nfac[j] - 1;
+    // `other`, once per factor, from the powers as they stand
+    const double *Po = m->nfac[j] > 1 ? m->fac[j][1 - i].P.p : x.P.p;
+    sf_count(c, KSF_OTHER);
+    k_sf_other<<<sf_grid(FT), 256, 0, c->stream>>>(Po, m->other.p, FT);
+    FASST_LAUNCH_CHECK();
+    const double *RB[2] = {m->rn.p, m->rd.p};
+    if (x.fb_free) {
+      if ((st = sf_ratio(c, j, i))) return st;
+      // (FW.TW) [Kb][T]; num^T [Kb][F] = (FW.TW) rn^T, den^T likewise
+      if ((st = sf_mm(c, x.fw, x.tw, m->fwh.p, Kb, T, Kw))) return st;
+      double *Cs[2] = {m->cn.p, m->cd.p};
+      sf_count(c, KSF_GEMM);
+      if ((st = gemm<false, true, 2>(c->stream, m->fwh.p, T, RB, T, Cs, F, Kb, F, T, m->work.p))) return st;
+      if ((st = sf_apply(c, x.fb, F, Kb, m->cn.p, m->cd.p, 1, omega))) return st;
+      if ((more || x.fw_free || x.tw_free) && (st = sf_power(c, j, i))) return st;
+    }
+    if (x.fw_free) {
+      if ((st = sf_ratio(c, j, i))) return st;
+      // X^T [Kw][F] = TW r^T, then num^T [Kw][Kb] = X^T FB
+      double *Xs[2] = {m->xn.p, m->xd.p};
+      sf_count(c, KSF_GEMM);
+      if ((st = gemm<false, true, 2>(c->stream, x.tw, T, RB, T, Xs, F, Kw, F, T, m->work.p))) return st;
+      if ((st = sf_mm(c, m->xn.p, x.fb, m->cn.p, Kw, Kb, F))) return st;
+      if ((st = sf_mm(c, m->xd.p, x.fb, m->cd.p, Kw, Kb, F))) return st;
+      if ((st = sf_apply(c, x.fw, Kb, Kw, m->cn.p, m->cd.p, 1, omega))) return st;
+      if ((more || x.tw_free) && (st = sf_power(c, j, i))) return st;
+    }
+    if (x.tw_free) {
+      if ((st = sf_ratio(c, j, i))) return st;
+      // num [Kw][T] = W^T rn, den = W^T rd
+      double *Cs[2] = {m->cn.p, m->cd.p};
+      sf_count(c, KSF_GEMM);
+      if ((st = gemm<true, false, 2>(c->stream, x.W.p, Kw, RB, T, Cs, T, Kw, T, F, m->work.p))) return st;
+      if ((st = sf_apply(c, x.tw, Kw, T, m->cn.p, m->cd.p, 0, omega))) return st;
+      if (more && (st = sf_power(c, j, i, false))) return st;
+    }
+  }
+  return FASST_OK;
+}
+
+static int sf_renormalize(fasst_ctx *c) {
+  fasst_sf_model *m = c->sf;
+  sf_count(c, KSF_ENERGY);
+  k_sf_energy<<<m->J, 256, 0, c->stream>>>(m->mix.p, c->F, m->droff.p, m->dconv.p, m->energy.p);
+  FASST_LAUNCH_CHECK();
+  for (int j = 0; j < m->J; ++j)
+    for (int i = 0; i < m->nfac[j]; ++i) {
+      SfFactor &x = m->fac[j][i];
+      sf_count(c, KSF_RENORM);
+      int *flag = m->flags.p + 1 + 2 * j + i;
+      k_sf_renorm<<<1, 256, 0, c->stream>>>(x.fb, x.fw, x.tw, c->F, x.Kb, x.Kw, c->T,
+                                            m->energy.p + (i ? kMaxJ + j : j), i == m->nfac[j] - 1,
+                                            m->scal.p, flag, i ? flag - 1 : nullptr, m->energy.p + kMaxJ + j);
+      FASST_LAUNCH_CHECK();
+    }
+  return FASST_OK;
+}
+
+static int sf_iteration(fasst_ctx *c, const double *dpsd, double *dll, double omega, int nconv) {
+  fasst_sf_model *m = c->sf;
+  const size_t FT = (size_t)c->F * c->T;
+  int st;
+  if ((st = sf_all_powers(c))) return st;
+  int vmap[kStepMaxR];
+  for (int j = 0; j < m->J; ++j)
+    for (int r = m->roff[j]; r < m->roff[j + 1]; ++r) vmap[r] = j;
+  if ((st = suff_stat_device(c, c->stream, m->R, m->V.p, vmap, m->mix.p, dpsd, m->rxx.p, m->rxs.p, m->rss.p,
+                             m->ws.p, m->llb.p, dll)))
+    return st;
+  if ((st = mix_solve_device(c->stream, c->F, m->R, m->rss.p, m->rxs.p, m->mix.p, m->kind.p, nconv,
+                             m->flags.p)))
+    return st;
+  for (int j = 0; j < m->J; ++j) {
+    sf_count(c, KSF_HATW);
+    k_sf_hatw<<<sf_grid(FT), 256, 0, c->stream>>>(m->ws.p, m->hatW.p + (size_t)j * FT, m->roff[j], m->rank[j],
+                                                  FT);
+    FASST_LAUNCH_CHECK();
+  }
+  for (int j = 0; j < m->J; ++j)
+    if ((st = sf_spectral_update(c, j, omega))) return st;
+  return sf_renormalize(c);
+}
+
+static int sf_flags_mask(fasst_ctx *c, int *mask) {
+  fasst_sf_model *m = c->sf;
+  int h[1 + 2 * kMaxJ];
+  FASST_HIP(hipMemcpyAsync(h, m->flags.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  FASST_HIP(hipStreamSynchronize(c->stream));
+  if (h[0]) {
+    set_error("Singular Matrix");
+    return FASST_ERR_SINGULAR;
+  }
+  *mask = 0;
+  for (int j = 0; j < m->J; ++j)
+    for (int i = 0; i < m->nfac[j]; ++i)
+      if (h[1 + 2 * j + i]) *mask = (int)((unsigned)*mask | (1u << (2 * j + i)));
+  return FASST_OK;
+}
+
+static int sf_launch_wiener(fasst_ctx *c, const double *dpsd, int nsrc, const int *src_of, double2 *dS,
+                            size_t splane, size_t sf, size_t st_) {
+  fasst_sf_model *m = c->sf;
+  SfWArgs a;
+  a.V = m->V.p;
+  a.mix = m->mix.p;
+  a.psd = dpsd;
+  a.X = c->X.p;
+  a.S = dS;
+  a.F = c->F;
+  a.T = c->T;
+  a.Fp = c->Fp;
+  a.Tp = c->Tp;
+  a.J = m->J;
+  a.nsrc = nsrc;
+  for (int j = 0; j <= kMaxJ; ++j) a.roff[j] = j <= m->J ? m->roff[j] : m->roff[m->J];
+  for (int j = 0; j < kMaxJ; ++j) a.src_of[j] = j < m->J ? src_of[j] : -1;
+  a.splane = splane;
+  a.sf = sf;
+  a.st = st_;
+  sf_count(c, KSF_WIENER);
+  k_sf_wiener<<<dim3((c->T + 255) / 256, c->F), 256, 0, c->stream>>>(a);
+  FASST_LAUNCH_CHECK();
+  return FASST_OK;
+}
+
+static int sf_check_sources(fasst_ctx *c, int nsrc, const int *src_of) {
+  if (nsrc < 1 || nsrc > kMaxJ || !src_of) {
+    set_error("separation sources: %d outside 1..%d", nsrc, kMaxJ);
+    return FASST_ERR_SHAPE;
+  }
+  for (int j = 0; j < c->sf->J; ++j)
+    if (src_of[j] < -1 || src_of[j] >= nsrc) {
+      set_error("separation sources: component %d in source %d of %d", j, src_of[j], nsrc);
+      return FASST_ERR_SHAPE;
+    }
+  return FASST_OK;
+}
+
+}  // namespace fasst
+
+using namespace fasst;
+
+extern "C" {
+
+int fasst_sf_configure(fasst_ctx *c, int J, const int *rank, const int *mix_conv, const int *nfac,
+                       const int *Kb, const int *Kw, const int *priors, const int *alias) {
+  if (!c || !rank || !mix_conv || !nfac || !Kb || !Kw || !priors || !alias) return FASST_ERR_SHAPE;
+  if (J < 1 || J > kMaxJ) {
+    set_error("J=%d outside the HIP path (1..%d sources)", J, kMaxJ);
+    return FASST_ERR_UNSUPPORTED;
+  }
+  int R = 0;
+  for (int j = 0; j < J; ++j) {
+    if (rank[j] < 1 || nfac[j] < 1 || nfac[j] > kSfMaxFac) {
+      set_error("component %d: rank %d, %d factors (1..%d)", j, rank[j], nfac[j], kSfMaxFac);
+      return FASST_ERR_UNSUPPORTED;
+    }
+    for (int i = 0; i < nfac[j]; ++i)
+      if (Kb[2 * j + i] < 1 || Kw[2 * j + i] < 1) {
+        set_error("component %d factor %d: Kb %d, Kw %d", j, i, Kb[2 * j + i], Kw[2 * j + i]);
+        return FASST_ERR_SHAPE;
+      }
+    R += rank[j];
+  }
+  if (R > kStepMaxR) {
+    set_error("total spatial rank %d above the explicit-V E-step's %d", R, kStepMaxR);
+    return FASST_ERR_UNSUPPORTED;
+  }
+  DeviceGuard g(c->device);
+  sf_release(c);
+  fasst_sf_model *m = new fasst_sf_model();
+  c->sf = m;
+  m->J = J;
+  m->R = R;
+  const int F = c->F, T = c->T;
+  const size_t FT = (size_t)F * T;
+  size_t ncd = 1, nx = 1, nfwh = 1, nwork = 1, nscal = 1;
+  int kind[kStepMaxR];
+  for (int j = 0; j < J; ++j) {
+    m->rank[j] = rank[j];
+    m->roff[j + 1] = m->roff[j] + rank[j];
+    m->conv[j] = mix_conv[j] ? 1 : 0;
+    m->nfac[j] = nfac[j];
+    for (int r = m->roff[j]; r < m->roff[j + 1]; ++r) kind[r] = 0;
+  }
+  int st = FASST_OK;
+  for (int j = 0; j < J && !st; ++j)
+    for (int i = 0; i < nfac[j] && !st; ++i) {
+      SfFactor &x = m->fac[j][i];
+      const int kb = Kb[2 * j + i], kw = Kw[2 * j + i];
+      x.Kb = kb;
+      x.Kw = kw;
+      x.fb_free = priors[(2 * j + i) * 3 + 0];
+      x.fw_free = priors[(2 * j + i) * 3 + 1];
+      x.tw_free = priors[(2 * j + i) * 3 + 2];
+      // a matrix shared with an earlier factor (one NumPy array in several
+      // factor dicts, updated in place by the reference) shares its buffer
+      const int *al = alias + (2 * j + i) * 3;
+      const SfFactor *o[3];
+      for (int q = 0; q < 3; ++q) {
+        o[q] = nullptr;
+        if (al[q] < 0) continue;
+        const int oj = al[q] / 2, oi = al[q] % 2;
+        if (al[q] >= 2 * j + i || oj >= J || oi >= nfac[oj]) {
+          set_error("component %d factor %d: shared matrix index %d", j, i, al[q]);
+          st = FASST_ERR_SHAPE;
+          break;
+        }
+        o[q] = &m->fac[oj][oi];
+        m->shared[j] = m->shared[oj] = 1;
+      }
+      if (st) break;
+      if ((o[0] && (o[0]->Kb != kb)) || (o[1] && (o[1]->Kb != kb || o[1]->Kw != kw)) ||
+          (o[2] && o[2]->Kw != kw)) {
+        set_error("component %d factor %d: shared matrices of different shapes", j, i);
+        st = FASST_ERR_SHAPE;
+        break;
+      }
+      if ((!o[0] && (st = x.FB.alloc((size_t)F * kb))) || (!o[1] && (st = x.FW.alloc((size_t)kb * kw))) ||
+          (!o[2] && (st = x.TW.alloc((size_t)kw * T))) || (st = x.W.alloc((size_t)F * kw)) ||
+          (st = x.P.alloc(FT)))
+        break;
+      x.fb = o[0] ? o[0]->fb : x.FB.p;
+      x.fw = o[1] ? o[1]->fw : x.FW.p;
+      x.tw = o[2] ? o[2]->tw : x.TW.p;
+      ncd = std::max({ncd, (size_t)kb * F, (size_t)kw * T, (size_t)kw * kb});
+      nx = std::max(nx, (size_t)kw * F);
+      nfwh = std::max(nfwh, (size_t)kb * T);
+      nscal = std::max({nscal, (size_t)kb, (size_t)kw});
+      nwork = std::max({nwork, gemm_workspace(F, kw, kb, 1), gemm_workspace(F, T, kw, 1),
+                        gemm_workspace(kb, T, kw, 1), gemm_workspace(kb, F, T, 2),
+                        gemm_workspace(kw, F, T, 2), gemm_workspace(kw, kb, F, 1),
+                        gemm_workspace(kw, T, F, 2)});
+    }
+  if (!st) {
+    (st = m->V.alloc((size_t)J * FT)) || (st = m->ws.alloc((size_t)R * FT)) ||
+        (st = m->hatW.alloc((size_t)J * FT)) || (st = m->other.alloc(FT)) || (st = m->rn.alloc(FT)) ||
+        (st = m->rd.alloc(FT)) || (st = m->mix.alloc((size_t)R * 2 * F)) ||
+        (st = m->rss.alloc((size_t)F * R * R)) || (st = m->rxs.alloc((size_t)F * 2 * R)) ||
+        (st = m->rxx.alloc((size_t)3 * F)) || (st = m->llb.alloc(F)) || (st = m->energy.alloc(2 * kMaxJ)) || (st = m->droff.alloc(kMaxJ + 1)) ||
+        (st = m->dconv.alloc(kMaxJ)) ||
+        (st = m->scal.alloc(nscal)) || (st = m->kind.alloc(kStepMaxR)) ||
+        (st = m->flags.alloc(1 + 2 * kMaxJ)) || (st = m->cn.alloc(ncd)) || (st = m->cd.alloc(ncd)) ||
+        (st = m->xn.alloc(nx)) || (st = m->xd.alloc(nx)) || (st = m->fwh.alloc(nfwh)) ||
+        (st = m->work.alloc(nwork));
+  }
+  if (st) {
+    sf_release(c);
+    return st;
+  }
+  FASST_HIP(hipMemcpy(m->kind.p, kind, R * sizeof(int), hipMemcpyHostToDevice));
+  FASST_HIP(hipMemcpy(m->droff.p, m->roff, (J + 1) * sizeof(int), hipMemcpyHostToDevice));
+  FASST_HIP(hipMemcpy(m->dconv.p, m->conv, J * sizeof(int), hipMemcpyHostToDevice));
+  return FASST_OK;
+}
+
+int fasst_sf_set_spatial(fasst_ctx *c, int j, const double *params, int free_) {
+  int st = need_sf(c, j);
+  if (st) return st;
+  if (!params) return FASST_ERR_SHAPE;
+  fasst_sf_model *m = c->sf;
+  DeviceGuard g(c->device);
+  const int F = c->F, r0 = m->roff[j], nr = m->rank[j];
+  std::vector<double2> h((size_t)nr * 2 * F);
+  const double2 *p = (const double2 *)params;
+  if (m->conv[j]) {
+    std::copy(p, p + h.size(), h.begin());
+  } else {   // the C x r matrix on every bin
+    for (int r = 0; r < nr; ++r)
+      for (int ch = 0; ch < 2; ++ch)
+        for (int f = 0; f < F; ++f) h[((size_t)r * 2 + ch) * F + f] = p[ch * nr + r];
+  }
+  m->spat_free[j] = free_ ? 1 : 0;
+  std::vector<int> kind(nr, free_ ? (m->conv[j] ? 2 : 1) : 0);
+  FASST_HIP(hipMemcpy(m->mix.p + (size_t)r0 * 2 * F, h.data(), h.size() * sizeof(double2),
+                      hipMemcpyHostToDevice));
+  FASST_HIP(hipMemcpy(m->kind.p + r0, kind.data(), nr * sizeof(int), hipMemcpyHostToDevice));
+  return FASST_OK;
+}
+
+int fasst_sf_get_spatial(fasst_ctx *c, int j, double *params) {
+  int st = need_sf(c, j);
+  if (st) return st;
+  if (!params) return FASST_ERR_SHAPE;
+  fasst_sf_model *m = c->sf;
+  DeviceGuard g(c->device);
+  const int F = c->F, r0 = m->roff[j], nr = m->rank[j];
+  std::vector<double2> h((size_t)nr * 2 * F);
+  FASST_HIP(hipStreamSynchronize(c->stream));
+  FASST_HIP(hipMemcpy(h.data(), m->mix.p + (size_t)r0 * 2 * F, h.size() * sizeof(double2),
+                      hipMemcpyDeviceToHost));
+  double2 *p = (double2 *)params;
+  if (m->conv[j]) {
+    std::copy(h.begin(), h.end(), p);
+  } else {
+    for (int r = 0; r < nr; ++r)
+      for (int ch = 0; ch < 2; ++ch) p[ch * nr + r] = h[((size_t)r * 2 + ch) * F];
+  }
+  return FASST_OK;
+}
+
+int fasst_set_factors(fasst_ctx *c, int j, int i, const double *FB, const double *FW, const double *TW) {
+  int st = need_sf(c, j, i);
+  if (st) return st;
+  if (!FB || !FW || !TW) return FASST_ERR_SHAPE;
+  SfFactor &x = c->sf->fac[j][i];
+  DeviceGuard g(c->device);
+  FASST_HIP(hipStreamSynchronize(c->stream));
+  FASST_HIP(hipMemcpy(x.fb, FB, (size_t)c->F * x.Kb * sizeof(double), hipMemcpyHostToDevice));
+  FASST_HIP(hipMemcpy(x.fw, FW, (size_t)x.Kb * x.Kw * sizeof(double), hipMemcpyHostToDevice));
+  FASST_HIP(hipMemcpy(x.tw, TW, (size_t)x.Kw * c->T * sizeof(double), hipMemcpyHostToDevice));
+  return FASST_OK;
+}
+
+int fasst_get_factors(fasst_ctx *c, int j, int i, double *FB, double *FW, double *TW) {
+  int st = need_sf(c, j, i);
+  if (st) return st;
+  SfFactor &x = c->sf->fac[j][i];
+  DeviceGuard g(c->device);
+  FASST_HIP(hipStreamSynchronize(c->stream));
+  if (FB) FASST_HIP(hipMemcpy(FB, x.fb, (size_t)c->F * x.Kb * sizeof(double), hipMemcpyDeviceToHost));
+  if (FW) FASST_HIP(hipMemcpy(FW, x.fw, (size_t)x.Kb * x.Kw * sizeof(double), hipMemcpyDeviceToHost));
+  if (TW) FASST_HIP(hipMemcpy(TW, x.tw, (size_t)x.Kw * c->T * sizeof(double), hipMemcpyDeviceToHost));
+  return FASST_OK;
+}
+
+int fasst_sf_renormalize(fasst_ctx *c, int *restart_mask) {
+  int st = need_sf(c, 0);
+  if (st) return st;
+  DeviceGuard g(c->device);
+  FASST_HIP(hipMemsetAsync(c->sf->flags.p, 0, (1 + 2 * kMaxJ) * sizeof(int), c->stream));
+  if ((st = sf_renormalize(c))) return st;
+  int mask = 0;
+  if ((st = sf_flags_mask(c, &mask))) return st;
+  if (restart_mask) *restart_mask = mask;
+  return FASST_OK;
+}
+
+int fasst_sf_run(fasst_ctx *c, int n_iter, const double *psd, double omega, double *logliks,
+                 int *restart_mask, int *iters_done) {
+  int st = need_sf(c, 0);
+  if (st) return st;
+  if (n_iter < 0 || (n_iter > 0 && (!psd || !logliks))) return FASST_ERR_SHAPE;
+  if (!c->cx_ready) {
+    set_error("fasst_sf_run: no observation resident (upload Cx first)");
+    return FASST_ERR_SHAPE;
+  }
+  fasst_sf_model *m = c->sf;
+  DeviceGuard g(c->device);
+  if (iters_done) *iters_done = 0;
+  if (restart_mask) *restart_mask = 0;
+  if (n_iter == 0) return FASST_OK;
+  if (m->psd_cap < n_iter) {
+    FASST_HIP(hipStreamSynchronize(c->stream));
+    if ((st = m->psd.alloc((size_t)n_iter * c->F)) || (st = m->ll.alloc(n_iter))) return st;
+    m->psd_cap = n_iter;
+  }
+  FASST_HIP(hipMemcpyAsync(m->psd.p, psd, (size_t)n_iter * c->F * sizeof(double), hipMemcpyHostToDevice,
+                           c->stream));
+  FASST_HIP(hipMemsetAsync(m->flags.p, 0, (1 + 2 * kMaxJ) * sizeof(int), c->stream));
+  int nconv = 0;
+  for (int j = 0; j < m->J; ++j)
+    if (m->conv[j] && m->spat_free[j]) nconv += m->rank[j];
+  if (nconv && nconv != m->R) {
+    set_error("update_mix_matrix: a free 'conv' component next to other components");
+    return FASST_ERR_SHAPE;
+  }
+  int done = 0, mask = 0;
+  for (int it = 0; it < n_iter; ++it) {
+    if ((st = sf_iteration(c, m->psd.p + (size_t)it * c->F, m->ll.p + it, omega, nconv))) return st;
+    if ((st = sf_flags_mask(c, &mask))) return st;
+    done = it + 1;
+    if (mask) break;
+  }
+  if (iters_done) *iters_done = done;
+  FASST_HIP(hipMemcpy(logliks, m->ll.p, (size_t)done * sizeof(double), hipMemcpyDeviceToHost));
+  if (mask) {
+    if (restart_mask) *restart_mask = mask;
+    return FASST_TW_RESTART;
+  }
+  return FASST_OK;
+}
+
+int fasst_sf_wiener_images(fasst_ctx *c, const double *psd, int nsrc, const int *src_of, double *S) {
+  int st = need_sf(c, 0);
+  if (st) return st;
+  if (!psd || !S) return FASST_ERR_SHAPE;
+  if ((st = sf_check_sources(c, nsrc, src_of))) return st;
+  if (!c->have_X) {
+    set_error("fasst_sf_wiener_images: no STFT available (set_audio / set_stft)");
+    return FASST_ERR_SHAPE;
+  }
+  DeviceGuard g(c->device);
+  const size_t FT = (size_t)c->F * c->T;
+  DBuf<double> dpsd;
+  DBuf<double2> dS;
+  if ((st = dpsd.alloc_uninit(c->F)) || (st = dS.alloc_uninit((size_t)nsrc * 2 * FT))) return st;
+  FASST_HIP(hipMemcpyAsync(dpsd.p, psd, c->F * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if ((st = sf_all_powers(c))) return st;
+  if ((st = sf_launch_wiener(c, dpsd.p, nsrc, src_of, dS.p, FT, (size_t)c->T, 1))) return st;
+  FASST_HIP(hipMemcpyAsync(S, dS.p, dS.n * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+  FASST_HIP(hipStreamSynchronize(c->stream));
+  return FASST_OK;
+}
+
+int fasst_sf_separate_waveforms(fasst_ctx *c, const double *psd, int nsrc, const int *src_of,
+                                const double *window, const double *analysis_window, int wlen,
+                                int nfft, int hop, double *y) {
+  int st = need_sf(c, 0);
+  if (st) return st;
+  if (!psd || !window || !y) return FASST_ERR_SHAPE;
+  if ((st = sf_check_sources(c, nsrc, src_of))) return st;
+  if (nfft < 2 || nfft / 2 + 1 != c->F || wlen < 2 || wlen > nfft || hop < 1) {
+    set_error("fasst_sf_separate_waveforms: nfft=%d wlen=%d hop=%d for F=%d", nfft, wlen, hop, c->F);
+    return FASST_ERR_SHAPE;
+  }
+  if (!c->have_X) {
+    set_error("fasst_sf_separate_waveforms: no STFT available (set_audio / set_stft)");
+    return FASST_ERR_SHAPE;
+  }
+  DeviceGuard g(c->device);
+  const int T = c->T;
+  const size_t plane = (size_t)c->Tp * c->Fp;
+  const int len_out = hop * (T - 1) + wlen - wlen / 2;
+  DBuf<double> dpsd, dw, daw, dframes, dy;
+  DBuf<double2> dS, dtw;
+  if ((st = dpsd.alloc_uninit(c->F)) || (st = dS.alloc((size_t)nsrc * 2 * plane)) || (st = dw.alloc(wlen)) ||
+      (st = daw.alloc(wlen)) || (st = dtw.alloc(nfft / 2)) || (st = dframes.alloc((size_t)T * wlen)) ||
+      (st = dy.alloc((size_t)nsrc * 2 * len_out)))
+    return st;
+  auto tw = twiddles(nfft, +1);
+  FASST_HIP(hipMemcpyAsync(dpsd.p, psd, c->F * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  FASST_HIP(hipMemcpyAsync(dw.p, window, (size_t)wlen * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  FASST_HIP(hipMemcpyAsync(daw.p, analysis_window ? analysis_window : window, (size_t)wlen * sizeof(double),
+                           hipMemcpyHostToDevice, c->stream));
+  FASST_HIP(hipMemcpyAsync(dtw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+  if ((st = sf_all_powers(c))) return st;
+  // images frame-major [Tp][Fp], the layout the device iSTFT reads
+  if ((st = sf_launch_wiener(c, dpsd.p, nsrc, src_of, dS.p, plane, 1, (size_t)c->Fp))) return st;
+  for (int q = 0; q < 2 * nsrc; ++q)
+    if ((st = tf_launch_istft(c->stream, dS.p + (size_t)q * plane, c->Fp, T, dw.p, daw.p, dtw.p, wlen, nfft,
+                              hop, dframes.p, dy.p + (size_t)q * len_out, len_out)))
+      return st;
+  FASST_HIP(hipMemcpyAsync(y, dy.p, dy.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  FASST_HIP(hipStreamSynchronize(c->stream));
+  return FASST_OK;
+}
+
+}  // extern "C"

@@ -16,6 +16,7 @@
 // algebra as the fused E-step (S = Sigma_x^-1, N = S Cx S - S, P = Cx S; the
 // R x R pair loop becomes per-bin t-reductions of V_r1 V_r2 N and V_r P).
 #include "fasst_ctx.h"
+#include "fasst_sf.h"
 
 #include <cmath>
 #include <vector>
@@ -56,7 +57,8 @@ constexpr int kSsTile = 256;
 constexpr int kSsMaxOut = 4 * (kStepMaxR * (kStepMaxR + 1) / 2) + 8 * kStepMaxR + kStepMaxR;
 struct SSArgs {
   const double *cx00, *cx11, *cxr, *cxi;  // [Tp][Fp]
-  const double *V;                        // [R][F][T]
+  const double *V;                        // [.][F][T]; rank r reads plane vmap[r]
+  int vmap[kStepMaxR];
   const double2 *mix;                     // [R][2][F]
   const double *psd;                      // [F]
   double2 *rss, *rxs;                     // [F][R][R], [F][2][R]
@@ -77,7 +79,9 @@ __global__ __launch_bounds__(kSsTile) void k_suff_stat(const SSArgs a) {
   __shared__ double s_red[kSsTile];
   __shared__ unsigned char s_p1[kSsMaxOut], s_p2[kSsMaxOut];
   __shared__ double2 s_m[kStepMaxR * kStepMaxR];
+  __shared__ int s_vm[kStepMaxR];
   if (tid < R) {
+    s_vm[tid] = a.vmap[tid];
     const double2 a0 = a.mix[((size_t)tid * 2 + 0) * a.F + f], a1 = a.mix[((size_t)tid * 2 + 1) * a.F + f];
     s_a[tid][0] = a0;
     s_a[tid][1] = a1;
@@ -121,7 +125,7 @@ __global__ __launch_bounds__(kSsTile) void k_suff_stat(const SSArgs a) {
       xis += xi;
       double d0 = psd, d1 = psd, ore = 0.0, oim = 0.0;
       for (int r = 0; r < R; ++r) {
-        const double v = a.V[((size_t)r * a.F + f) * a.T + t];
+        const double v = a.V[((size_t)s_vm[r] * a.F + f) * a.T + t];
         s_v[r][tid] = v;
         d0 += s_c[r][0] * v;
         d1 += s_c[r][1] * v;
@@ -495,6 +499,45 @@ __global__ void k_wiener_gain(const double *__restrict__ sd, const double2 *__re
 
 static int grid_of(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 16384); }
 
+int suff_stat_device(fasst_ctx *c, hipStream_t s, int R, const double *dV, const int *vmap,
+                     const double2 *dmix, const double *dpsd, double2 *drxx, double2 *drxs,
+                     double2 *drss, double *dws, double *dllb, double *dll) {
+  SSArgs a;
+  a.cx00 = c->cx.p;
+  a.cx11 = c->cx.p + (size_t)c->Tp * c->Fp;
+  a.cxr = c->cx.p + 2 * (size_t)c->Tp * c->Fp;
+  a.cxi = c->cx.p + 3 * (size_t)c->Tp * c->Fp;
+  a.V = dV;
+  for (int r = 0; r < kStepMaxR; ++r) a.vmap[r] = r < R ? vmap[r] : 0;
+  a.mix = dmix;
+  a.psd = dpsd;
+  a.rss = drss;
+  a.rxs = drxs;
+  a.rxx = drxx;
+  a.ws = dws;
+  a.llb = dllb;
+  a.F = c->F;
+  a.T = c->T;
+  a.Fp = c->Fp;
+  a.R = R;
+  k_suff_stat<<<c->F, kSsTile, 0, s>>>(a);
+  FASST_LAUNCH_CHECK();
+  k_ss_loglik<<<1, 256, 0, s>>>(dllb, c->F, 1.0 / ((double)c->F * (double)c->T), dll);
+  FASST_LAUNCH_CHECK();
+  return FASST_OK;
+}
+
+int mix_solve_device(hipStream_t s, int F, int R, const double2 *drss, const double2 *drxs,
+                     double2 *dmix, const int *dkind, int nconv, int *dsing) {
+  k_mix_solve_inst<<<1, 1024, 0, s>>>(drss, drxs, dmix, F, R, dkind, dsing);
+  FASST_LAUNCH_CHECK();
+  if (nconv) {
+    k_mix_solve_conv<<<(F + 63) / 64, 64, 0, s>>>(drss, drxs, dmix, F, R, dsing);
+    FASST_LAUNCH_CHECK();
+  }
+  return FASST_OK;
+}
+
 }  // namespace fasst
 
 using namespace fasst;
@@ -549,27 +592,11 @@ int fasst_suff_stat(fasst_ctx *c, int R, const double *V, const double *mix, con
   FASST_HIP(hipMemcpyAsync(dmix.p, mix, (size_t)R * 2 * c->F * sizeof(double2), hipMemcpyHostToDevice,
                            c->stream));
   FASST_HIP(hipMemcpyAsync(dpsd.p, psd, c->F * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  SSArgs a;
-  a.cx00 = c->cx.p;
-  a.cx11 = c->cx.p + (size_t)c->Tp * c->Fp;
-  a.cxr = c->cx.p + 2 * (size_t)c->Tp * c->Fp;
-  a.cxi = c->cx.p + 3 * (size_t)c->Tp * c->Fp;
-  a.V = dV.p;
-  a.mix = dmix.p;
-  a.psd = dpsd.p;
-  a.rss = drss.p;
-  a.rxs = drxs.p;
-  a.rxx = drxx.p;
-  a.ws = dws.p;
-  a.llb = dllb.p;
-  a.F = c->F;
-  a.T = c->T;
-  a.Fp = c->Fp;
-  a.R = R;
-  k_suff_stat<<<c->F, kSsTile, 0, c->stream>>>(a);
-  FASST_LAUNCH_CHECK();
-  k_ss_loglik<<<1, 256, 0, c->stream>>>(dllb.p, c->F, 1.0 / ((double)c->F * (double)c->T), dll.p);
-  FASST_LAUNCH_CHECK();
+  int vmap[kStepMaxR];
+  for (int r = 0; r < R; ++r) vmap[r] = r;
+  if ((st = suff_stat_device(c, c->stream, R, dV.p, vmap, dmix.p, dpsd.p, drxx.p, drxs.p, drss.p, dws.p,
+                             dllb.p, dll.p)))
+    return st;
   FASST_HIP(hipMemcpyAsync(rxx, drxx.p, 3 * c->F * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
   FASST_HIP(hipMemcpyAsync(rxs, drxs.p, (size_t)c->F * 2 * R * sizeof(double2), hipMemcpyDeviceToHost,
                            c->stream));

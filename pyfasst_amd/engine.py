@@ -50,6 +50,7 @@ class Engine(object):
         check(lib.fasst_create(self.device, self.F, self.T, ctypes.byref(h)), "fasst_create")
         self._h = h
         self.structure = None
+        self.sf = False   # a two-factor model is configured (sf_configure)
 
     # ------------------------------------------------------------ lifecycle
     def close(self):
@@ -69,8 +70,9 @@ class Engine(object):
         per = np.broadcast_to(np.asarray(conv, dtype=bool), (len(ranks),))
         key = (tuple(int(r) for r in ranks), tuple(int(k) for k in Ks),
                tuple(bool(c) for c in per))
-        if key == self.structure:
+        if key == self.structure and not self.sf:
             return
+        self.sf = False
         r = np.ascontiguousarray(ranks, dtype=np.int32)
         k = np.ascontiguousarray(Ks, dtype=np.int32)
         c = np.ascontiguousarray(per, dtype=np.int32)
@@ -200,10 +202,90 @@ class Engine(object):
               "fasst_get_spectral")
         return FB, FW, TW
 
+    # ------------------------------------------------------------ two-factor model
+    def sf_configure(self, ranks, conv, factors, alias):
+        """Two-factor model (fasst_sf_configure): factors[j] = [(Kb, Kw,
+        fb_free, fw_free, tw_free), ...] (one or two per spatial component),
+        alias[j][i] = (FB, FW, TW) indices 2 j' + i' of the earlier factor a
+        matrix is shared with, or -1."""
+        J = len(ranks)
+        r = np.ascontiguousarray(ranks, dtype=np.int32)
+        c = np.ascontiguousarray(np.broadcast_to(np.asarray(conv, dtype=bool), (J,)), dtype=np.int32)
+        nf = np.array([len(f) for f in factors], dtype=np.int32)
+        Kb = np.zeros((J, 2), dtype=np.int32)
+        Kw = np.zeros((J, 2), dtype=np.int32)
+        pri = np.zeros((J, 2, 3), dtype=np.int32)
+        al = -np.ones((J, 2, 3), dtype=np.int32)
+        for j, facs in enumerate(factors):
+            for i, (kb, kw, fb, fw, tw) in enumerate(facs):
+                Kb[j, i], Kw[j, i] = kb, kw
+                pri[j, i] = (bool(fb), bool(fw), bool(tw))
+                al[j, i] = alias[j][i]
+        check(lib.fasst_sf_configure(self._h, J, iptr(r), iptr(c), iptr(nf), iptr(Kb), iptr(Kw),
+                                     iptr(pri), iptr(al)), "fasst_sf_configure")
+        self.structure = (tuple(int(x) for x in r), None, tuple(bool(x) for x in c))
+        self.sf = True
+        self.sf_factors = [[(int(f[0]), int(f[1])) for f in facs] for facs in factors]
+
+    def sf_set_spatial(self, j, params, free):
+        p = np.ascontiguousarray(params, dtype=np.complex128)
+        check(lib.fasst_sf_set_spatial(self._h, int(j), dptr(p), int(bool(free))),
+              "fasst_sf_set_spatial")
+
+    def sf_get_spatial(self, j, shape):
+        out = np.empty(shape, dtype=np.complex128)
+        check(lib.fasst_sf_get_spatial(self._h, int(j), dptr(out)), "fasst_sf_get_spatial")
+        return out
+
+    def set_factors(self, j, i, FB, FW, TW):
+        kb, kw = self.sf_factors[j][i]
+        FB = np.ascontiguousarray(FB, dtype=np.float64)
+        FW = np.ascontiguousarray(FW, dtype=np.float64)
+        TW = np.ascontiguousarray(TW, dtype=np.float64)
+        if FB.shape != (self.F, kb) or FW.shape != (kb, kw) or TW.shape != (kw, self.T):
+            raise ValueError("factor %d of component %d: FB %s, FW %s, TW %s for F=%d, Kb=%d, "
+                             "Kw=%d, T=%d" % (i, j, FB.shape, FW.shape, TW.shape, self.F, kb, kw,
+                                              self.T))
+        check(lib.fasst_set_factors(self._h, int(j), int(i), dptr(FB), dptr(FW), dptr(TW)),
+              "fasst_set_factors")
+
+    def get_factors(self, j, i):
+        kb, kw = self.sf_factors[j][i]
+        FB = np.empty((self.F, kb))
+        FW = np.empty((kb, kw))
+        TW = np.empty((kw, self.T))
+        check(lib.fasst_get_factors(self._h, int(j), int(i), dptr(FB), dptr(FW), dptr(TW)),
+              "fasst_get_factors")
+        return FB, FW, TW
+
+    def _src_of(self, src_of):
+        s = np.ascontiguousarray(src_of, dtype=np.int32)
+        return s, int(s.max()) + 1
+
+    def sf_wiener_images(self, psd, src_of):
+        psd = np.ascontiguousarray(psd, dtype=np.float64)
+        s, n = self._src_of(src_of)
+        out = np.empty((n, 2, self.F, self.T), dtype=np.complex128)
+        check(lib.fasst_sf_wiener_images(self._h, dptr(psd), n, iptr(s), dptr(out)),
+              "fasst_sf_wiener_images")
+        return out
+
+    def sf_separate_waveforms(self, psd, src_of, window, analysis_window, nfft, hop):
+        psd = np.ascontiguousarray(psd, dtype=np.float64)
+        w = np.ascontiguousarray(window, dtype=np.float64)
+        aw = np.ascontiguousarray(analysis_window, dtype=np.float64)
+        s, n = self._src_of(src_of)
+        out = np.empty((n, 2, int(hop) * (self.T - 1) + w.size - w.size // 2))
+        check(lib.fasst_sf_separate_waveforms(self._h, dptr(psd), n, iptr(s), dptr(w), dptr(aw),
+                                              w.size, int(nfft), int(hop), dptr(out)),
+              "fasst_sf_separate_waveforms")
+        return out
+
     # ------------------------------------------------------------ compute
     def renormalize(self):
         mask = ctypes.c_int(0)
-        check(lib.fasst_renormalize(self._h, ctypes.byref(mask)), "fasst_renormalize")
+        fn = lib.fasst_sf_renormalize if self.sf else lib.fasst_renormalize
+        check(fn(self._h, ctypes.byref(mask)), "fasst_renormalize")
         return mask.value
 
     def run(self, psd_rows, omega):
@@ -215,8 +297,9 @@ class Engine(object):
         ll = np.zeros(max(n, 1))
         mask = ctypes.c_int(0)
         done = ctypes.c_int(0)
-        st = lib.fasst_run(self._h, n, dptr(psd_rows) if n else None, float(omega), dptr(ll),
-                           ctypes.byref(mask), ctypes.byref(done))
+        fn = lib.fasst_sf_run if self.sf else lib.fasst_run
+        st = fn(self._h, n, dptr(psd_rows) if n else None, float(omega), dptr(ll),
+                ctypes.byref(mask), ctypes.byref(done))
         if st == _lib.FASST_TW_RESTART:
             return ll[:done.value], done.value, mask.value
         check(st, "fasst_run")

@@ -20,6 +20,12 @@
                     time weights SHMM at K = 32 (TW_constr, audioModel.py:
                     1728-1928): ms per GEM iteration, and the two kernels of
                     the discrete-state TW step from fasst_kernel_times
+  --workload sf     one GEM iteration of the source / filter model
+                    (multiChanSourceF0Filter's default shape: 3 components,
+                    the F0 dictionary of minF0=39 .. maxF0=2000 at
+                    stepnoteF0=16 plus one column, 20 filter basis functions
+                    with 4 weights) at C3's signal size, on the engine (the
+                    class surface takes Kb <= 128)
   --workload viterbi  melody tracking (_tracking.pyx:11-93) at config 5:
                     S = 1092 F0 states, N = 20000 frames (runViterbi's
                     transitions, stepNotes 16): tracks/s, device time
@@ -421,10 +427,57 @@ def bench_viterbi(steps, warmup, S=1092, N=20000, seed=0):
                              "scaled to N=%d" % (n_cpu, N)}}
 
 
+def bench_sf(steps, warmup, F=2049, T=10000, seed=0):
+    """The two-factor path (csrc/fasst_sf.hip) at the reference class's default
+    shape: ms per GEM iteration (a host sync per iteration: the restart flags),
+    then the launch counts of a profiled iteration."""
+    from pyfasst_amd import synthetic
+    from pyfasst_amd.engine import Engine
+    nf0 = int(np.ceil(12.0 * 16 * np.log2(2000.0 / 39.0)) + 1) + 1     # + the column of ones
+    kf, kw, kres = 20, 4, 1
+    rs = np.random.RandomState(seed)
+    X = synthetic.stereo_mixture(F, T, J=3, K_true=8, rank=1, seed=seed)
+    eng = Engine(F, T, 0)
+    eng.set_stft(X)
+    pos = lambda *shape: 0.75 * np.abs(rs.randn(*shape)) + 0.25
+    factors = [[(nf0, nf0, False, False, True), (kf, kw, False, True, True)]] * 2 + \
+              [[(kres, kres, True, False, True)]]
+    alias = [[(-1, -1, -1), (-1, -1, -1)], [(0, 0, -1), (1, -1, -1)], [(-1, -1, -1)]]
+    eng.sf_configure([1, 1, 1], False, factors, alias)
+    src, filt = pos(F, nf0), pos(F, kf)
+    for j in range(3):
+        eng.sf_set_spatial(j, rs.randn(2, 1), True)
+    for j in range(2):
+        eng.set_factors(j, 0, src, np.eye(nf0), pos(nf0, T))
+        eng.set_factors(j, 1, filt, pos(kf, kw), pos(kw, T))
+    eng.set_factors(2, 0, pos(F, kres), np.eye(kres), pos(kres, T))
+    eng.renormalize()
+    psd = np.tile(eng.mix_psd() / 100., (max(steps, warmup, 1), 1))
+    eng.run(psd[:max(warmup, 1)], 1.0)
+    t0 = time.perf_counter()
+    eng.run(psd[:steps], 1.0)
+    dt = (time.perf_counter() - t0) / steps
+    eng.set_profiling(True)
+    eng.run(psd[:1], 1.0)
+    kt = eng.kernel_times()
+    eng.set_profiling(False)
+    gflop = 2.0 * 2 * F * nf0 * T * (3 + 2) / 1e9   # P0 three times, W0^T [rn | rd]: per SF component
+    return {"metric": "GEM iteration, source / filter model (two-factor path)",
+            "value": round(dt * 1e3, 3), "unit": "ms", "higher_is_better": False,
+            "steps": steps, "warmup": warmup, "dtype": "f64",
+            "data": "synthetic STFT-domain stereo mixture (seed %d), seeded positive factors" % seed,
+            "config": {"workload": "F=%d T=%d, 3 components: 2 x (FB %dx%d . I . TW %dxT) * "
+                                   "(FB %dx%d . FW %dx%d . TW %dxT) + 1 x NMF K=%d, rank 1 'inst'"
+                                   % (F, T, F, nf0, nf0, F, kf, kf, kw, kw, kres)},
+            "source_factor_gflop": round(gflop, 1),
+            "source_factor_tflops": round(gflop / 1e3 / dt, 2),
+            "launches_per_iteration": {k: int(v[1]) for k, v in sorted(kt.items())}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=("simm", "nmf", "cqt", "viterbi", "wf0", "separate",
-                                           "nnls", "spatial", "hmm"),
+                                           "nnls", "spatial", "hmm", "sf"),
                     required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -435,7 +488,7 @@ def main():
     NO_CPU = a.no_cpu_baseline
     fn = {"simm": bench_simm, "nmf": bench_nmf, "cqt": bench_cqt, "viterbi": bench_viterbi,
           "wf0": bench_wf0, "separate": bench_separate, "nnls": bench_nnls,
-          "spatial": bench_spatial, "hmm": bench_hmm}[a.workload]
+          "spatial": bench_spatial, "hmm": bench_hmm, "sf": bench_sf}[a.workload]
     out = fn(a.steps, a.warmup)
     if NO_CPU:
         out["cpu_baseline"] = None   # not measured (the sample above timed nothing)
