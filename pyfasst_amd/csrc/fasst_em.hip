@@ -3566,7 +3566,6 @@ static int launch_grid(size_t n, int block = 256) {
 static int estep_occupancy(const fasst_ctx *c);
 static int contract_occupancy(const fasst_ctx *c);
 static int twl_occupancy(const fasst_ctx *c, int *units);
-static int tpw_of(const fasst_ctx *c);
 // bins per block of the FW update's f-contraction (k_fw_reduce holds three
 // [fpc][KP] tiles in LDS: 96 KB at KP = 128 with 32 bins)
 static int fw_fpc(const fasst_ctx *c) { return c->KP > 64 ? 32 : kFwFpc; }
@@ -3795,10 +3794,17 @@ int build_inst_A(fasst_ctx *c) {
   return FASST_OK;
 }
 
+// W = FB.FW of the current parameters into wkf ([KP][Fp]) and, unless null,
+// wfk ([Fp][KP]), on stream s
+static void launch_w(fasst_ctx *c, double *wkf, double *wfk, hipStream_t s) {
+  (c->KP > 64 ? k_w_from_fb<true> : k_w_from_fb<false>)<<<dim3(c->nft, c->J), 256,
+                fw_lds(c, 16 * (c->KP + 1)), s>>>(c->FB.p, c->FW.p, wkf, wfk, c->J, c->Fp, c->KP,
+                                                  c->halt);
+}
+
 int launch_w_old(fasst_ctx *c) {
   prof_begin(c, KW);
-  (c->KP > 64 ? k_w_from_fb<true> : k_w_from_fb<false>)<<<dim3(c->nft, c->J), 256, fw_lds(c, 16 * (c->KP + 1)),
-                c->stream>>>(c->FB.p, c->FW.p, c->Wkf.p, nullptr, c->J, c->Fp, c->KP, c->halt);
+  launch_w(c, c->Wkf.p, nullptr, c->stream);
   prof_end(c, KW);
   FASST_LAUNCH_CHECK();
   return FASST_OK;
@@ -3858,6 +3864,224 @@ static int launch_tb_h(fasst_ctx *c, const TBArgs &a) {
            c->stream>>>(a);
   FASST_LAUNCH_CHECK();
   return FASST_OK;
+}
+
+// What one spectral step updates: the columns [kb0, kb1) of every source that
+// is `on`, under the priors of those columns.  b < 0: every source whole,
+// under its source-level priors (spectral_update); otherwise block b of every
+// source that has one (only_j < 0) or of source only_j alone, under the
+// block's priors (multi_step).  A discrete-state TW (twc) is never updated by
+// the contraction: tw is off for it in both forms.
+struct Step {
+  int on[kMaxJ], kb0[kMaxJ], kb1[kMaxJ], fb[kMaxJ], fw[kMaxJ], tw[kMaxJ];
+  bool any_fw;
+};
+
+static Step step_of(const fasst_ctx *c, int b = -1, int only_j = -1) {
+  Step s{};
+  for (int j = 0; j < c->J; ++j) {
+    const bool whole = b < 0;
+    if (!whole && !(b < c->nblk[j] && (only_j < 0 || j == only_j))) continue;
+    s.on[j] = 1;
+    s.kb0[j] = whole ? 0 : c->kb[j][b];
+    s.kb1[j] = whole ? c->K[j] : c->kb[j][b + 1];
+    s.fb[j] = (whole ? c->fb_free[j] : c->bfb[j][b]) != 0;
+    s.fw[j] = (whole ? c->fw_free[j] : c->bfw[j][b]) != 0;
+    s.tw[j] = (whole ? c->tw_free[j] : c->btw[j][b]) && !c->twc[j];
+    s.any_fw |= s.fw[j] != 0;
+  }
+  return s;
+}
+
+// The kernel-argument structs of a GEM iteration, one builder each: value-
+// initialised, every field that follows from the context (buffers, shapes,
+// chunking, halt) and from the step set here.  What a caller adds is named at
+// each builder; a pointer left out stays null.
+
+static EArgs e_args(const fasst_ctx *c, const double *psd_dev) {
+  EArgs e{};
+  const size_t plane = (size_t)c->Tp * c->Fp;
+  e.cx00 = c->cx.p;
+  e.cx11 = c->cx.p + plane;
+  e.cxr = c->cx.p + 2 * plane;
+  e.cxi = c->cx.p + 3 * plane;
+  e.TW = c->TW.p;
+  e.Wkf = c->Wkf.p;
+  e.A = c->A.p;
+  e.psd = psd_dev;
+  e.hatW = c->hatW.p;
+  e.halt = c->halt;
+  e.part = c->epart.p;
+  e.llpart = c->llpart.p;
+  e.F = c->F;
+  e.T = c->T;
+  e.Fp = c->Fp;
+  e.Tp = c->Tp;
+  e.KP = c->KP;
+  e.R = c->R;
+  e.ntt = c->ntt;
+  e.tpc = c->tpc_e;
+  e.nft = c->nft;
+  for (int j = 0; j <= kMaxJ; ++j) e.roff[j] = j <= c->J ? c->roff[j] : c->R;
+  return e;
+}
+
+// the caller adds the planes rnum / rden / rtw / rcp / rpow / roth and `first`
+static MPArgs mp_args(const fasst_ctx *c, const Step &s) {
+  MPArgs a{};
+  a.TW = c->TW.p;
+  a.Wkf = c->Wkf.p;
+  a.hatW = c->hatW.p;
+  a.lambda = c->lambda;
+  a.F = c->F;
+  a.T = c->T;
+  a.Fp = c->Fp;
+  a.Tp = c->Tp;
+  a.KP = c->KP;
+  a.J = c->J;
+  a.ntt = c->ntt;
+  a.tpc = c->tpc_b;
+  a.halt = c->halt;
+  for (int j = 0; j < kMaxJ; ++j) {
+    a.on[j] = s.on[j];
+    a.kb0[j] = s.kb0[j];
+    a.kb1[j] = s.kb1[j];
+  }
+  return a;
+}
+
+// the caller adds the ratio plane hatW and, for the DEN form, hatW2 and bden
+static BArgs b_args(const fasst_ctx *c, const Step &s) {
+  BArgs a{};
+  a.TW = c->TW.p;
+  a.Wkf = c->Wkf.p;
+  a.FWHt = c->FWHt.p;
+  a.bnum = c->bnum.p;
+  a.halt = c->halt;
+  a.F = c->F;
+  a.T = c->T;
+  a.Fp = c->Fp;
+  a.Tp = c->Tp;
+  a.KP = c->KP;
+  a.J = c->J;
+  a.ntt = c->ntt;
+  a.nft = c->nft;
+  a.tpc = c->tpc_b;
+  for (int j = 0; j < kMaxJ; ++j) a.fb_free[j] = s.fb[j];
+  return a;
+}
+
+// the caller adds bden (the contracted denominator) and the fused tail's pmax
+static UArgs u_args(const fasst_ctx *c, const Step &s, double omega) {
+  UArgs a{};
+  a.FB = c->FB.p;
+  a.FW = c->FW.p;
+  a.bnum = c->bnum.p;
+  a.hsum = c->hsum.p;
+  a.Wkf_new = c->Wkf_new.p;
+  a.Wfk_new = c->Wfk_new.p;
+  a.halt = c->halt;
+  a.F = c->F;
+  a.Fp = c->Fp;
+  a.KP = c->KP;
+  a.J = c->J;
+  a.nchunk = c->nchunk_b;
+  a.omega = omega;
+  for (int j = 0; j < kMaxJ; ++j) {
+    a.kb0[j] = s.kb0[j];
+    a.kb1[j] = s.kb1[j];
+    a.fb_free[j] = s.fb[j];
+  }
+  return a;
+}
+
+// the caller adds the ratio plane hatW and, for LAM, the planes cp / pw
+static FWArgs fw_args(const fasst_ctx *c, const Step &s, double omega) {
+  FWArgs a{};
+  a.TW = c->TW.p;
+  a.TWt = c->TWt.p;
+  a.Wkf_old = c->Wkf.p;
+  a.Wkf_mid = c->Wkf_new.p;
+  a.FB = c->FB.p;
+  a.gnum = c->bnum.p;
+  a.gden = c->gden.p;
+  a.pnum = c->pnum.p;
+  a.pden = c->pden.p;
+  a.FW = c->FW.p;
+  a.F = c->F;
+  a.T = c->T;
+  a.Fp = c->Fp;
+  a.Tp = c->Tp;
+  a.KP = c->KP;
+  a.J = c->J;
+  a.ntt = c->ntt;
+  a.tpc = c->tpc_b;
+  a.nchunk = c->nchunk_b;
+  a.fpc = fw_fpc(c);
+  a.nfc = (c->F + a.fpc - 1) / a.fpc;
+  a.omega = omega;
+  a.halt = c->halt;
+  for (int j = 0; j < kMaxJ; ++j) {
+    a.K[j] = j < c->J ? c->K[j] : 0;
+    a.fw_free[j] = s.fw[j];
+    a.kb0[j] = s.kb0[j];
+    a.kb1[j] = s.kb1[j];
+  }
+  return a;
+}
+
+// the caller adds the ratio plane hatW and, for LAM / TBQ, the planes cp / pw / oth
+static TArgs t_args(const fasst_ctx *c, const Step &s, double omega) {
+  TArgs a{};
+  a.TW = c->TW.p;
+  a.Wkf_old = c->Wkf.p;
+  a.Wkf_new = c->Wkf_new.p;
+  a.Wfk_new = c->Wfk_new.p;
+  a.tnum = c->tnum.p;
+  a.tden = c->tden.p;
+  a.halt = c->halt;
+  a.F = c->F;
+  a.T = c->T;
+  a.Fp = c->Fp;
+  a.Tp = c->Tp;
+  a.KP = c->KP;
+  a.J = c->J;
+  a.nft = c->nft;
+  a.ntt = c->ntt;
+  a.fpc = c->fpc_t;
+  a.omega = omega;
+  for (int j = 0; j < kMaxJ; ++j) {
+    a.tw_free[j] = s.tw[j];
+    a.kb0[j] = s.kb0[j];
+    a.kb1[j] = s.kb1[j];
+  }
+  return a;
+}
+
+// tbw (multi_step: the step's blocks whose TW goes through time blobs, null
+// otherwise): those rows are k_tb_tw_red / _apply's, not k_tw_update's.  The
+// caller adds the fused tail's scal / tpart / ntb / FWHt / hpart
+static TUArgs tu_args(const fasst_ctx *c, const Step &s, double omega, const TBArgs *tbw = nullptr) {
+  TUArgs a{};
+  a.TW = c->TW.p;
+  a.tnum = c->tnum.p;
+  a.tden = c->tden.p;
+  a.FW = c->FW.p;
+  a.halt = c->halt;
+  a.T = c->T;
+  a.Tp = c->Tp;
+  a.KP = c->KP;
+  a.J = c->J;
+  a.nsplit = c->nsplit_t;
+  a.omega = omega;
+  for (int j = 0; j < kMaxJ; ++j) {
+    a.kb0[j] = s.kb0[j];
+    a.kb1[j] = s.kb1[j];
+    a.tw_free[j] = s.tw[j] && !(tbw && tbw->tb[j]);
+    a.K[j] = j < c->J ? c->K[j] : 0;
+    a.soff[j] = j < c->J ? c->soff[j] : 0;
+  }
+  return a;
 }
 
 static RArgs renorm_args(fasst_ctx *c) {
@@ -4059,9 +4283,7 @@ static int launch_tail_side(fasst_ctx *c) {
   prof_end(c, KREN, side);
   // the next iteration's W (the TW contraction still reads Wkf)
   prof_begin(c, KW, side);
-  (c->KP > 64 ? k_w_from_fb<true> : k_w_from_fb<false>)<<<dim3(c->nft, c->J), 256,
-                fw_lds(c, 16 * (c->KP + 1)), side>>>(c->FB.p, c->FW.p, c->Wkf_next.p, nullptr,
-                                                     c->J, c->Fp, c->KP, c->halt);
+  launch_w(c, c->Wkf_next.p, nullptr, side);
   prof_end(c, KW, side);
   FASST_LAUNCH_CHECK();
   FASST_HIP(hipEventRecord(c->ev_rows, c->aux));
@@ -4141,16 +4363,31 @@ static int estep_occupancy(const fasst_ctx *c) {
   return occ;
 }
 
+// The spectral update's template arms, chosen from the model in one place:
+// `f` receives NKC = KP / 16 as a std::integral_constant<int, 1 | 2 | 4 | 8>
+// (launches and occupancy queries alike), and LAM as a std::bool_constant.
+template <class F>
+static void nkc_dispatch(const fasst_ctx *c, F &&f) {
+  switch (c->KP / 16) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;   // KP = 128
+  }
+}
+
+template <class F>
+static void lam_dispatch(const fasst_ctx *c, F &&f) {
+  if (c->lambda > 0.0)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+
 // frame tiles per wave of the TW contraction: KP = 128 keeps one (its
 // numerator / denominator tiles alone fill 128 VGPRs)
 template <int NKC>
 constexpr int tpw_for() { return NKC > 4 ? 1 : kTPW; }
-static int tpw_of(const fasst_ctx *c) { return c->KP > 64 ? 1 : kTPW; }
-
-static void launch_fw_reduce(fasst_ctx *c, const FWArgs &w) {
-  const size_t lds = (size_t)3 * w.fpc * c->KP * sizeof(double);   // (ceiling: set_lds_limits)
-  k_fw_reduce<<<dim3(w.nfc, c->J), 256, lds, c->stream>>>(w);
-}
 
 // k_tw_contract_lds's shape: 8 waves per block, one frame tile per wave, two
 // LDS stages (C3 same-box A/B, k_tw_contract 0.395 ms: NW x TPW x NS = 8 x 1 x
@@ -4160,64 +4397,50 @@ static void launch_fw_reduce(fasst_ctx *c, const FWArgs &w) {
 template <int NKC>
 using TwlShape = TwlCfg<NKC, 8, 1, 2>;
 
-template <int NKC>
-static void launch_contract(fasst_ctx *c, const BArgs &b, const TArgs &t, bool fb, int nz = 0) {
-  if (fb) {
-    prof_begin(c, KFBC);
-    k_fb_contract<NKC, kFPW><<<dim3((c->nft + kFPW - 1) / kFPW, c->J, nz ? nz : c->nchunk_b), 64,
-                               0, c->stream>>>(b);
-    prof_end(c, KFBC);
-    return;
-  }
-  using CF = TwlShape<NKC>;
+// The launches of the spectral update.  `timed`: with the per-kernel timing
+// events (spectral_update's launches record them, multi_step's none).
+
+// k_fb_contract, with DEN the contracted denominator of the multi-block update
+static void launch_fb_contract(fasst_ctx *c, const BArgs &b, bool den, bool timed) {
+  const dim3 g((c->nft + kFPW - 1) / kFPW, c->J, c->nchunk_b);
+  if (timed) prof_begin(c, KFBC);
+  nkc_dispatch(c, [&](auto n) {
+    constexpr int NKC = decltype(n)::value;
+    if (den)
+      k_fb_contract<NKC, kFPW, true><<<g, 64, 0, c->stream>>>(b);
+    else
+      k_fb_contract<NKC, kFPW><<<g, 64, 0, c->stream>>>(b);
+  });
+  if (timed) prof_end(c, KFBC);
+}
+
+// k_tw_contract_lds, the TW contraction of the single-component path
+static void launch_tw_contract_lds(fasst_ctx *c, const TArgs &t) {
   prof_begin(c, KTWC);
-  const int g = (c->ntt + CF::NW_ * CF::TPW_ - 1) / (CF::NW_ * CF::TPW_);
-  k_tw_contract_lds<CF><<<dim3(g, c->J, c->nsplit_t), CF::NT, CF::smem, c->stream>>>(t);
+  nkc_dispatch(c, [&](auto n) {
+    using CF = TwlShape<decltype(n)::value>;
+    const int g = (c->ntt + CF::NW_ * CF::TPW_ - 1) / (CF::NW_ * CF::TPW_);
+    k_tw_contract_lds<CF><<<dim3(g, c->J, c->nsplit_t), CF::NT, CF::smem, c->stream>>>(t);
+  });
   prof_end(c, KTWC);
 }
 
-// resident k_tw_contract_lds blocks per CU, and its frame-tile groups (units)
-template <int NKC>
-static int twl_occ_of(const fasst_ctx *c, int *units) {
-  using CF = TwlShape<NKC>;
-  (void)hipFuncSetAttribute((const void *)k_tw_contract_lds<CF>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF::smem);
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_tw_contract_lds<CF>, CF::NT, CF::smem) !=
-      hipSuccess)
-    n = 1;
-  *units = (c->ntt + CF::NW_ * CF::TPW_ - 1) / (CF::NW_ * CF::TPW_);
-  return std::max(1, n);
-}
-static int twl_occupancy(const fasst_ctx *c, int *units) {
-  switch (c->KP) {
-    case 16: return twl_occ_of<1>(c, units);
-    case 32: return twl_occ_of<2>(c, units);
-    case 64: return twl_occ_of<4>(c, units);
-    default: return twl_occ_of<8>(c, units);
-  }
+// k_tw_contract<BLK>, the TW contraction of one block (multi_step); tbq: its
+// TB-step form
+static void launch_tw_contract_blk(fasst_ctx *c, const TArgs &t, bool tbq) {
+  nkc_dispatch(c, [&](auto n) {
+    constexpr int NKC = decltype(n)::value, TPW = tpw_for<NKC>();
+    const dim3 g((c->ntt + TPW - 1) / TPW, c->J, c->nsplit_t);
+    lam_dispatch(c, [&](auto l) {
+      constexpr bool LAM = decltype(l)::value;
+      if (tbq)
+        k_tw_contract<NKC, TPW, true, LAM, true><<<g, 64, 0, c->stream>>>(t);
+      else
+        k_tw_contract<NKC, TPW, true, LAM><<<g, 64, 0, c->stream>>>(t);
+    });
+  });
 }
 
-// resident k_fb_contract waves per CU
-static int contract_occupancy(const fasst_ctx *c) {
-  int n = 1;
-  hipError_t e = hipSuccess;
-  switch (c->KP / 16) {
-    case 1: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fb_contract<1, kFPW>, 64, 0); break;
-    case 2: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fb_contract<2, kFPW>, 64, 0); break;
-    case 4: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fb_contract<4, kFPW>, 64, 0); break;
-    default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fb_contract<8, kFPW>, 64, 0); break;
-  }
-  return e == hipSuccess ? std::max(1, n) : 1;
-}
-
-// Spectral update of a model with several spectral components on some source
-// (see k_multi_prep): step b updates block b of every source that has one
-// (FB, then TW), all launches on c->stream; W = FB FW of the step's result
-// becomes the next step's current W.
-// one step: block b of every source that has one (only_j < 0), or of source
-// only_j alone (lambdaCorr > 0: the penalty couples the sources, so the
-// components go one at a time in the reference's key order)
 // The fused-tail pointers of k_fb_update / k_tw_update are null or the
 // context's own buffers; anything else is refused here, on the host, before a
 // kernel could dereference it (an uninitialised argument struct on the
@@ -4230,6 +4453,80 @@ static int check_tail_args(const fasst_ctx *c, const UArgs &u, const TUArgs &tu)
   if (ok_u && ok_t) return FASST_OK;
   set_error("internal: fused renormalisation arguments do not point at the context's buffers");
   return FASST_ERR_SHAPE;
+}
+
+// k_fb_update, after check_tail_args on the step's two update structs (the
+// only launch of k_fb_update; k_tw_update's is launch_tw_update)
+static int launch_fb_update(fasst_ctx *c, const UArgs &u, const TUArgs &tu, bool timed) {
+  if (int st = check_tail_args(c, u, tu)) return st;
+  if (timed) prof_begin(c, KFBU);
+  (c->KP > 64 ? k_fb_update<true> : k_fb_update<false>)<<<dim3(c->nft, c->J), 256,
+                fw_lds(c, 16 * (c->KP + 1) + c->KP + 16 * (c->KP + 1)),
+                c->stream>>>(u);
+  if (timed) prof_end(c, KFBU);
+  FASST_LAUNCH_CHECK();
+  return FASST_OK;
+}
+
+// k_tw_update; with the fused tail's FWHt it stages the block's TW rows in LDS
+static int launch_tw_update(fasst_ctx *c, const UArgs &u, const TUArgs &tu, bool timed) {
+  if (int st = check_tail_args(c, u, tu)) return st;
+  if (timed) prof_begin(c, KTWU);
+  k_tw_update<<<dim3(c->ntb, c->J), 256, tu.FWHt ? (size_t)c->KP * 64 * sizeof(double) : 0,
+                c->stream>>>(tu);
+  if (timed) prof_end(c, KTWU);
+  FASST_LAUNCH_CHECK();
+  return FASST_OK;
+}
+
+// The FW update (:1578-1631) of the step's free FW, between its FB and TW
+// updates: W_new = FB_new FW_old from k_fb_update is the V_mid operand
+// (blk: the component's own V), then W_new is rebuilt with FW_new
+static int launch_fw_update(fasst_ctx *c, const FWArgs &w, bool blk, bool timed) {
+  if (timed) prof_begin(c, KFWU);
+  const dim3 gc(c->nft, c->J, c->nchunk_b);
+  nkc_dispatch(c, [&](auto n) {
+    constexpr int NKC = decltype(n)::value;
+    if (!blk)
+      k_fw_contract<NKC><<<gc, 64, 0, c->stream>>>(w);
+    else
+      lam_dispatch(c, [&](auto l) {
+        k_fw_contract<NKC, true, decltype(l)::value><<<gc, 64, 0, c->stream>>>(w);
+      });
+  });
+  const size_t lds = (size_t)3 * w.fpc * c->KP * sizeof(double);   // (ceiling: set_lds_limits)
+  k_fw_reduce<<<dim3(w.nfc, c->J), 256, lds, c->stream>>>(w);
+  k_fw_final<<<c->J, 256, 0, c->stream>>>(w);
+  launch_w(c, c->Wkf_new.p, c->Wfk_new.p, c->stream);
+  if (timed) prof_end(c, KFWU);
+  FASST_LAUNCH_CHECK();
+  return FASST_OK;
+}
+
+// resident k_tw_contract_lds blocks per CU, and its frame-tile groups (units)
+static int twl_occupancy(const fasst_ctx *c, int *units) {
+  int n = 0;
+  nkc_dispatch(c, [&](auto k) {
+    using CF = TwlShape<decltype(k)::value>;
+    (void)hipFuncSetAttribute((const void *)k_tw_contract_lds<CF>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF::smem);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_tw_contract_lds<CF>, CF::NT,
+                                                     CF::smem) != hipSuccess)
+      n = 1;
+    *units = (c->ntt + CF::NW_ * CF::TPW_ - 1) / (CF::NW_ * CF::TPW_);
+  });
+  return std::max(1, n);
+}
+
+// resident k_fb_contract waves per CU
+static int contract_occupancy(const fasst_ctx *c) {
+  int n = 1;
+  hipError_t e = hipSuccess;
+  nkc_dispatch(c, [&](auto k) {
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fb_contract<decltype(k)::value, kFPW>,
+                                                     64, 0);
+  });
+  return e == hipSuccess ? std::max(1, n) : 1;
 }
 
 // source j's TW step is the discrete-state one (fasst_set_tw_constr)
@@ -4253,270 +4550,80 @@ static int launch_tw_constr(fasst_ctx *c, double omega, bool plane_is_hatw) {
   return st;
 }
 
+// Spectral update of a model with several spectral components on some source
+// (see k_multi_prep): step b updates block b of every source that has one
+// (FB, then TW), all launches on c->stream; W = FB FW of the step's result
+// becomes the next step's current W.
+// one step: block b of every source that has one (only_j < 0), or of source
+// only_j alone (lambdaCorr > 0: the penalty couples the sources, so the
+// components go one at a time in the reference's key order)
 static int multi_step(fasst_ctx *c, double omega, int b, int only_j) {
-  const int J = c->J, nkc = c->KP / 16;
+  const int J = c->J;
   const size_t plane = (size_t)J * c->Tp * c->Fp;
-  const bool lam = c->lambda > 0.0;
-  {
-    MPArgs mp{};
-    mp.TW = c->TW.p;
-    mp.Wkf = c->Wkf.p;
-    mp.hatW = c->hatW.p;
-    mp.rnum = c->mplanes.p;
-    mp.rden = c->mplanes.p + plane;
-    mp.rtw = c->mplanes.p + 2 * plane;
-    mp.rcp = c->mplanes.p + 3 * plane;
-    mp.rpow = c->mplanes.p + 4 * plane;
-    mp.roth = nullptr;
-    mp.lambda = c->lambda;
-    mp.F = c->F;
-    mp.T = c->T;
-    mp.Fp = c->Fp;
-    mp.Tp = c->Tp;
-    mp.KP = c->KP;
-    mp.J = J;
-    mp.ntt = c->ntt;
-    mp.tpc = c->tpc_b;
-    mp.first = b == 0;
-    mp.halt = c->halt;
-    BArgs bb{};
-    bb.TW = c->TW.p;
-    bb.Wkf = c->Wkf.p;
-    bb.FWHt = c->FWHt.p;
-    bb.hatW = mp.rnum;
-    bb.hatW2 = mp.rden;
-    bb.bnum = c->bnum.p;
-    bb.bden = c->bden.p;
-    bb.halt = c->halt;
-    bb.F = c->F;
-    bb.T = c->T;
-    bb.Fp = c->Fp;
-    bb.Tp = c->Tp;
-    bb.KP = c->KP;
-    bb.J = J;
-    bb.ntt = c->ntt;
-    bb.nft = c->nft;
-    bb.tpc = c->tpc_b;
-    bb.zbase = bb.tbase = 0;
-    UArgs u{};   // (pmax null: no fused-tail statistics on this path)
-    u.FB = c->FB.p;
-    u.FW = c->FW.p;
-    u.bnum = c->bnum.p;
-    u.bden = c->bden.p;
-    u.hsum = c->hsum.p;
-    u.Wkf_new = c->Wkf_new.p;
-    u.Wfk_new = c->Wfk_new.p;
-    u.halt = c->halt;
-    u.F = c->F;
-    u.Fp = c->Fp;
-    u.KP = c->KP;
-    u.J = J;
-    u.nchunk = c->nchunk_b;
-    u.omega = omega;
-    TArgs t{};
-    t.TW = c->TW.p;
-    t.Wkf_old = c->Wkf.p;
-    t.Wkf_new = c->Wkf_new.p;
-    t.Wfk_new = c->Wfk_new.p;
-    t.hatW = mp.rtw;
-    t.tnum = c->tnum.p;
-    t.tden = c->tden.p;
-    t.halt = c->halt;
-    t.F = c->F;
-    t.T = c->T;
-    t.Fp = c->Fp;
-    t.Tp = c->Tp;
-    t.KP = c->KP;
-    t.J = J;
-    t.nft = c->nft;
-    t.ntt = c->ntt;
-    t.fpc = c->fpc_t;
-    TUArgs tu{};   // (scal null: the plain TW update)
-    tu.TW = c->TW.p;
-    tu.tnum = c->tnum.p;
-    tu.tden = c->tden.p;
-    tu.halt = c->halt;
-    tu.T = c->T;
-    tu.Tp = c->Tp;
-    tu.KP = c->KP;
-    tu.J = J;
-    tu.nsplit = c->nsplit_t;
-    tu.omega = omega;
-    t.cp = mp.rcp;
-    t.pw = mp.rpow;
-    t.oth = nullptr;
-    t.omega = omega;
-    const TBArgs tbw = tb_args(c, b, only_j, 1, omega), tbb = tb_args(c, b, only_j, 2, omega);
-    int lmax, kwmax;
-    const bool any_tbb = tb_any(tbb, &lmax, &kwmax);
-    if (any_tbb) mp.roth = c->mplanes.p + 5 * plane;
-    for (int j = 0; j < kMaxJ; ++j) {
-      const bool has = j < J && b < c->nblk[j] && (only_j < 0 || j == only_j);
-      mp.on[j] = has;
-      const int k0 = has ? c->kb[j][b] : 0, k1 = has ? c->kb[j][b + 1] : 0;
-      mp.kb0[j] = u.kb0[j] = t.kb0[j] = tu.kb0[j] = k0;
-      mp.kb1[j] = u.kb1[j] = t.kb1[j] = tu.kb1[j] = k1;
-      bb.fb_free[j] = u.fb_free[j] = has && c->bfb[j][b];
-      t.tw_free[j] = has && c->btw[j][b] && !c->twc[j];
-      tu.tw_free[j] = t.tw_free[j] && !tbw.tb[j];   // time blobs: k_tb_tw_red / apply
-    }
-    const dim3 gp(c->nft, J, c->nchunk_b);
-    const dim3 gb((c->nft + kFPW - 1) / kFPW, J, c->nchunk_b);
-    const dim3 gt((c->ntt + tpw_of(c) - 1) / tpw_of(c), J, c->nsplit_t);
-    switch (nkc) {
-      case 1:
-        if (lam) k_multi_prep<1, true><<<gp, 64, 0, c->stream>>>(mp);
-        else k_multi_prep<1><<<gp, 64, 0, c->stream>>>(mp);
-        k_fb_contract<1, kFPW, true><<<gb, 64, 0, c->stream>>>(bb);
-        break;
-      case 2:
-        if (lam) k_multi_prep<2, true><<<gp, 64, 0, c->stream>>>(mp);
-        else k_multi_prep<2><<<gp, 64, 0, c->stream>>>(mp);
-        k_fb_contract<2, kFPW, true><<<gb, 64, 0, c->stream>>>(bb);
-        break;
-      case 4:
-        if (lam) k_multi_prep<4, true><<<gp, 64, 0, c->stream>>>(mp);
-        else k_multi_prep<4><<<gp, 64, 0, c->stream>>>(mp);
-        k_fb_contract<4, kFPW, true><<<gb, 64, 0, c->stream>>>(bb);
-        break;
-      default:   // KP = 128
-        if (lam) k_multi_prep<8, true><<<gp, 64, 0, c->stream>>>(mp);
-        else k_multi_prep<8><<<gp, 64, 0, c->stream>>>(mp);
-        k_fb_contract<8, kFPW, true><<<gb, 64, 0, c->stream>>>(bb);
-        break;
-    }
-    FASST_LAUNCH_CHECK();
-    if (int st = check_tail_args(c, u, tu)) return st;
-    (c->KP > 64 ? k_fb_update<true> : k_fb_update<false>)<<<dim3(c->nft, J), 256,
-                  fw_lds(c, 16 * (c->KP + 1) + c->KP + 16 * (c->KP + 1)),
-                  c->stream>>>(u);
-    FASST_LAUNCH_CHECK();
-    bool any_fw = false;
-    for (int j = 0; j < J; ++j) any_fw |= b < c->nblk[j] && c->bfw[j][b] && (only_j < 0 || j == only_j);
-    if (any_fw) {
-      // FW update of the step's components (:1578-1631): V_mid = (FB_new FW) H
-      // of the component, then W_new rebuilt with FW_new
-      FWArgs w{};
-      w.TW = c->TW.p;
-      w.TWt = c->TWt.p;
-      w.Wkf_old = c->Wkf.p;
-      w.Wkf_mid = c->Wkf_new.p;
-      w.hatW = mp.rtw;
-      w.FB = c->FB.p;
-      w.gnum = c->bnum.p;
-      w.gden = c->gden.p;
-      w.pnum = c->pnum.p;
-      w.pden = c->pden.p;
-      w.FW = c->FW.p;
-      w.F = c->F;
-      w.T = c->T;
-      w.Fp = c->Fp;
-      w.Tp = c->Tp;
-      w.KP = c->KP;
-      w.J = J;
-      w.ntt = c->ntt;
-      w.tpc = c->tpc_b;
-      w.nchunk = c->nchunk_b;
-      w.fpc = fw_fpc(c);
-      w.nfc = (c->F + w.fpc - 1) / w.fpc;
-      w.omega = omega;
-      w.halt = c->halt;
-      w.cp = mp.rcp;
-      w.pw = mp.rpow;
-      for (int j = 0; j < kMaxJ; ++j) {
-        const bool has = j < J && b < c->nblk[j] && (only_j < 0 || j == only_j);
-        w.K[j] = j < J ? c->K[j] : 0;
-        w.fw_free[j] = has && c->bfw[j][b];
-        w.kb0[j] = has ? c->kb[j][b] : 0;
-        w.kb1[j] = has ? c->kb[j][b + 1] : 0;
-      }
-      const dim3 gc(c->nft, J, c->nchunk_b);
-      switch (nkc) {
-        case 1:
-          if (lam) k_fw_contract<1, true, true><<<gc, 64, 0, c->stream>>>(w);
-          else k_fw_contract<1, true><<<gc, 64, 0, c->stream>>>(w);
-          break;
-        case 2:
-          if (lam) k_fw_contract<2, true, true><<<gc, 64, 0, c->stream>>>(w);
-          else k_fw_contract<2, true><<<gc, 64, 0, c->stream>>>(w);
-          break;
-        case 4:
-          if (lam) k_fw_contract<4, true, true><<<gc, 64, 0, c->stream>>>(w);
-          else k_fw_contract<4, true><<<gc, 64, 0, c->stream>>>(w);
-          break;
-        default:
-          if (lam) k_fw_contract<8, true, true><<<gc, 64, 0, c->stream>>>(w);
-          else k_fw_contract<8, true><<<gc, 64, 0, c->stream>>>(w);
-          break;
-      }
-      launch_fw_reduce(c, w);
-      k_fw_final<<<J, 256, 0, c->stream>>>(w);
-      (c->KP > 64 ? k_w_from_fb<true> : k_w_from_fb<false>)<<<dim3(c->nft, J), 256, fw_lds(c, 16 * (c->KP + 1)),
-                    c->stream>>>(c->FB.p, c->FW.p, c->Wkf_new.p, c->Wfk_new.p, J, c->Fp, c->KP,
-                                 c->halt);
-      FASST_LAUNCH_CHECK();
-    }
-    switch (nkc) {
-      case 1:
-        if (lam) k_tw_contract<1, kTPW, true, true><<<gt, 64, 0, c->stream>>>(t);
-        else k_tw_contract<1, kTPW, true><<<gt, 64, 0, c->stream>>>(t);
-        break;
-      case 2:
-        if (lam) k_tw_contract<2, kTPW, true, true><<<gt, 64, 0, c->stream>>>(t);
-        else k_tw_contract<2, kTPW, true><<<gt, 64, 0, c->stream>>>(t);
-        break;
-      case 4:
-        if (lam) k_tw_contract<4, kTPW, true, true><<<gt, 64, 0, c->stream>>>(t);
-        else k_tw_contract<4, kTPW, true><<<gt, 64, 0, c->stream>>>(t);
-        break;
-      default:   // (one frame tile per wave at KP = 128)
-        if (lam) k_tw_contract<8, 1, true, true><<<gt, 64, 0, c->stream>>>(t);
-        else k_tw_contract<8, 1, true><<<gt, 64, 0, c->stream>>>(t);
-        break;
-    }
-    FASST_LAUNCH_CHECK();
-    k_tw_update<<<dim3((c->Tp + 63) / 64, J), 256, 0, c->stream>>>(tu);
-    FASST_LAUNCH_CHECK();
-    if (tb_any(tbw, &lmax, &kwmax)) {   // TW with time blobs (:1665-1691)
-      k_tb_tw_red<<<dim3(lmax, (kwmax + 15) / 16, J), 256, 0, c->stream>>>(tbw);
-      k_tb_tw_apply<<<J, 256, 0, c->stream>>>(tbw);
-      FASST_LAUNCH_CHECK();
-      if (int st = launch_tb_h(c, tbw)) return st;
-    }
-    if (tb_any(tbb, &lmax, &kwmax)) {   // TB (:1931-1978) with the updated H
-      TArgs t2 = t;
-      t2.hatW = c->hatW.p;
-      t2.oth = mp.roth;
-      for (int j = 0; j < kMaxJ; ++j) t2.tw_free[j] = tbb.tb[j] != nullptr;
-      switch (nkc) {
-        case 1:
-          if (lam) k_tw_contract<1, kTPW, true, true, true><<<gt, 64, 0, c->stream>>>(t2);
-          else k_tw_contract<1, kTPW, true, false, true><<<gt, 64, 0, c->stream>>>(t2);
-          break;
-        case 2:
-          if (lam) k_tw_contract<2, kTPW, true, true, true><<<gt, 64, 0, c->stream>>>(t2);
-          else k_tw_contract<2, kTPW, true, false, true><<<gt, 64, 0, c->stream>>>(t2);
-          break;
-        case 4:
-          if (lam) k_tw_contract<4, kTPW, true, true, true><<<gt, 64, 0, c->stream>>>(t2);
-          else k_tw_contract<4, kTPW, true, false, true><<<gt, 64, 0, c->stream>>>(t2);
-          break;
-        default:
-          if (lam) k_tw_contract<8, 1, true, true, true><<<gt, 64, 0, c->stream>>>(t2);
-          else k_tw_contract<8, 1, true, false, true><<<gt, 64, 0, c->stream>>>(t2);
-          break;
-      }
-      k_tb_tb_upd<<<dim3((c->T + 63) / 64, J), 64,
-                    (size_t)(kwmax * lmax + 2 * 64 * lmax) * sizeof(double), c->stream>>>(tbb);
-      FASST_LAUNCH_CHECK();
-      if (int st = launch_tb_h(c, tbb)) return st;
-    }
-    if (c->anytwc && b == 0)   // (a constrained source has one component: block 0)
-      if (int st = launch_tw_constr(c, omega, true)) return st;
-    // the step's W = FB FW is the current W of the next step
-    FASST_HIP(hipMemcpyAsync(c->Wkf.p, c->Wkf_new.p, (size_t)J * c->KP * c->Fp * sizeof(double),
-                             hipMemcpyDeviceToDevice, c->stream));
+  const Step s = step_of(c, b, only_j);
+  const TBArgs tbw = tb_args(c, b, only_j, 1, omega), tbb = tb_args(c, b, only_j, 2, omega);
+  int lmax, kwmax;
+  const bool any_tbb = tb_any(tbb, &lmax, &kwmax);
+  MPArgs mp = mp_args(c, s);
+  mp.rnum = c->mplanes.p;
+  mp.rden = c->mplanes.p + plane;
+  mp.rtw = c->mplanes.p + 2 * plane;
+  mp.rcp = c->mplanes.p + 3 * plane;
+  mp.rpow = c->mplanes.p + 4 * plane;
+  if (any_tbb) mp.roth = c->mplanes.p + 5 * plane;
+  mp.first = b == 0;
+  BArgs bb = b_args(c, s);
+  bb.hatW = mp.rnum;
+  bb.hatW2 = mp.rden;
+  bb.bden = c->bden.p;
+  UArgs u = u_args(c, s, omega);   // (pmax null: no fused-tail statistics on this path)
+  u.bden = c->bden.p;
+  TArgs t = t_args(c, s, omega);
+  t.hatW = mp.rtw;
+  t.cp = mp.rcp;
+  t.pw = mp.rpow;
+  const TUArgs tu = tu_args(c, s, omega, &tbw);   // (scal null: the plain TW update)
+  nkc_dispatch(c, [&](auto n) {
+    lam_dispatch(c, [&](auto l) {
+      k_multi_prep<decltype(n)::value, decltype(l)::value>
+          <<<dim3(c->nft, J, c->nchunk_b), 64, 0, c->stream>>>(mp);
+    });
+  });
+  launch_fb_contract(c, bb, true, false);
+  FASST_LAUNCH_CHECK();
+  if (int st = launch_fb_update(c, u, tu, false)) return st;
+  if (s.any_fw) {   // V_mid = (FB_new FW) H of the component
+    FWArgs w = fw_args(c, s, omega);
+    w.hatW = mp.rtw;
+    w.cp = mp.rcp;
+    w.pw = mp.rpow;
+    if (int st = launch_fw_update(c, w, true, false)) return st;
   }
+  launch_tw_contract_blk(c, t, false);
+  FASST_LAUNCH_CHECK();
+  if (int st = launch_tw_update(c, u, tu, false)) return st;
+  if (tb_any(tbw, &lmax, &kwmax)) {   // TW with time blobs (:1665-1691)
+    k_tb_tw_red<<<dim3(lmax, (kwmax + 15) / 16, J), 256, 0, c->stream>>>(tbw);
+    k_tb_tw_apply<<<J, 256, 0, c->stream>>>(tbw);
+    FASST_LAUNCH_CHECK();
+    if (int st = launch_tb_h(c, tbw)) return st;
+  }
+  if (tb_any(tbb, &lmax, &kwmax)) {   // TB (:1931-1978) with the updated H
+    TArgs t2 = t;
+    t2.hatW = c->hatW.p;
+    t2.oth = mp.roth;
+    for (int j = 0; j < kMaxJ; ++j) t2.tw_free[j] = tbb.tb[j] != nullptr;
+    launch_tw_contract_blk(c, t2, true);
+    k_tb_tb_upd<<<dim3((c->T + 63) / 64, J), 64,
+                  (size_t)(kwmax * lmax + 2 * 64 * lmax) * sizeof(double), c->stream>>>(tbb);
+    FASST_LAUNCH_CHECK();
+    if (int st = launch_tb_h(c, tbb)) return st;
+  }
+  if (c->anytwc && b == 0)   // (a constrained source has one component: block 0)
+    if (int st = launch_tw_constr(c, omega, true)) return st;
+  // the step's W = FB FW is the current W of the next step
+  FASST_HIP(hipMemcpyAsync(c->Wkf.p, c->Wkf_new.p, (size_t)J * c->KP * c->Fp * sizeof(double),
+                           hipMemcpyDeviceToDevice, c->stream));
   return FASST_OK;
 }
 
@@ -4567,84 +4674,21 @@ static int launch_spectral_prep(fasst_ctx *c, bool fork) {
 // models inside gem_iteration): the fused renormalisation tail, its scales /
 // rescale forked onto the side stream beside the TW contraction
 static int spectral_update(fasst_ctx *c, double omega, bool tail = false) {
-  const int J = c->J;
-  const int nkc = c->KP / 16;
-  bool any_fw = false;
-  for (int j = 0; j < J; ++j) any_fw |= c->fw_free[j] != 0;
   if (c->anytwc && c->lambda > 0.0) {
     set_error("a discrete-state TW (TW_constr GSMM / SHMM) with lambdaCorr > 0 is outside the "
               "HIP path");
     return FASST_ERR_UNSUPPORTED;
   }
   if (c->multi) return multi_spectral(c, omega);
-  BArgs b{};
-  b.TW = c->TW.p;
-  b.Wkf = c->Wkf.p;
-  b.FWHt = c->FWHt.p;
-  b.hatW = c->hatW.p;
-  b.hatW2 = nullptr;
-  b.bnum = c->bnum.p;
-  b.bden = nullptr;
-  b.halt = c->halt;
-  b.F = c->F;
-  b.T = c->T;
-  b.Fp = c->Fp;
-  b.Tp = c->Tp;
-  b.KP = c->KP;
-  b.J = J;
-  b.ntt = c->ntt;
-  b.nft = c->nft;
-  b.tpc = c->tpc_b;
-  b.zbase = b.tbase = 0;
-  for (int j = 0; j < kMaxJ; ++j) b.fb_free[j] = j < J ? c->fb_free[j] : 0;
   // spectral update: FB then TW (one NMF factor per source)
-  TArgs t{};
-  t.TW = c->TW.p;
-  t.Wkf_old = c->Wkf.p;
-  t.Wkf_new = c->Wkf_new.p;
-  t.Wfk_new = c->Wfk_new.p;
-  t.hatW = c->hatW.p;
-  t.tnum = c->tnum.p;
-  t.halt = c->halt;
-  t.tden = c->tden.p;
-  t.F = c->F;
-  t.T = c->T;
-  t.Fp = c->Fp;
-  t.Tp = c->Tp;
-  t.KP = c->KP;
-  t.J = J;
-  t.nft = c->nft;
-  t.ntt = c->ntt;
-  t.fpc = c->fpc_t;
-  t.cp = t.pw = t.oth = nullptr;
-  t.omega = omega;
-  TUArgs tu{};
-  tu.TW = c->TW.p;
-  tu.tnum = c->tnum.p;
-  tu.halt = c->halt;
-  tu.tden = c->tden.p;
-  tu.T = c->T;
-  tu.Tp = c->Tp;
-  tu.KP = c->KP;
-  tu.J = J;
-  tu.nsplit = c->nsplit_t;
-  tu.omega = omega;
-  UArgs u{};
-  u.FB = c->FB.p;
-  u.FW = c->FW.p;
-  u.bnum = c->bnum.p;
-  u.halt = c->halt;
-  u.hsum = c->hsum.p;
-  u.Wkf_new = c->Wkf_new.p;
-  u.Wfk_new = c->Wfk_new.p;
-  u.F = c->F;
-  u.Fp = c->Fp;
-  u.KP = c->KP;
-  u.J = J;
-  u.nchunk = c->nchunk_b;
-  u.omega = omega;
-  u.bden = nullptr;
+  const Step s = step_of(c);
+  BArgs b = b_args(c, s);
+  b.hatW = c->hatW.p;
+  UArgs u = u_args(c, s, omega);
   u.pmax = tail ? c->rpmax2.p : nullptr;
+  TArgs t = t_args(c, s, omega);
+  t.hatW = c->hatW.p;
+  TUArgs tu = tu_args(c, s, omega);
   tu.scal = tail ? c->rscal.p : nullptr;
   tu.tpart = c->rtpart2.p;
   tu.ntb = c->ntb;
@@ -4652,99 +4696,23 @@ static int spectral_update(fasst_ctx *c, double omega, bool tail = false) {
   // (not at KP = 128: its 64 KB TW tile leaves k_tw_update one block per CU,
   // 0.12 -> 0.38 ms at J = 4, more than the 0.23 ms it takes off the E-step)
   const bool prep = tail && c->ftail >= 2 && c->KP <= 64;
-  tu.FW = c->FW.p;
   tu.FWHt = prep ? c->FWHt.p : nullptr;
   tu.hpart = c->hpart.p;
-  for (int j = 0; j < kMaxJ; ++j) {
-    tu.K[j] = j < J ? c->K[j] : 0;
-    tu.soff[j] = j < J ? c->soff[j] : 0;
-  }
-  for (int j = 0; j < kMaxJ; ++j) {
-    const bool in = j < J;
-    tu.kb0[j] = u.kb0[j] = t.kb0[j] = 0;
-    tu.kb1[j] = u.kb1[j] = t.kb1[j] = in ? c->K[j] : 0;
-    t.tw_free[j] = tu.tw_free[j] = in ? (c->tw_free[j] && !c->twc[j]) : 0;
-    u.fb_free[j] = in ? c->fb_free[j] : 0;
-  }
-  switch (nkc) {
-    case 1: launch_contract<1>(c, b, t, true); break;
-    case 2: launch_contract<2>(c, b, t, true); break;
-    case 4: launch_contract<4>(c, b, t, true); break;
-    default: launch_contract<8>(c, b, t, true); break;
-  }
+  launch_fb_contract(c, b, false, true);
   FASST_LAUNCH_CHECK();
-  if (int st = check_tail_args(c, u, tu)) return st;
-  prof_begin(c, KFBU);
-  (c->KP > 64 ? k_fb_update<true> : k_fb_update<false>)<<<dim3(c->nft, J), 256,
-                fw_lds(c, 16 * (c->KP + 1) + c->KP + 16 * (c->KP + 1)),
-                c->stream>>>(u);
-  prof_end(c, KFBU);
-  FASST_LAUNCH_CHECK();
+  if (int st = launch_fb_update(c, u, tu, true)) return st;
   if (tail)
     if (int st = launch_tail_side(c)) return st;
-  if (any_fw) {
-    // FW update (:1578-1631) between the FB and TW updates; W_new = FB_new FW_old
-    // from k_fb_update is the V_mid operand, then W_new is rebuilt with FW_new
-    FWArgs w{};
-    w.TW = c->TW.p;
-    w.TWt = c->TWt.p;
-    w.Wkf_old = c->Wkf.p;
-    w.Wkf_mid = c->Wkf_new.p;
+  if (s.any_fw) {
+    FWArgs w = fw_args(c, s, omega);
     w.hatW = c->hatW.p;
-    w.FB = c->FB.p;
-    w.gnum = c->bnum.p;
-    w.gden = c->gden.p;
-    w.pnum = c->pnum.p;
-    w.pden = c->pden.p;
-    w.FW = c->FW.p;
-    w.F = c->F;
-    w.T = c->T;
-    w.Fp = c->Fp;
-    w.Tp = c->Tp;
-    w.KP = c->KP;
-    w.J = J;
-    w.ntt = c->ntt;
-    w.tpc = c->tpc_b;
-    w.nchunk = c->nchunk_b;
-    w.fpc = fw_fpc(c);
-    w.nfc = (c->F + w.fpc - 1) / w.fpc;
-    w.omega = omega;
-    w.halt = c->halt;
-    for (int j = 0; j < kMaxJ; ++j) {
-      w.K[j] = j < J ? c->K[j] : 0;
-      w.fw_free[j] = j < J ? c->fw_free[j] : 0;
-      w.kb0[j] = 0;
-      w.kb1[j] = w.K[j];
-    }
-    prof_begin(c, KFWU);
-    const dim3 gc(c->nft, J, c->nchunk_b);
-    switch (nkc) {
-      case 1: k_fw_contract<1><<<gc, 64, 0, c->stream>>>(w); break;
-      case 2: k_fw_contract<2><<<gc, 64, 0, c->stream>>>(w); break;
-      case 4: k_fw_contract<4><<<gc, 64, 0, c->stream>>>(w); break;
-      default: k_fw_contract<8><<<gc, 64, 0, c->stream>>>(w); break;
-    }
-    launch_fw_reduce(c, w);
-    k_fw_final<<<J, 256, 0, c->stream>>>(w);
-    (c->KP > 64 ? k_w_from_fb<true> : k_w_from_fb<false>)<<<dim3(c->nft, J), 256, fw_lds(c, 16 * (c->KP + 1)),
-                  c->stream>>>(c->FB.p, c->FW.p, c->Wkf_new.p, c->Wfk_new.p, J, c->Fp, c->KP,
-                               c->halt);
-    prof_end(c, KFWU);
-    FASST_LAUNCH_CHECK();
+    if (int st = launch_fw_update(c, w, false, true)) return st;
   }
-  switch (nkc) {
-    case 1: launch_contract<1>(c, b, t, false); break;
-    case 2: launch_contract<2>(c, b, t, false); break;
-    case 4: launch_contract<4>(c, b, t, false); break;
-    default: launch_contract<8>(c, b, t, false); break;
-  }
+  launch_tw_contract_lds(c, t);
   FASST_LAUNCH_CHECK();
   // (prep reads the renormalised FW: wait for k_renorm_rows, else the scales)
   if (tail) FASST_HIP(hipStreamWaitEvent(c->stream, prep ? c->ev_rows : c->ev_scales, 0));
-  prof_begin(c, KTWU);
-  k_tw_update<<<dim3(c->ntb, J), 256, prep ? (size_t)c->KP * 64 * sizeof(double) : 0, c->stream>>>(tu);
-  prof_end(c, KTWU);
-  FASST_LAUNCH_CHECK();
+  if (int st = launch_tw_update(c, u, tu, true)) return st;
   if (c->anytwc) return launch_tw_constr(c, omega, false);
   return FASST_OK;
 }
@@ -4791,30 +4759,7 @@ static int gem_iteration(fasst_ctx *c, const double *psd_dev, double *ll_dev, do
   if (!w_ready && (st = launch_w_old(c))) return st;
   st = build_inst_A(c);
   if (st) return st;
-  EArgs e{};
-  e.cx00 = c->cx.p;
-  e.cx11 = c->cx.p + (size_t)c->Tp * c->Fp;
-  e.cxr = c->cx.p + 2 * (size_t)c->Tp * c->Fp;
-  e.cxi = c->cx.p + 3 * (size_t)c->Tp * c->Fp;
-  e.TW = c->TW.p;
-  e.Wkf = c->Wkf.p;
-  e.A = c->A.p;
-  e.psd = psd_dev;
-  e.hatW = c->hatW.p;
-  e.halt = c->halt;
-  e.part = c->epart.p;
-  e.llpart = c->llpart.p;
-  e.F = c->F;
-  e.T = c->T;
-  e.Fp = c->Fp;
-  e.Tp = c->Tp;
-  e.KP = c->KP;
-  e.R = c->R;
-  e.ntt = c->ntt;
-  e.tpc = c->tpc_e;
-  e.nft = c->nft;
-  for (int j = 0; j <= kMaxJ; ++j) e.roff[j] = j <= J ? c->roff[j] : c->R;
-  e.ybase = e.tbase = 0;
+  const EArgs e = e_args(c, psd_dev);
   if (J > 8 && c->KP <= 32) {   // the fused many-source E-step
     GArgs gg{};
     gg.J = J;
@@ -4832,12 +4777,11 @@ static int gem_iteration(fasst_ctx *c, const double *psd_dev, double *ll_dev, do
     gg.lw = c->lgen.p;
     gg.J = J;
     prof_begin(c, KESTEP);
-    switch (c->KP) {
-      case 16: k_egen_point<4><<<dim3(c->ntt, c->nft), 64, 0, c->stream>>>(e, gg); break;
-      case 32: k_egen_point<8><<<dim3(c->ntt, c->nft), 64, 0, c->stream>>>(e, gg); break;
-      case 64: k_egen_point<16><<<dim3(c->ntt, c->nft), 64, 0, c->stream>>>(e, gg); break;
-      default: k_egen_point<32><<<dim3(c->ntt, c->nft), 64, 0, c->stream>>>(e, gg); break;
-    }
+    nkc_dispatch(c, [&](auto n) {
+      constexpr int NKC = decltype(n)::value;
+      if constexpr (NKC >= 4)   // this path has KP > 32: the fused branch above took the rest
+        k_egen_point<4 * NKC><<<dim3(c->ntt, c->nft), 64, 0, c->stream>>>(e, gg);
+    });
     const size_t lds = (size_t)((J + 12) | 1) * 256 * sizeof(double);   // (ceiling: set_lds_limits)
     k_egen_stats<<<dim3(c->nft, c->nchunk_e), kEgsThreads, lds, c->stream>>>(e, gg);
     prof_end(c, KESTEP);
@@ -5411,10 +5355,6 @@ int fasst_run(fasst_ctx *c, int n_iter, const double *psd, double omega, double 
   }
   return FASST_OK;
 }
-
-}  // extern "C"
-
-extern "C" {
 
 int fasst_set_profiling(fasst_ctx *c, int on) {
   if (!c) return FASST_ERR_SHAPE;

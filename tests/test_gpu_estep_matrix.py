@@ -32,17 +32,15 @@ def estep_instance(J, K, ranks):
     """The E-step kernel instantiation fasst_run launches for J sources of at
     most K NMF columns each with these spatial ranks.  Restates
     pyfasst_amd/csrc/fasst_em.hip:
-      :3658       KP = K padded to 16 / 32 / 64 / 128 (NKS = KP / 4);
-      :4783-4811  gem_iteration: J > 8 with KP <= 32 -> k_egen_fused<NKS>,
-                  J > 8 otherwise -> k_egen_point<NKS> + k_egen_stats,
-                  else launch_estep -> k_estep_mx<J, NKS, RKU>;
-      :4072-4095  estep_dispatch_r / _j: RKU = 1 (every rank 1), 2 (every
-                  rank 2) or 0 (general ranks); KP = 128 has the general form
-                  only.
-    A change to those lines must be restated here, and the completeness test
-    then says which instantiations lost their case.
-    (k_egen_point<4> and k_egen_point<8>, :4801-4802, are dead: the :4783
-    branch takes every J > 8 model with KP <= 32.  Nothing here reaches them.)
+      configure_model   KP = K padded to 16 / 32 / 64 / 128 (NKS = KP / 4);
+      gem_iteration     J > 8 with KP <= 32 -> k_egen_fused<NKS>,
+                        J > 8 otherwise -> k_egen_point<NKS> + k_egen_stats,
+                        else launch_estep -> k_estep_mx<J, NKS, RKU>;
+      estep_dispatch_r / _j
+                        RKU = 1 (every rank 1), 2 (every rank 2) or 0
+                        (general ranks); KP = 128 has the general form only.
+    A change to those functions must be restated here, and the completeness
+    test then says which instantiations lost their case.
     """
     ranks = [ranks] * J if np.isscalar(ranks) else list(ranks)
     assert len(ranks) == J
@@ -234,7 +232,7 @@ def _run_case(J, K, ranks, chunks, monkeypatch, capfd, shape=None):
         " ".join("%s=%.3g" % kv for kv in sorted(d.items()))))
     if chunks:
         # a silently clamped chunk count would make this a repeat of the
-        # unchunked case (fasst_em.hip:3716-3720)
+        # unchunked case (configure_model's FASST_NCHUNK_E clamp in fasst_em.hip)
         assert "estep %d chunks" % chunks in err, err
     assert tw0 < 1e-14
     assert d['ll'] < 1e-10
