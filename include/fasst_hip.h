@@ -47,9 +47,19 @@ typedef struct fasst_ctx fasst_ctx;
  * and fasst_gcc_phat.  Revision 4 adds the discrete-state time weights
  * (fasst_set_tw_constr / fasst_get_tw_constr).  Revision 5 adds the two-factor
  * (source / filter) spectral components (fasst_sf_* and fasst_set_factors /
- * fasst_get_factors). */
-#define FASST_ABI_VERSION 5
+ * fasst_get_factors).  Revision 6 adds fasst_estep_partition. */
+#define FASST_ABI_VERSION 6
 int fasst_abi_version(void);
+
+/* The E-step's balanced schedule, host arithmetic only (no device call;
+ * pyfasst_amd/csrc/fasst_esched.h).  nbt bin tiles x Q quad-steps are the units
+ * u = bin_tile Q + q; block b of nb owns [lo[b], lo[b + 1]).  Fills lo[nb + 1],
+ * first[nbt] (the first block that meets each bin tile), nseg[nbt] (how many
+ * do: the bin tile's partial slots 0 .. nseg - 1) and *max_slots (the slots
+ * the context allocates for the E-step partials); a null pointer is skipped.
+ * Needs 1 <= nb <= nbt Q < 2^30. */
+int fasst_estep_partition(int nbt, int Q, int nb, long long *lo, int *first, int *nseg,
+                          int *max_slots);
 
 const char *fasst_last_error(void);
 int fasst_device_count(int *n);

@@ -17,6 +17,7 @@
 //   hatW    [J][Tp][Fp]         posterior source power hat_W
 #pragma once
 #include "fasst_common.h"
+#include "fasst_esched.h"
 
 struct fasst_sf_model;   // two-factor spectral components (fasst_sf.h)
 
@@ -88,6 +89,7 @@ struct fasst_ctx {
   fasst::DBuf<int> twante, twstate;
   // work space
   int nchunk_e = 1, tpc_e = 1, nchunk_b = 1, tpc_b = 1, nacc = 0;
+  fasst::ESched esched = {};   // the E-step's schedule and the layout of epart / llpart
   int nsplit_t = 1, fpc_t = 1;  // TW contraction bin chunks
   fasst::DBuf<double> epart, llpart, bnum, tnum, tden, psd, ll, hsum, rscal, rpmax, rpe, rtpart;
   fasst::DBuf<double> gden, TWt, pnum, pden;  // FW update (free FW)

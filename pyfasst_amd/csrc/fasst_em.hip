@@ -241,10 +241,11 @@ struct EArgs {
   const double2 *A;                       // [R][2][Fp]
   const double *psd;                      // [Fp]
   double *hatW;                           // [J][Tp][Fp]: rho = hat_W / max(V, eps)
-  double *part;                           // [nchunk][Fp][NACC]
-  double *llpart;                         // [nchunk][nft]
+  double *part;                           // [slot][Fp][NACC]
+  double *llpart;                         // [slot][nft]
   int F, T, Fp, Tp, KP, R, ntt, tpc, nft;
   int ybase, tbase;  // this launch's chunks start at partial ybase, frame tile tbase (ntt = end)
+  ESched es;         // the partials' layout (k_estep_mx: also its schedule; fasst_esched.h)
   int roff[kMaxJ + 1];
   const int *halt;
 };
@@ -393,22 +394,58 @@ void k_estep_mx(const EArgs a) {
   double *s_slab = s_w + (WL ? J * KP * 16 : 0);  // [4 waves][SLAB] operand slabs
   double *s_red = s_w;                     // [4][NACC][16 | 4] (epilogue, aliases W + slabs)
 
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  // The block's work: segments, each a run of frame tiles [tb, te) of one
+  // 16-bin tile whose statistics go to partial `slot`.  Chunk grid: one
+  // segment, (bin tile, chunk) = the XCD-ordered block (x, y).  Balanced
+  // schedule (fasst_esched.h): the quad-steps [wu, wend) of the flattened
+  // (bin tile, quad-step) list, cut where the bin tile changes; the XCD order
+  // gives each XCD a contiguous run of the list.  All of it is wave-uniform.
+  const dim3 bi = xcd_block();   // chunk grid: x: 16-bin tile, y: frame chunk
+  // (chunk grid: the one segment)
+  int btile = bi.x, tb = a.tbase + bi.y * a.tpc, te = min(tb + a.tpc, a.ntt);
+  int slot = a.ybase + bi.y;
+  int left = 0;   // balanced: quad-steps of the range after this segment
+  if (a.es.bal) {
+    // the range's first segment: the only divisions, ahead of the segment loop
+    // (inside it their loop-invariant parts stayed live across the tile loop)
+    const int blk = bi.x, Q = a.es.Q;
+    const long long U = (long long)a.es.nbt * Q;
+    const int wu = (int)es_lo(blk, U, a.es.nb), wend = (int)es_lo(blk + 1, U, a.es.nb);
+    btile = wu / Q;
+    const int q0 = wu - btile * Q, nq = min(Q - q0, wend - wu);
+    tb = a.tbase + 4 * q0;
+    te = min(tb + 4 * nq, a.ntt);
+    slot = blk - es_first(btile, Q, a.es.nbt, a.es.nb);
+    left = wend - wu - nq;
+  }
+  // (pinned to SGPRs: the tile loop's bounds and the buffer resources derive from them)
+  btile = __builtin_amdgcn_readfirstlane(btile);
+  tb = __builtin_amdgcn_readfirstlane(tb);
+  te = __builtin_amdgcn_readfirstlane(te);
+  slot = __builtin_amdgcn_readfirstlane(slot);
+  left = __builtin_amdgcn_readfirstlane(left);
+  for (;;) {
+  // launder: every per-thread value (the prologue's, the tile loop's and the
+  // epilogue's addresses) is formed per segment from this thread index, as in
+  // a kernel of one segment: the compiler would otherwise hoist them out of
+  // the segment loop and keep them live across the tile loop, ~30 registers
+  int tidp = threadIdx.x;
+  asm volatile("" : "+v"(tidp));
+  const int tid = tidp, lane = tid & 63, wv = tid >> 6;
   const int fl = lane & 15, tq = lane >> 4;
-  const dim3 bi = xcd_block();   // x: 16-bin tile, y: frame chunk
-  const int f0 = bi.x * 16;
-  const int f = f0 + fl;
   double *slab = s_slab + wv * S::SLAB;
+  const int f0 = btile * 16;
+  const int f = f0 + fl;
 
   if (WL)
-    for (int idx = tid; idx < J * KP * 16; idx += 256) {
+    for (int idx = tidp; idx < J * KP * 16; idx += 256) {
       const int ff = idx & 15, jk = idx >> 4;
       s_w[idx] = a.Wkf[(size_t)jk * a.Fp + f0 + ff];
     }
   // operand slots no point writes (sources >= J, pairs >= NP) stay zero
-  for (int idx = tid; idx < 4 * S::SLAB; idx += 256) s_slab[idx] = 0.0;
-  if (tid < 16) {
-    const int ff = f0 + tid;
+  for (int idx = tidp; idx < 4 * S::SLAB; idx += 256) s_slab[idx] = 0.0;
+  if (tidp < 16) {
+    const int ff = f0 + tidp;
 #pragma unroll
     for (int j = 0; j < J; ++j) {
       double al = 0, be = 0, gr = 0, gi = 0;
@@ -420,10 +457,10 @@ void k_estep_mx(const EArgs a) {
         gr += a0.x * a1.x + a0.y * a1.y;  // Re a0 conj(a1)
         gi += a0.y * a1.x - a0.x * a1.y;  // Im a0 conj(a1)
       }
-      s_cj[(j * 4 + 0) * 16 + tid] = al;
-      s_cj[(j * 4 + 1) * 16 + tid] = be;
-      s_cj[(j * 4 + 2) * 16 + tid] = gr;
-      s_cj[(j * 4 + 3) * 16 + tid] = gi;
+      s_cj[(j * 4 + 0) * 16 + tidp] = al;
+      s_cj[(j * 4 + 1) * 16 + tidp] = be;
+      s_cj[(j * 4 + 2) * 16 + tidp] = gr;
+      s_cj[(j * 4 + 3) * 16 + tidp] = gi;
     }
   }
   __syncthreads();
@@ -481,8 +518,6 @@ void k_estep_mx(const EArgs a) {
   }
   double ll = 0.0, lm = 1.0, lev = 0.0, xmin = 1.0;
 
-  const int tb = a.tbase + bi.y * a.tpc;
-  const int te = min(tb + a.tpc, a.ntt);
   // SA: wave-uniform buffer resources (SGPRs, formed on the scalar unit) +
   // 32-bit per-lane byte offsets instead of one 64-bit VALU address
   // computation per access
@@ -927,9 +962,12 @@ void k_estep_mx(const EArgs a) {
   // bin group at a time, [4][NACC][4], to fit the smaller slab allocation)
 #pragma unroll
   for (int mm = 1; mm < 64; mm <<= 1) ll += __shfl_xor(ll, mm, 64);
+  int tide = tid;   // (launder: see tidp)
+  asm volatile("" : "+v"(tide));
+  const int lanee = tide & 63, wve = tide >> 6;
   if constexpr (VR) {
     static_assert(4 * NACC * 4 <= 4 * S::SLAB, "VR epilogue fits the slabs");
-    const int m = lane >> 4, bb = (lane >> 2) & 3, n = lane & 3;
+    const int m = lanee >> 4, bb = (lanee >> 2) & 3, n = lanee & 3;
     double *red = s_slab;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -938,33 +976,32 @@ void k_estep_mx(const EArgs a) {
       for (int vg = 0; vg < NVG; ++vg) {
         const int j = 4 * vg + m;
         if (j < J) {
-          red[((wv * NACC) + 4 * NP + 8 * j + n) * 4 + bb] = xacc[g][vg][0];
-          red[((wv * NACC) + 4 * NP + 8 * j + 4 + n) * 4 + bb] = xacc[g][vg][1];
+          red[((wve * NACC) + 4 * NP + 8 * j + n) * 4 + bb] = xacc[g][vg][0];
+          red[((wve * NACC) + 4 * NP + 8 * j + 4 + n) * 4 + bb] = xacc[g][vg][1];
         }
       }
 #pragma unroll
       for (int h = 0; h < NPG; ++h) {
         const int p = rp_pair<J>(h, m);
-        if (p >= 0) red[((wv * NACC) + 4 * p + n) * 4 + bb] = pacc[g][h];
+        if (p >= 0) red[((wve * NACC) + 4 * p + n) * 4 + bb] = pacc[g][h];
       }
       __syncthreads();
-      for (int idx = tid; idx < NACC * 4; idx += 256) {
-        const int u = idx >> 2, ff = idx & 3;
-        const double x = red[(0 * NACC + u) * 4 + ff] + red[(1 * NACC + u) * 4 + ff] +
-                         red[(2 * NACC + u) * 4 + ff] + red[(3 * NACC + u) * 4 + ff];
-        a.part[((size_t)(a.ybase + bi.y) * a.Fp + f0 + 4 * g + ff) * NACC + u] = x;
+      for (int idx = tide; idx < NACC * 4; idx += 256) {
+        const int ac = idx >> 2, ff = idx & 3;
+        const double x = red[(0 * NACC + ac) * 4 + ff] + red[(1 * NACC + ac) * 4 + ff] +
+                         red[(2 * NACC + ac) * 4 + ff] + red[(3 * NACC + ac) * 4 + ff];
+        a.part[((size_t)slot * a.Fp + f0 + 4 * g + ff) * NACC + ac] = x;
       }
     }
-    if (lane == 0) s_ll[wv] = ll;
+    if (lanee == 0) s_ll[wve] = ll;
     __syncthreads();
-    if (tid == 0)
-      a.llpart[(a.ybase + bi.y) * a.nft + bi.x] = ((s_ll[0] + s_ll[1]) + s_ll[2]) + s_ll[3];
-    return;
-  }
+    if (tide == 0)
+      a.llpart[slot * a.nft + btile] = ((s_ll[0] + s_ll[1]) + s_ll[2]) + s_ll[3];
+  } else {
   __syncthreads();  // s_red aliases the W tile and the slabs
-  double *red = s_red + wv * NACC * 16;
+  double *red = s_red + wve * NACC * 16;
   {
-    const int m = lane >> 4, bb = (lane >> 2) & 3, n = lane & 3;
+    const int m = lanee >> 4, bb = (lanee >> 2) & 3, n = lanee & 3;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int bin = 4 * g + bb;
@@ -983,16 +1020,30 @@ void k_estep_mx(const EArgs a) {
       }
     }
   }
-  if (lane == 0) s_ll[wv] = ll;
+  if (lanee == 0) s_ll[wve] = ll;
   __syncthreads();
-  for (int idx = tid; idx < NACC * 16; idx += 256) {
-    const int u = idx >> 4, ff = idx & 15;
-    const double x = s_red[(0 * NACC + u) * 16 + ff] + s_red[(1 * NACC + u) * 16 + ff] +
-                     s_red[(2 * NACC + u) * 16 + ff] + s_red[(3 * NACC + u) * 16 + ff];
-    a.part[((size_t)(a.ybase + bi.y) * a.Fp + f0 + ff) * NACC + u] = x;
+  for (int idx = tide; idx < NACC * 16; idx += 256) {
+    const int ac = idx >> 4, ff = idx & 15;
+    const double x = s_red[(0 * NACC + ac) * 16 + ff] + s_red[(1 * NACC + ac) * 16 + ff] +
+                     s_red[(2 * NACC + ac) * 16 + ff] + s_red[(3 * NACC + ac) * 16 + ff];
+    a.part[((size_t)slot * a.Fp + f0 + ff) * NACC + ac] = x;
   }
-  if (tid == 0)
-    a.llpart[(a.ybase + bi.y) * a.nft + bi.x] = ((s_ll[0] + s_ll[1]) + s_ll[2]) + s_ll[3];
+  if (tide == 0)
+    a.llpart[slot * a.nft + btile] = ((s_ll[0] + s_ll[1]) + s_ll[2]) + s_ll[3];
+  }
+  // the next segment's prologue rewrites the W tile, the slabs and s_cj that
+  // this epilogue (s_red / red alias them) and this segment's tiles read
+  __syncthreads();
+  if (left <= 0) break;
+  // the next bin tile from its first quad-step: this block is the first to
+  // meet it, so the segment is the bin tile's slot 0
+  const int nq = min(a.es.Q, left);
+  ++btile;
+  slot = 0;
+  tb = a.tbase;
+  te = min(tb + 4 * nq, a.ntt);
+  left -= nq;
+  }  // segments
 }
 
 // ---------------------------------------------------------------- E-step, J > 8
@@ -1510,12 +1561,23 @@ __global__ void k_tw_rowsum(const double *__restrict__ TW, double *__restrict__ 
   if (threadIdx.x == 0) hsum[blockIdx.x] = s[0];
 }
 
-__global__ void k_loglik(const double *__restrict__ llpart, int n, double *__restrict__ out,
+// sum of the E-step's loglik partials [slot][bin tile]: the live entries
+// (slot < segments of the bin tile, fasst_esched.h) in index order, strided
+// over the 256 threads (a fixed order)
+__device__ __forceinline__ double ll_partial_sum(const double *__restrict__ llpart, const ESched es) {
+  double x = 0.0;
+  for (int i = threadIdx.x; i < es.nslot * es.nbt; i += 256) {
+    const int sl = i / es.nbt, bt = i - sl * es.nbt;
+    if (sl < es_segments(es, bt)) x += llpart[i];
+  }
+  return x;
+}
+
+__global__ void k_loglik(const double *__restrict__ llpart, const ESched es, double *__restrict__ out,
                          double inv_FT, const int *halt) {
   HALT_GUARD(halt);
   __shared__ double s[256];
-  double x = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) x += llpart[i];
+  const double x = ll_partial_sum(llpart, es);
   s[threadIdx.x] = x;
   __syncthreads();
   for (int w = 128; w > 0; w >>= 1) {
@@ -1543,13 +1605,14 @@ __device__ __forceinline__ double chunk_sum(const double *__restrict__ p, size_t
 
 // ---------------------------------------------------------------- mixing
 struct MArgs {
-  const double *part;  // [nchunk][Fp][NACC]
+  const double *part;  // [slot][Fp][NACC]
   const double *Wkf;   // [J][KP][Fp]   (W before the spectral update)
   const double *hsum;  // [J][KP]       sum_t TW
   double2 *A;          // [R][2][Fp]
   double2 *rss, *rxs;  // inst: [Fp][R][R], [Fp][2][R]
   int *flags;
-  int F, Fp, J, R, nchunk, nacc, conv_update, KP;
+  int F, Fp, J, R, nacc, conv_update, KP;
+  ESched es;           // layout of part
   double invT;
   int jr[kMaxR];
   const int *halt;
@@ -1611,13 +1674,15 @@ __global__ __launch_bounds__(64) void k_mix(const MArgs a) {
     double x[kQ] = {};
     const size_t cs = (size_t)a.Fp * NACC;
     const double *p0 = a.part + (size_t)f * NACC + lane;
-    for (int c = 0; c < a.nchunk; c += 8) {
+    // the bin's segments, slot order (fasst_esched.h: from the formula)
+    const int nseg = es_segments(a.es, f >> 4);
+    for (int c = 0; c < nseg; c += 8) {
       double v[kQ][8];
 #pragma unroll
       for (int q = 0; q < kQ; ++q)
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-          v[q][u] = (lane + 64 * q < NACC && c + u < a.nchunk) ? p0[(size_t)(c + u) * cs + 64 * q] : 0.0;
+          v[q][u] = (lane + 64 * q < NACC && c + u < nseg) ? p0[(size_t)(c + u) * cs + 64 * q] : 0.0;
 #pragma unroll
       for (int q = 0; q < kQ; ++q)
 #pragma unroll
@@ -2918,7 +2983,8 @@ struct RArgs {
   double *hsum;
   int J;
   double inv_FT;
-  int nstat, ntb, nll;
+  int nstat, ntb;
+  ESched es;   // layout of llpart
   int F, T, Fp, Tp, KP, nchunk, tpc, fpc, nslot;
   unsigned convm;    // bit j: spatial component j is 'conv' (per-bin filters in A)
   int K[kMaxJ], roff[kMaxJ + 1];
@@ -3291,8 +3357,7 @@ __global__ __launch_bounds__(256) void k_renorm_tail(const RArgs a, int iter) {
     return;
   }
   __shared__ double s[256];
-  double x = 0.0;
-  for (int i = threadIdx.x; i < a.nll; i += 256) x += a.llpart[i];
+  const double x = ll_partial_sum(a.llpart, a.es);
   s[threadIdx.x] = x;
   __syncthreads();
   for (int w = 128; w > 0; w >>= 1) {
@@ -3563,6 +3628,10 @@ static int launch_grid(size_t n, int block = 256) {
   return (int)(g ? g : 1);
 }
 
+// the E-step's default schedule and the fewest quad-steps a balanced block
+// takes by default (fasst_configure)
+constexpr bool kEsBalancedDefault = true;
+constexpr int kEsMinUnits = 10;
 static int estep_occupancy(const fasst_ctx *c);
 static int contract_occupancy(const fasst_ctx *c);
 static int twl_occupancy(const fasst_ctx *c, int *units);
@@ -3703,6 +3772,31 @@ int configure_model(fasst_ctx *c, int J, const int *rank, const int *K, const in
   if (const char *v = getenv("FASST_NCHUNK_E")) c->nchunk_e = std::max(1, std::min(atoi(v), c->ntt));
   c->tpc_e = (c->ntt + c->nchunk_e - 1) / c->nchunk_e;
   c->nchunk_e = (c->ntt + c->tpc_e - 1) / c->tpc_e;
+  // The single-pass E-step's schedule (k_estep_mx, J <= 8; fasst_esched.h).
+  // FASST_ESTEP_SCHED=chunk | balanced picks it (read here, once per
+  // configuration, like FASST_NCHUNK_E), FASST_ESTEP_NB sets the
+  // balanced schedule's block count.  Balanced: one round of resident blocks,
+  // each at least kEsMinUnits quad-steps (the per-segment prologue / epilogue
+  // stays small, as with the chunks of >= 40 frame tiles above) but never
+  // fewer blocks than bin tiles.
+  c->esched = ESched{};
+  c->esched.nbt = c->nft;
+  c->esched.nslot = c->nchunk_e;
+  {
+    // (an explicit FASST_NCHUNK_E asks for the chunk grid)
+    bool bal = kEsBalancedDefault && !getenv("FASST_NCHUNK_E");
+    if (const char *v = getenv("FASST_ESTEP_SCHED")) bal = !strcmp(v, "balanced");
+    const long long Q = (c->ntt + 3) / 4, U = (long long)c->nft * Q;
+    if (bal && J <= 8 && U < (1ll << 30)) {
+      long long nb = std::min(U, std::max<long long>(c->nft, std::min<long long>(cap_e, U / kEsMinUnits)));
+      if (const char *v = getenv("FASST_ESTEP_NB")) nb = atoll(v);
+      nb = std::max(1ll, std::min(nb, U));
+      c->esched.bal = 1;
+      c->esched.nb = (int)nb;
+      c->esched.Q = (int)Q;
+      c->esched.nslot = es_max_slots(c->nft, (int)Q, (int)nb);
+    }
+  }
   const long cap_b = (long)contract_occupancy(c) * ncu;
   c->nchunk_b = best_split((long)((c->nft + kFPW - 1) / kFPW) * J, cap_b, c->ntt / 32);
   if (const char *v = getenv("FASST_NCHUNK_B")) c->nchunk_b = std::max(1, std::min(atoi(v), c->ntt));
@@ -3720,9 +3814,10 @@ int configure_model(fasst_ctx *c, int J, const int *rank, const int *K, const in
   c->nsplit_t = (c->nft + c->fpc_t - 1) / c->fpc_t;
   if (getenv("FASST_VERBOSE"))
     fprintf(stderr,
-            "fasst: %d CUs; estep %d chunks (cap %ld blocks); fb %d chunks (cap %ld); tw %d "
+            "fasst: %d CUs; estep %d %s, %d slots (cap %ld blocks); fb %d chunks (cap %ld); tw %d "
             "splits (cap %ld)\n",
-            ncu, c->nchunk_e, cap_e, c->nchunk_b, cap_b, c->nsplit_t, cap_t);
+            ncu, c->esched.bal ? c->esched.nb : c->nchunk_e,
+            c->esched.bal ? "balanced blocks" : "chunks", c->esched.nslot, cap_e, c->nchunk_b, cap_b, c->nsplit_t, cap_t);
   const int NP = J * (J + 1) / 2;
   c->nacc = 4 * NP + 8 * J;
   int st;
@@ -3739,8 +3834,8 @@ int configure_model(fasst_ctx *c, int J, const int *rank, const int *K, const in
   ALLOC(A, (size_t)R * 2 * Fp);
   ALLOC(Pinst, (size_t)R * 2);
   // (+8 chunks: the interleaved E-step / FB ranges round their chunks up)
-  ALLOC(epart, (size_t)(c->nchunk_e + 8) * Fp * c->nacc);
-  ALLOC(llpart, (size_t)(c->nchunk_e + 8) * c->nft);
+  ALLOC(epart, (size_t)(c->esched.nslot + 8) * Fp * c->nacc);
+  ALLOC(llpart, (size_t)(c->esched.nslot + 8) * c->nft);
   ALLOC(bnum, (size_t)(c->nchunk_b + 8) * J * Fp * KP);
   // FW update (free FW only, allocated with the model so set_spectral may switch it on)
   ALLOC(gden, (size_t)c->nchunk_b * J * Fp * KP);
@@ -3922,6 +4017,7 @@ static EArgs e_args(const fasst_ctx *c, const double *psd_dev) {
   e.ntt = c->ntt;
   e.tpc = c->tpc_e;
   e.nft = c->nft;
+  e.es = c->esched;
   for (int j = 0; j <= kMaxJ; ++j) e.roff[j] = j <= c->J ? c->roff[j] : c->R;
   return e;
 }
@@ -4127,7 +4223,7 @@ static RArgs renorm_args(fasst_ctx *c) {
   r.inv_FT = 1.0 / ((double)c->F * (double)c->T);
   r.nstat = c->nft;
   r.ntb = c->ntb;
-  r.nll = c->nchunk_e * c->nft;
+  r.es = c->esched;
   return r;
 }
 
@@ -4215,7 +4311,7 @@ static int launch_mix(fasst_ctx *c, hipStream_t s) {
     m.Fp = c->Fp;
     m.J = J;
     m.R = c->R;
-    m.nchunk = c->nchunk_e;
+    m.es = c->esched;
     m.nacc = c->nacc;
     m.conv_update = c->conv ? 1 : 0;
     m.invT = 1.0 / (double)c->T;
@@ -4340,8 +4436,8 @@ static void launch_estep(fasst_ctx *c, const EArgs &e, int ny) {
   estep_dispatch(c, [&](auto tag) {
     using T = decltype(tag);
     prof_begin(c, KESTEP);
-    k_estep_mx<T::J, T::NKS, T::RKU>
-        <<<dim3(c->nft, ny), 256, estep_mx_smem<T::J, T::NKS>(), c->stream>>>(e);
+    const dim3 g = e.es.bal ? dim3(e.es.nb) : dim3(c->nft, ny);
+    k_estep_mx<T::J, T::NKS, T::RKU><<<g, 256, estep_mx_smem<T::J, T::NKS>(), c->stream>>>(e);
     prof_end(c, KESTEP);
   });
 }
@@ -4793,7 +4889,7 @@ static int gem_iteration(fasst_ctx *c, const double *psd_dev, double *ll_dev, do
   const bool ft = fast_tail(c);
   if (!ft) {   // (fused tail: summed by k_renorm_tail)
     prof_begin(c, KLL);
-    k_loglik<<<1, 256, 0, c->stream>>>(c->llpart.p, c->nchunk_e * c->nft, ll_dev,
+    k_loglik<<<1, 256, 0, c->stream>>>(c->llpart.p, c->esched, ll_dev,
                                        1.0 / ((double)c->F * (double)c->T), c->halt);
     prof_end(c, KLL);
     FASST_LAUNCH_CHECK();
@@ -4832,6 +4928,23 @@ extern "C" {
 const char *fasst_last_error(void) { return fasst::g_err.c_str(); }
 
 int fasst_abi_version(void) { return FASST_ABI_VERSION; }
+
+int fasst_estep_partition(int nbt, int Q, int nb, long long *lo, int *first, int *nseg,
+                          int *max_slots) {
+  if (nbt < 1 || Q < 1 || nb < 1 || (long long)nbt * Q >= (1ll << 30) || nb > (long long)nbt * Q) {
+    set_error("fasst_estep_partition: need 1 <= nb <= nbt Q < 2^30 (nbt=%d Q=%d nb=%d)", nbt, Q, nb);
+    return FASST_ERR_SHAPE;
+  }
+  const long long U = (long long)nbt * Q;
+  if (lo)
+    for (int b = 0; b <= nb; ++b) lo[b] = es_lo(b, U, nb);
+  for (int bt = 0; bt < nbt; ++bt) {
+    if (first) first[bt] = es_first(bt, Q, nbt, nb);
+    if (nseg) nseg[bt] = es_nseg(bt, Q, nbt, nb);
+  }
+  if (max_slots) *max_slots = es_max_slots(nbt, Q, nb);
+  return FASST_OK;
+}
 
 int fasst_device_count(int *n) {
   FASST_HIP(hipGetDeviceCount(n));
