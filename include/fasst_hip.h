@@ -47,8 +47,9 @@ typedef struct fasst_ctx fasst_ctx;
  * and fasst_gcc_phat.  Revision 4 adds the discrete-state time weights
  * (fasst_set_tw_constr / fasst_get_tw_constr).  Revision 5 adds the two-factor
  * (source / filter) spectral components (fasst_sf_* and fasst_set_factors /
- * fasst_get_factors).  Revision 6 adds fasst_estep_partition. */
-#define FASST_ABI_VERSION 6
+ * fasst_get_factors).  Revision 6 adds fasst_estep_partition.  Revision 7 adds
+ * the source / filter IS-NMF (sfnmf_*, fasst_nmf.h). */
+#define FASST_ABI_VERSION 7
 int fasst_abi_version(void);
 
 /* The E-step's balanced schedule, host arithmetic only (no device call;

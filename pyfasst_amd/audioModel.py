@@ -1266,8 +1266,10 @@ class multiChanSourceF0Filter(FASST):
     columns.  A model with `sparsity` set raises
     NotImplementedError from estim_param_a_post_model(): the reference's
     schedule needs a host step between iterations and a median filter the
-    package does not have.  initSpecCompsWithLabelAndFiles, initializeFreeMats
-    and the multichanLead subclass are outside the scope."""
+    package does not have.  initializeFreeMats() starts the source
+    activations from an IS-NMF of the mono power on the source dictionary, at
+    any dictionary width.  initSpecCompsWithLabelAndFiles and the
+    multichanLead subclass are outside the scope."""
 
     def __init__(self, audio, nbComps=3, nbNMFResComps=1, nbFilterComps=20, nbFilterWeigs=[4, ],
                  minF0=39, maxF0=2000, minF0search=80, maxF0search=800, stepnoteF0=16,
@@ -1391,6 +1393,22 @@ class multiChanSourceF0Filter(FASST):
         speccomp['FW'] = np.eye(ncomp)
         speccomp['TW'] = 0.75 * np.abs(np.random.randn(ncomp, self.nbFramesSigRepr)) + 0.25
         speccomp['FB_frdm_prior'] = FB_frdm_prior
+
+    def initializeFreeMats(self, niter=10):
+        """audioModel.py:2878-2908: IS-NMF of the mono power on the fixed
+        source dictionary (NMF_decomp_init with updateW=False, on the GPU at
+        any dictionary width), the activations shared out in place over the
+        source / filter components, then the renormalisation (on the host, as
+        the constructor's).  The residual component is left as it is."""
+        from .tools.nmf import NMF_decomp_init
+        W, H = NMF_decomp_init(SX=self._mono_power(),
+                               Winit=np.dot(self.sourceFreqComps,
+                                            self.spec_comps[0]['factor'][0]['FW']),
+                               verbose=self.verbose, nbComps=self.nbSourceComps, niter=niter,
+                               updateW=False, updateH=True, device=self.device)
+        for ncomp in range(self.nbComps - 1):
+            self.spec_comps[ncomp]['factor'][0]['TW'][:] = np.copy(H) / (self.nbComps - 1)
+        self._renormalize_host()
 
     def makeItConvolutive(self):
         """audioModel.py:2910-2931"""

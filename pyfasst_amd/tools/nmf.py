@@ -3,7 +3,8 @@
 `NMF_decomposition` (nmf.py:24-61) and `NMF_decomp_init` (nmf.py:63-159)
 keep the reference's signatures, random draws (NumPy's global stream, same
 order) and return values; the multiplicative-update loop runs in
-libfasst_hip.so (include/fasst_nmf.h).  No CPU fallback.
+libfasst_hip.so (include/fasst_nmf.h).  So does `SFNMF_decomp_init`
+(nmf.py:161-360), the source / filter model.  No CPU fallback.
 """
 import ctypes
 
@@ -76,6 +77,79 @@ def NMF_decomp_init(SX, nbComps=10, niter=10, verbose=0, Winit=None, Hinit=None,
         W /= W.sum(axis=0)
     W, H = _run(SX, W, Ht.T, niter, updateW, updateH, device)
     return W, H
+
+
+class _SfNmfContext(object):
+    def __init__(self, F, N, K, Kf, Kr, device):
+        self.ptr = ctypes.c_void_p()
+        _lib.check(_lib.lib.sfnmf_create(device, F, N, K, Kf, Kr, ctypes.byref(self.ptr)),
+                   "sfnmf_create")
+
+    def __del__(self):
+        if getattr(self, "ptr", None) is not None and self.ptr.value:
+            _lib.lib.sfnmf_destroy(self.ptr)
+            self.ptr = None
+
+
+def _run_sf(SX, mats, niter, switches, device):
+    """mats: W [F, K], H [K, N], WFilt, HFilt, Wres, Hres in the device layout;
+    returns the six updated matrices in the same layout."""
+    F, N = SX.shape
+    mats = [np.ascontiguousarray(m, dtype=np.float64) for m in mats]
+    dev = _lib.default_device() if device is None else device
+    ctx = _SfNmfContext(F, N, mats[0].shape[1], mats[2].shape[1], mats[4].shape[1], dev)
+    SXc = np.ascontiguousarray(SX, dtype=np.float64)
+    ptrs = [_lib.dptr(m) for m in mats]
+    _lib.check(_lib.lib.sfnmf_set_data(ctx.ptr, _lib.dptr(SXc)), "sfnmf_set_data")
+    _lib.check(_lib.lib.sfnmf_set_params(ctx.ptr, *ptrs), "sfnmf_set_params")
+    _lib.check(_lib.lib.sfnmf_run(ctx.ptr, int(niter), *[int(bool(s)) for s in switches]),
+               "sfnmf_run")
+    _lib.check(_lib.lib.sfnmf_get_params(ctx.ptr, *ptrs), "sfnmf_get_params")
+    return mats
+
+
+def SFNMF_decomp_init(SX, nbComps=10, nbFiltComps=10, niter=10, verbose=0, Winit=None,
+                      Hinit=None, WFiltInit=None, HFiltInit=None, updateW=True, updateH=True,
+                      updateWFilt=True, updateHFilt=True, nbResComps=2, device=None):
+    """Source / filter IS-NMF SX ~ (W H) * (WFilt HFilt) + Wres Hres
+    (nmf.py:161-360), the multiplicative updates on the GPU (sfnmf_run).
+
+    The random draws are the reference's, in its order, on NumPy's global
+    stream.  Hinit and HFiltInit are taken only as (nframes, nbComps), unlike
+    NMF_decomp_init.  Returns (W, H, WFilt, HFilt, Wres, Hres) with H and HFilt
+    as components x frames and Hres as frames x components, as the reference
+    does (:360).  verbose > 1 opens figures in the reference; here it prints.
+    """
+    freqs, nframes = SX.shape
+    if Winit is None or (Winit.shape != (freqs, nbComps)):
+        W = np.random.randn(freqs, nbComps) ** 2
+    else:
+        W = np.copy(Winit)
+    if Hinit is None or (Hinit.shape != (nframes, nbComps)):
+        H = np.random.randn(nframes, nbComps, ) ** 2
+    else:
+        H = np.copy(Hinit)
+    if updateW:
+        W /= W.sum(axis=0)
+    if WFiltInit is None or (WFiltInit.shape != (freqs, nbFiltComps)):
+        WFilt = np.random.randn(freqs, nbFiltComps) ** 2
+    else:
+        WFilt = np.copy(WFiltInit)
+    if HFiltInit is None or (HFiltInit.shape != (nframes, nbFiltComps)):
+        HFilt = np.random.randn(nframes, nbFiltComps, ) ** 2
+    else:
+        HFilt = np.copy(HFiltInit)
+    if updateWFilt:
+        WFilt /= WFilt.sum(axis=0)
+    Wres = (1 + np.random.randn(freqs, nbResComps)) ** 2
+    Hres = (1 + np.random.randn(nframes, nbResComps)) ** 2
+    if verbose:
+        print("    SFNMF: %d iterations on the GPU (W %s, H %s, WFilt %s, HFilt %s)"
+              % (niter, updateW, updateH, updateWFilt, updateHFilt))
+    W, H, WFilt, HFilt, Wres, Hres = _run_sf(
+        SX, [W, H.T, WFilt, HFilt.T, Wres, Hres.T], niter,
+        (updateW, updateH, updateWFilt, updateHFilt), device)
+    return W, H, WFilt, HFilt, Wres, np.ascontiguousarray(Hres.T)
 
 
 def _comp_source(comp_ind, K):

@@ -26,6 +26,10 @@
                     stepnoteF0=16 plus one column, 20 filter basis functions
                     with 4 weights) at C3's signal size, on the engine (the
                     class surface takes Kb <= 128)
+  --workload sfnmf  SFNMF_decomp_init (tools/nmf.py:161-360) at F = 2049,
+                    N = 10000 on the default F0 dictionary's width K = 1093,
+                    Kf = 10, Kr = 2: ms per iteration (sfnmf_run), and the
+                    CPU restatement's one iteration at the same size
   --workload viterbi  melody tracking (_tracking.pyx:11-93) at config 5:
                     S = 1092 F0 states, N = 20000 frames (runViterbi's
                     transitions, stepNotes 16): tracks/s, device time
@@ -474,10 +478,58 @@ def bench_sf(steps, warmup, F=2049, T=10000, seed=0):
             "launches_per_iteration": {k: int(v[1]) for k, v in sorted(kt.items())}}
 
 
+def bench_sfnmf(steps, warmup, F=2049, N=10000, K=1093, Kf=10, Kr=2, seed=0):
+    from pyfasst_amd import _lib
+    from pyfasst_amd.tools.nmf import _SfNmfContext
+    rs = np.random.RandomState(seed)
+    SX = rs.gamma(0.7, 1.0, size=(F, N))
+    mats = [rs.randn(F, K) ** 2, rs.randn(K, N) ** 2, rs.randn(F, Kf) ** 2, rs.randn(Kf, N) ** 2,
+            (1 + rs.randn(F, Kr)) ** 2, (1 + rs.randn(Kr, N)) ** 2]
+    mats[0] /= mats[0].sum(axis=0)
+    mats[2] /= mats[2].sum(axis=0)
+    ptrs = [_lib.dptr(m) for m in mats]
+    ctx = _SfNmfContext(F, N, K, Kf, Kr, _lib.default_device())
+    _lib.check(_lib.lib.sfnmf_set_data(ctx.ptr, _lib.dptr(SX)), "set_data")
+    _lib.check(_lib.lib.sfnmf_set_params(ctx.ptr, *ptrs), "set_params")
+    if warmup:
+        _lib.check(_lib.lib.sfnmf_run(ctx.ptr, warmup, 1, 1, 1, 1), "run")
+    t0 = time.perf_counter()
+    _lib.check(_lib.lib.sfnmf_run(ctx.ptr, steps, 1, 1, 1, 1), "run")
+    dt = time.perf_counter() - t0
+    # per iteration: SF0 formed 3 times, SPHI 3, Sres 2, and two planes per
+    # contraction of each of the six updates
+    flops = 2.0 * F * N * (K * (3 + 4) + Kf * (3 + 4) + Kr * (2 + 4))
+    achieved = flops / (dt / steps) / 1e12
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sfnmf_ref
+    cpu_s = None
+    if not NO_CPU:
+        np.random.seed(seed)
+        t1 = time.perf_counter()
+        sfnmf_ref.sfnmf_decomp_init(SX, nbComps=K, nbFiltComps=Kf, nbResComps=Kr, niter=1,
+                                    Winit=mats[0], Hinit=np.ascontiguousarray(mats[1].T),
+                                    WFiltInit=mats[2], HFiltInit=np.ascontiguousarray(mats[3].T))
+        cpu_s = time.perf_counter() - t1
+    return {"metric": "SFNMF_decomp_init ms per iteration", "value": round(dt / steps * 1e3, 4),
+            "unit": "ms/it", "ms_per_step": round(dt / steps * 1e3, 4), "steps": steps,
+            "warmup": warmup, "dtype": "f64", "data": "synthetic gamma spectrogram, RandomState(0)",
+            "config": {"workload": "source/filter IS-NMF F=%d N=%d K=%d Kf=%d Kr=%d"
+                       % (F, N, K, Kf, Kr)},
+            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": FP64_PEAK / 1e12,
+                         "unit": "TFLOP/s", "frac": round(achieved * 1e12 / FP64_PEAK, 4),
+                         "traffic": None,
+                         "scope": "whole iteration, GEMM flops 2FN(7K + 7Kf + 6Kr)"},
+            "gemm_tflops_per_s": round(achieved, 2),
+            "cpu_baseline": {"value": round(cpu_s * 1e3, 1) if cpu_s else None, "unit": "ms/it",
+                             "cores": _blas_threads(), "kind": "port",
+                             "sample": "tests/sfnmf_ref.py sfnmf_decomp_init, 1 iteration at the "
+                                       "full size"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=("simm", "nmf", "cqt", "viterbi", "wf0", "separate",
-                                           "nnls", "spatial", "hmm", "sf"),
+                                           "nnls", "spatial", "hmm", "sf", "sfnmf"),
                     required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -488,7 +540,8 @@ def main():
     NO_CPU = a.no_cpu_baseline
     fn = {"simm": bench_simm, "nmf": bench_nmf, "cqt": bench_cqt, "viterbi": bench_viterbi,
           "wf0": bench_wf0, "separate": bench_separate, "nnls": bench_nnls,
-          "spatial": bench_spatial, "hmm": bench_hmm, "sf": bench_sf}[a.workload]
+          "spatial": bench_spatial, "hmm": bench_hmm, "sf": bench_sf,
+          "sfnmf": bench_sfnmf}[a.workload]
     out = fn(a.steps, a.warmup)
     if NO_CPU:
         out["cpu_baseline"] = None   # not measured (the sample above timed nothing)
