@@ -1,6 +1,6 @@
 """ctypes binding of libfasst_hip.so (declared in include/fasst_hip.h,
 include/fasst_simm.h, include/fasst_nmf.h, include/fasst_cqt.h,
-include/fasst_viterbi.h and include/fasst_dict.h).
+include/fasst_viterbi.h, include/fasst_dict.h and include/fasst_sigtools.h).
 
 The product path has no CPU fallback: if the HIP library is missing this
 module raises at import time, and every compute call raises if the device
@@ -169,7 +169,28 @@ SFNMF_SIGNATURES = {
     "sfnmf_get_params": (ctypes.c_int, [_vp] + [_dp] * 6),
 }
 
-for _name, (_res, _args) in list(SIGNATURES.items()) + list(SFNMF_SIGNATURES.items()):
+# include/fasst_sigtools.h, the signal tools (`sig_` is not on that list either).
+# Each call also exists as `<name>_dev` with the same arguments, every array a
+# device pointer (sig_hsum_dev takes the length of bin_idx after it).
+_SIG_PCA = [ctypes.c_int] * 4 + [_dp] * 6 + [_ip]
+_SIG_MEDIAN = [ctypes.c_int] * 4 + [_dp, _dp]
+_SIG_INVHERM = [ctypes.c_int, ctypes.c_long, ctypes.c_int] + [_dp] * 6 + [_ip]
+SIG_SIGNATURES = {
+    "sig_pca2d": (ctypes.c_int, _SIG_PCA),
+    "sig_pca2d_dev": (ctypes.c_int, _SIG_PCA),
+    "sig_median": (ctypes.c_int, _SIG_MEDIAN),
+    "sig_median_dev": (ctypes.c_int, _SIG_MEDIAN),
+    "sig_hsum": (ctypes.c_int, [ctypes.c_int] * 5 + [_dp, _dp, _ip, _ip, ctypes.c_int, _dp]),
+    "sig_hsum_dev": (ctypes.c_int, [ctypes.c_int] * 5 + [_dp, _dp, _ip, _ip, ctypes.c_int,
+                                    ctypes.c_int, _dp]),
+    "sig_invherm": (ctypes.c_int, _SIG_INVHERM),
+    "sig_invherm_dev": (ctypes.c_int, _SIG_INVHERM),
+    "sig_launch_count": (ctypes.c_int, [ctypes.POINTER(ctypes.c_long)]),
+    "sig_last_ms": (ctypes.c_int, [_dp]),
+}
+
+for _name, (_res, _args) in (list(SIGNATURES.items()) + list(SFNMF_SIGNATURES.items()) +
+                             list(SIG_SIGNATURES.items())):
     _fn = getattr(lib, _name)
     _fn.restype = _res
     _fn.argtypes = _args

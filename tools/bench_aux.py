@@ -30,6 +30,11 @@
                     N = 10000 on the default F0 dictionary's width K = 1093,
                     Kf = 10, Kr = 2: ms per iteration (sfnmf_run), and the
                     CPU restatement's one iteration at the same size
+  --workload sigtools  tools/signalTools.py: prinComp2D at F = 2049, N = 10000,
+                    neighborNb = 20; harmonicSum at F = 2049, T = 10000 on the
+                    default F0 grid; medianFilter at 3 rows of N = 10000,
+                    length = 10: device ms (HIP events), host-inclusive ms,
+                    and the CPU restatement once per case
   --workload viterbi  melody tracking (_tracking.pyx:11-93) at config 5:
                     S = 1092 F0 states, N = 20000 frames (runViterbi's
                     transitions, stepNotes 16): tracks/s, device time
@@ -526,10 +531,77 @@ def bench_sfnmf(steps, warmup, F=2049, N=10000, K=1093, Kf=10, Kr=2, seed=0):
                                        "full size"}}
 
 
+def bench_sigtools(steps, warmup, F=2049, N=10000, seed=0):
+    from pyfasst_amd.tools import signalTools as st
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sigtools_ref as S
+    rs = np.random.RandomState(seed)
+    X0 = rs.randn(F, N) + 1j * rs.randn(F, N)
+    X1 = rs.randn(F, N) + 1j * rs.randn(F, N) + 0.5 * X0
+    TF = rs.gamma(0.7, 1.0, size=(F, N))
+    rows = rs.randn(3, N)
+    nb, length = 20, 10
+    L = N - nb + 1
+
+    def timed(fn, ref):
+        for _ in range(warmup):
+            fn()
+        dev, wall = [], []
+        for _ in range(steps):
+            t0 = time.perf_counter()
+            fn()
+            wall.append(time.perf_counter() - t0)
+            dev.append(st.last_ms())
+        cpu_s = None
+        if not NO_CPU:
+            t1 = time.perf_counter()
+            ref()
+            cpu_s = time.perf_counter() - t1
+        return float(np.median(dev)), float(np.median(wall)) * 1e3, cpu_s
+
+    def case(name, fn, ref, nbytes, what):
+        dev_ms, wall_ms, cpu_s = timed(fn, ref)
+        gbs = nbytes / (dev_ms * 1e-3) / 1e9
+        return {"case": name, "device_ms": round(dev_ms, 4), "host_inclusive_ms": round(wall_ms, 2),
+                "hbm_bytes": int(nbytes), "hbm_gb_per_s": round(gbs, 1),
+                "frac_of_measured_copy_6290": round(gbs / 6290., 4), "bytes_counted": what,
+                "cpu_restatement_ms": round(cpu_s * 1e3, 1) if cpu_s else None}
+
+    kw = dict(samplingrate=44100, fouriersize=2 * (F - 1))
+    ptr, _ = st.harmonic_bins(np.arange(F) * 44100 / np.double(2 * (F - 1)), st.f0_table(), 20, 0.5)
+    cases = [
+        case("prinComp2D F=%d N=%d neighborNb=%d" % (F, N, nb),
+             lambda: st.prinComp2D(X0, X1, neighborNb=nb), lambda: S.prin_comp_2d(X0, X1, nb),
+             2 * 16 * F * N + (2 * 8 + 4 * 16) * F * L, "both planes read once, six planes written"),
+        case("harmonicSum F=%d T=%d default grid (%d F0s, %d selected bins)"
+             % (F, N, st.f0_table().size, ptr[-1]),
+             lambda: st.harmonicSum(TF, **kw), lambda: S.f0_detection(TF, **kw),
+             2 * 8 * F * N + 8 * st.f0_table().size * N,
+             "TF read twice (column sums, maxima), hs written; re-reads of bins shared by "
+             "several F0s are cache traffic and not counted"),
+        case("medianFilter R=3 N=%d length=%d" % (N, length),
+             lambda: st.median_rows(rows, length),
+             lambda: [S.median_filter(r, length) for r in rows],
+             2 * 8 * 3 * N, "rows read and written once"),
+    ]
+    return {"metric": "signalTools device ms (prinComp2D)", "value": cases[0]["device_ms"],
+            "unit": "ms", "ms_per_step": cases[0]["device_ms"], "steps": steps, "warmup": warmup,
+            "dtype": "f64", "data": "synthetic, RandomState(0)",
+            "config": {"workload": "signalTools: prinComp2D, harmonicSum, medianFilter"},
+            "cases": cases,
+            "roofline": {"bound": "hbm", "achieved": cases[0]["hbm_gb_per_s"], "peak": 6290.,
+                         "unit": "GB/s", "frac": cases[0]["frac_of_measured_copy_6290"],
+                         "traffic": cases[0]["hbm_bytes"], "scope": "k_pca2d, device events"},
+            "cpu_baseline": {"value": cases[0]["cpu_restatement_ms"], "unit": "ms",
+                             "cores": _blas_threads(), "kind": "port",
+                             "sample": "tests/sigtools_ref.py at the full size, once per case "
+                                       "(cases[*].cpu_restatement_ms)"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=("simm", "nmf", "cqt", "viterbi", "wf0", "separate",
-                                           "nnls", "spatial", "hmm", "sf", "sfnmf"),
+                                           "nnls", "spatial", "hmm", "sf", "sfnmf", "sigtools"),
                     required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -541,7 +613,7 @@ def main():
     fn = {"simm": bench_simm, "nmf": bench_nmf, "cqt": bench_cqt, "viterbi": bench_viterbi,
           "wf0": bench_wf0, "separate": bench_separate, "nnls": bench_nnls,
           "spatial": bench_spatial, "hmm": bench_hmm, "sf": bench_sf,
-          "sfnmf": bench_sfnmf}[a.workload]
+          "sfnmf": bench_sfnmf, "sigtools": bench_sigtools}[a.workload]
     out = fn(a.steps, a.warmup)
     if NO_CPU:
         out["cpu_baseline"] = None   # not measured (the sample above timed nothing)
