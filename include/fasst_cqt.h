@@ -58,6 +58,30 @@ int cqt_forward(cqt_ctx *ctx, const double *x, long L, double *sp);
  * -> y [L]                                                                */
 int cqt_inverse(cqt_ctx *ctx, const double *sp, long L, double *y);
 
+/* ---- perfRast=0: the plain transform, kept as per-octave cells ----------
+ *
+ *   cqt_forward_cells    CQTransfo.computeCQT, non-raster branch  (minqt.py:495-522)
+ *                        + MinQTransfo.computeLinearPart          (minqt.py:1410-1435)
+ *   cqt_cells_to_raster  cellCQT2spCQT (+ linCellCQT2LinSpCQT)    (minqt.py:870-947, 1527-1549)
+ *   cqt_raster_to_cells  spCQT2CellCQT                            (minqt.py:949-1011, 1500-1525)
+ *   cqt_inverse_cells    invertFromCellCQT (+ invertLinearPart)   (minqt.py:1019-1055, 1469-1485)
+ *
+ * `cells` is one packed complex buffer: octave 0 .. octave_nr-1 back to back,
+ * octave i as [bins*win_nr][nframes[i]] row-major (cellCQT[i]), then, for a
+ * MinQT context, the linear cell [lin_bins][lin_frames] (cellCQT['linear']).
+ * L is the length of the transformed signal throughout.                    */
+int cqt_cell_shape(cqt_ctx *ctx, long L, int *nframes_per_octave /*[octave_nr]*/, int *lin_frames);
+/* x [L] -> cells */
+int cqt_forward_cells(cqt_ctx *ctx, const double *x, long L, double *cells);
+/* cells -> sp [freqbins][width]: columns that are multiples of 2^octave keep
+ * their complex sample, the others hold the linearly interpolated magnitude */
+int cqt_cells_to_raster(cqt_ctx *ctx, const double *cells, long L, double *sp);
+/* sp [freqbins][width] -> cells (every 2^octave-th column, zeros where the
+ * reference pads)                                                          */
+int cqt_raster_to_cells(cqt_ctx *ctx, const double *sp, long L, double *cells);
+/* cells -> y [L] */
+int cqt_inverse_cells(cqt_ctx *ctx, const double *cells, long L, double *y);
+
 /* SIMM source dictionary on this transform (generate_WF0_TR_chirped with a
  * CQT / MinQT transform, SeparateLeadStereo/separateLeadFunctions.py:742-886,
  * replacing its per-F0 computeTransform loop :829-879): for every column j the
@@ -72,8 +96,11 @@ int dict_wf0_cqt(cqt_ctx *ctx, int n_cols, const double *f1, const double *f2,
                  const int *n_partials, int max_partials, const double *amps, double fs,
                  long length_odgd, int col, double *wf0);
 /* Device time (HIP events on the context's stream) of the last cqt_forward /
- * cqt_inverse, excluding the host<->device copies of x, sp and y.         */
+ * cqt_forward_cells and of the last cqt_inverse / cqt_inverse_cells,
+ * excluding the host<->device copies of x, sp, cells and y.               */
 int cqt_device_ms(cqt_ctx *ctx, double *forward_ms, double *inverse_ms);
+/* The same for the last cqt_cells_to_raster and cqt_raster_to_cells.       */
+int cqt_raster_device_ms(cqt_ctx *ctx, double *to_raster_ms, double *to_cells_ms);
 
 #ifdef __cplusplus
 }

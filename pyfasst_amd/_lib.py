@@ -139,6 +139,12 @@ SIGNATURES = {
     "cqt_forward": (ctypes.c_int, [_vp, _dp, ctypes.c_long, _dp]),
     "cqt_inverse": (ctypes.c_int, [_vp, _dp, ctypes.c_long, _dp]),
     "cqt_device_ms": (ctypes.c_int, [_vp, _dp, _dp]),
+    "cqt_cell_shape": (ctypes.c_int, [_vp, ctypes.c_long, _ip, _ip]),
+    "cqt_forward_cells": (ctypes.c_int, [_vp, _dp, ctypes.c_long, _dp]),
+    "cqt_cells_to_raster": (ctypes.c_int, [_vp, _dp, ctypes.c_long, _dp]),
+    "cqt_raster_to_cells": (ctypes.c_int, [_vp, _dp, ctypes.c_long, _dp]),
+    "cqt_inverse_cells": (ctypes.c_int, [_vp, _dp, ctypes.c_long, _dp]),
+    "cqt_raster_device_ms": (ctypes.c_int, [_vp, _dp, _dp]),
     "dict_wf0_cqt": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, _ip, ctypes.c_int, _dp,
                                     ctypes.c_double, ctypes.c_long, ctypes.c_int, _dp]),
     # include/fasst_viterbi.h

@@ -40,6 +40,14 @@
 // LDS, then a deterministic gather overlap-add in the reference's (shift,
 // frame) summation order; upsampling through the same filtfilt kernels.
 //
+// perfRast=0 (the constructors' default, minqt.py:495-522, :870-1055): one
+// product per octave without a phase ramp, kept as per-octave cells
+// (k_cqt_band_cells); the raster is an interpolated view of the cells
+// (k_cqt_cell_raster) and folds back into them (k_cqt_raster_cell); the
+// inverse reads the cells handed in (k_icqt_frames<true>).  Cells are laid
+// out as the reference's cellCQT[i], [bins*winNr][nframes_i], packed octave
+// after octave, then the MinQT linear cell [linBins][W].
+//
 // Internal spCQT layout: frame-major [W][F] (bins contiguous, the FASST
 // engine's device layout); the C ABI hands out [F][W].
 #include "fasst_fft.h"
@@ -202,6 +210,140 @@ __global__ __launch_bounds__(256) void k_cqt_band(const BandArgs a) {
   }
 }
 
+// perfRast=0 (minqt.py:495-522): cellCQT[i] = K XX, one product per octave and
+// no phase ramp (a shift of zero would be a multiply by 1), written as the
+// reference's cell [M][nfr]: the 16 frames of a tile are 256 contiguous bytes.
+__global__ __launch_bounds__(256) void k_cqt_band_cells(const double2 *__restrict__ K,
+                                                        const double2 *__restrict__ XX, int M,
+                                                        int nb, int nbp, int nfr,
+                                                        double2 *__restrict__ cell) {
+  extern __shared__ __attribute__((aligned(16))) double2 sx[];  // [kBandFrames][nbp]
+  const int n0 = blockIdx.x * kBandFrames;
+  for (int idx = threadIdx.x; idx < kBandFrames * nb; idx += blockDim.x) {
+    const int fr = idx / nb, kk = idx - fr * nb;
+    const int n = n0 + fr;
+    sx[fr * nbp + kk] = n < nfr ? XX[(size_t)n * nbp + kk] : make_double2(0.0, 0.0);
+  }
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < M * kBandFrames; idx += blockDim.x) {
+    const int m = idx / kBandFrames, fr = idx - m * kBandFrames;
+    const int n = n0 + fr;
+    if (n >= nfr) continue;
+    const double2 *kr = K + (size_t)m * nbp;
+    const double2 *xr = sx + fr * nbp;
+    double re = 0.0, im = 0.0;
+    for (int kk = 0; kk < nb; ++kk) {
+      const double2 k = kr[kk], x = xr[kk];
+      re += k.x * x.x - k.y * x.y;
+      im += k.x * x.y + k.y * x.x;
+    }
+    cell[(size_t)m * nfr + n] = make_double2(re, im);
+  }
+}
+
+// np.abs(complex128): larger * sqrt(fma(r, r, 1)), r = smaller / larger
+// (NumPy's loop for the complex absolute value, as in fasst_sigtools.hip)
+__device__ __forceinline__ double cqt_np_cabs(double re, double im) {
+#pragma clang fp contract(off)
+  const double a = fabs(re), b = fabs(im);
+  if (isinf(a) || isinf(b)) return INFINITY;
+  if (a != a || b != b) return NAN;
+  const double l = a > b ? a : b, s = a > b ? b : a;
+  const double r = l == 0.0 ? 0.0 : s / l;
+  return sqrt(fma(r, r, 1.0)) * l;
+}
+
+struct RasterArgs {
+  const double2 *cell;  // [bins*win_nr][nfr] of this octave
+  double2 *sp;          // [F][W] row-major (the C ABI's layout)
+  int bins, win_nr, nfr, ns, row0, W;
+  long d;               // int(drop * nshifts)
+};
+
+// row nb of the octave after the scatter (minqt.py:901-910) and the drop
+// alignment (:911-914), column c.  The scatter fills column j*ns with
+// sub-window j % winNr of frame j / winNr; the alignment row[:W-d] = row[d:]
+// leaves the last d columns at their own pre-alignment values.  With one
+// atom per frame (:915-926) the reference offsets the scatter by the drop
+// instead, so those last columns stay zero.
+__device__ __forceinline__ double2 raster_at(const RasterArgs &a, int nb, long c) {
+  if (a.win_nr == 1 || c + a.d < a.W) c += a.d;
+  const long j = c / a.ns;
+  if (j * a.ns != c || j >= (long)a.nfr * a.win_nr) return make_double2(0.0, 0.0);
+  const long n = j / a.win_nr, at = j - n * a.win_nr;
+  return a.cell[((size_t)nb * a.win_nr + at) * a.nfr + n];
+}
+
+// cellCQT2spCQT for one octave (minqt.py:888-945), one thread per (row, col),
+// lanes along col.  Columns that are multiples of ns = 2^noct keep their
+// complex sample; the others get the linear interpolation of the magnitudes
+// of their two neighbours, in the operation order of
+// scipy.interpolate.interp1d(kind='linear') on a float64 1-D y, which is
+// numpy.interp's:  slope = (y_hi - y_lo) / (x_hi - x_lo);
+//                  y = slope * (x - x_lo) + y_lo
+// (two roundings in the last line: no FMA), and fill_value = 0 past the last
+// multiple of ns.  A pure gather of at most two cell values.
+__global__ __launch_bounds__(256) void k_cqt_cell_raster(const RasterArgs a) {
+#pragma clang fp contract(off)
+  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int nb = blockIdx.y;
+  if (c >= a.W) return;
+  double2 *o = a.sp + (size_t)(a.row0 + nb) * a.W + c;
+  const long c0 = c / a.ns * a.ns;
+  if (c0 == c) {
+    *o = raster_at(a, nb, c);
+    return;
+  }
+  const long c1 = c0 + a.ns;
+  if (c1 >= a.W) {
+    *o = make_double2(0.0, 0.0);
+    return;
+  }
+  const double2 lo = raster_at(a, nb, c0), hi = raster_at(a, nb, c1);
+  const double ylo = cqt_np_cabs(lo.x, lo.y), yhi = cqt_np_cabs(hi.x, hi.y);
+  const double slope = (yhi - ylo) / (double)(c1 - c0);
+  const double t = slope * (double)(c - c0);
+  *o = make_double2(t + ylo, 0.0);
+}
+
+// linCellCQT2LinSpCQT (minqt.py:1534-1549): sp[row0 + r][:W - drop] =
+// lin[r][drop:], the last drop columns zero
+__global__ __launch_bounds__(256) void k_cqt_lin_raster(const double2 *__restrict__ lin, int W,
+                                                        long drop, int row0,
+                                                        double2 *__restrict__ sp) {
+  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= W) return;
+  const size_t r = blockIdx.y;
+  sp[(r + row0) * W + c] = c + drop < W ? lin[r * W + c + drop] : make_double2(0.0, 0.0);
+}
+
+// spCQT2CellCQT for one octave (minqt.py:966-1011), one thread per cell
+// element (m, n), lanes along n: element j = n*winNr + a of the row
+// [zeros(dropped), sp[row, ::2^noct], zero padding]
+__global__ __launch_bounds__(256) void k_cqt_raster_cell(const double2 *__restrict__ sp, int W,
+                                                         int row0, int win_nr, int nfr, int step,
+                                                         long dropped, double2 *__restrict__ cell) {
+  const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= nfr) return;
+  const int m = blockIdx.y;
+  const int nbin = m / win_nr, at = m - nbin * win_nr;
+  const long q = n * win_nr + at - dropped;
+  double2 v = make_double2(0.0, 0.0);
+  if (q >= 0 && q * step < W) v = sp[(size_t)(row0 + nbin) * W + q * step];
+  cell[(size_t)m * nfr + n] = v;
+}
+
+// MinQTransfo.spCQT2CellCQT linear rows (minqt.py:1508-1525):
+// lin[r][n] = [zeros(dropped), sp[row0 + r]][n], n < W
+__global__ __launch_bounds__(256) void k_cqt_raster_lin(const double2 *__restrict__ sp, int W,
+                                                        int row0, long dropped,
+                                                        double2 *__restrict__ lin) {
+  const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= W) return;
+  const size_t r = blockIdx.y;
+  lin[r * W + n] = n >= dropped ? sp[(r + row0) * W + n - dropped] : make_double2(0.0, 0.0);
+}
+
 // MinQT linear part (minqt.py:1420-1435 with stft.py:3-69): frame n of the
 // STFT of xpad[first_center:] (half-window zero prefix), bins kmax..N/2 to
 // the linear rows of spCQT column n - drop, for n in [drop, W).
@@ -237,6 +379,7 @@ __global__ __launch_bounds__(256) void k_cqt_transpose(const double2 *__restrict
 
 struct ICellArgs {
   const double2 *sp;   // [W][F]
+  const double2 *cells;  // [M][nfr] of this octave (k_icqt_frames<true>), else unused
   const double2 *S;    // [nb][M]: sparKernel rows kb..ke-1
   double *frames;      // [nfr][N]
   const double2 *tw;   // inverse twiddles
@@ -258,13 +401,17 @@ __device__ __forceinline__ double2 cell_at(const ICellArgs &a, int m, int n) {
   return a.sp[(size_t)c * a.F + a.row0 + nbin];
 }
 
-// frame n: 2 Re(ifft(sparKernel . cell[:, n])) / ns   (minqt.py:829-839, :1028-1041)
+// frame n: 2 Re(ifft(sparKernel . cell[:, n])) / ns   (minqt.py:829-839, :1028-1041);
+// kGiven: the cell column is read from the cells handed in (perfRast=0)
+// instead of being derived from the raster
+template <bool kGiven>
 __global__ __launch_bounds__(256) void k_icqt_frames(const ICellArgs a) {
   extern __shared__ __attribute__((aligned(16))) double2 buf[];  // [N] + [M] cell column
   double2 *cell = buf + a.N;
   const int n = blockIdx.x;
   for (int i = threadIdx.x; i < a.N; i += blockDim.x) buf[i] = make_double2(0.0, 0.0);
-  for (int m = threadIdx.x; m < a.M; m += blockDim.x) cell[m] = cell_at(a, m, n);
+  for (int m = threadIdx.x; m < a.M; m += blockDim.x)
+    cell[m] = kGiven ? a.cells[(size_t)m * a.nfr + n] : cell_at(a, m, n);
   __syncthreads();
   for (int kk = threadIdx.x; kk < a.nb; kk += blockDim.x) {
     const double2 *sr = a.S + (size_t)kk * a.M;
@@ -402,10 +549,14 @@ struct cqt_ctx {
   long cap_L = -1;
   DBuf<double> xp, sa, sb, y1, frames, yb, yc;
   DBuf<double2> XX, sp, sph;
+  // perfRast=0: the packed per-octave cells (+ linear cell), allocated by the
+  // first cell call only
+  long cap_cells = -1;
+  DBuf<double2> cells;
   // device time of the last forward / inverse (HIP events on the ctx stream,
   // after the host->device copy and before the device->host copy)
   hipEvent_t ev[4] = {};
-  float ms_fwd = 0.f, ms_inv = 0.f;
+  float ms_fwd = 0.f, ms_inv = 0.f, ms_rast = 0.f, ms_cell = 0.f;
 };
 
 namespace {
@@ -558,6 +709,137 @@ int forward_dev(cqt_ctx *c, const Geo &g, hipStream_t s) {
   return FASST_OK;
 }
 
+// offset of octave noct's cell (noct == oct: the linear cell) in the packed cells
+size_t cell_offset(const cqt_ctx *c, const Geo &g, int noct) {
+  size_t off = 0;
+  for (int i = 0; i < noct; ++i) off += (size_t)c->M * g.nfr[i];
+  return off;
+}
+
+size_t cells_total(const cqt_ctx *c, const Geo &g) {
+  return cell_offset(c, g, c->oct) + (c->lin_N ? (size_t)c->lin_bins * g.W : 0);
+}
+
+int ensure_cells(cqt_ctx *c, const Geo &g, long L) {
+  if (c->cap_cells == L) return FASST_OK;
+  int st = c->cells.alloc(cells_total(c, g));
+  if (st) return st;
+  c->cap_cells = L;
+  return FASST_OK;
+}
+
+// The inverse on the device, result at *yout_p (L samples).  cells == nullptr:
+// from the raster in c->sp (MinQT: invertFromSpCQTRast; CQT: invertFromCellCQT
+// on the cells spCQT2CellCQT derives).  cells given (perfRast=0): invertFromCellCQT
+// on them (minqt.py:1019-1055), then invertLinearPart on the linear cell.
+int inverse_dev(cqt_ctx *c, const Geo &g, long L, const double2 *cells, hipStream_t s,
+                double **yout_p) {
+  int st;
+  const bool rast = !cells && c->lin_N != 0;
+  const double empty_hops = (double)c->first_center / (double)c->atom_hop;
+  long ysize = (long)std::ceil((double)L / std::ldexp(1.0, c->oct - 1));
+  const long ycap = (long)c->yb.n;
+  double *ycur = c->yb.p, *yalt = c->yc.p;
+  FASST_HIP(hipMemsetAsync(ycur, 0, ycap * sizeof(double), s));
+  for (int noct = c->oct - 1; noct >= 0; --noct) {
+    const long step = 1L << noct;
+    const int ns = rast ? (int)step : 1;
+    const double inc = (double)c->atom_hop / std::ldexp(1.0, noct);
+    const long dropped = (long)(empty_hops * (std::ldexp(1.0, c->oct - noct - 1) - 1.0));
+    const long ncolx = (g.W + step - 1) / step;
+    const long ncell = (dropped + ncolx + c->win_nr - 1) / c->win_nr;
+    int nfr = g.nfr[noct];
+    const size_t cell_off = cells ? cell_offset(c, g, noct) : 0;
+    if (!cells && ncell < nfr) {
+      if (rast) {
+        set_error("octave %d: %ld cells < %d frames", noct, ncell, nfr);
+        return FASST_ERR_SHAPE;
+      }
+      nfr = (int)ncell;
+    }
+    const double ylen = (double)c->fft_hop * (nfr - 1) + c->N + (rast ? ns * inc : 0.0);
+    if (ylen > (double)ysize) ysize += (long)(ylen - (double)ysize);
+    if (ysize > ycap) {
+      set_error("inverse CQT buffer overflow (%ld > %ld)", ysize, ycap);
+      return FASST_ERR_SHAPE;
+    }
+    for (int sh = 0; sh < ns; ++sh) {
+      ICellArgs a;
+      a.sp = c->sp.p;
+      a.cells = cells ? cells + cell_off : nullptr;
+      a.S = c->S.p;
+      a.frames = c->frames.p;
+      a.tw = c->tw_i.p;
+      a.N = c->N;
+      a.logN = c->logN;
+      a.kb = c->kb;
+      a.nb = c->nb;
+      a.M = c->M;
+      a.F = g.F;
+      a.W = g.W;
+      a.win_nr = c->win_nr;
+      a.row0 = c->bins * (c->oct - noct - 1);
+      a.step = (int)step;
+      a.shift = sh;
+      a.nfr = nfr;
+      a.dropped = dropped;
+      a.ncolx = ncolx;
+      a.ns = (double)ns;
+      if (cells)
+        k_icqt_frames<true><<<nfr, 256, ((size_t)c->N + c->M) * sizeof(double2), s>>>(a);
+      else
+        k_icqt_frames<false><<<nfr, 256, ((size_t)c->N + c->M) * sizeof(double2), s>>>(a);
+      FASST_LAUNCH_CHECK();
+      k_icqt_ola<<<(int)((ysize + 255) / 256), 256, 0, s>>>(c->frames.p, nfr, c->N, c->fft_hop,
+                                                            rast ? sh * inc : 0.0, ycur, ysize);
+      FASST_LAUNCH_CHECK();
+    }
+    if (noct != 0) {
+      if (2 * ysize > ycap) {
+        set_error("inverse CQT buffer overflow (%ld > %ld)", 2 * ysize, ycap);
+        return FASST_ERR_SHAPE;
+      }
+      FASST_HIP(hipMemsetAsync(yalt, 0, ycap * sizeof(double), s));
+      if ((st = filtfilt(c, ycur, 2 * ysize, 1, yalt, 0, 2.0))) return st;
+      std::swap(ycur, yalt);
+      ysize *= 2;
+    }
+  }
+  if (ysize < g.maxBlock + L) {
+    set_error("inverse CQT: %ld samples < prefix %ld + %ld", ysize, g.maxBlock, L);
+    return FASST_ERR_SHAPE;
+  }
+  double *yout = ycur + g.maxBlock;   // y[prefixZeros:][:datalen_init]
+  *yout_p = yout;
+  if (c->lin_N) {                     // + invertLinearPart (minqt.py:1469-1485)
+    long dropped0 = (long)(empty_hops * (std::ldexp(1.0, c->oct - 1) - 1.0));
+    const double2 *lsp = c->sp.p;
+    int lF = g.F, lrow0 = c->bins * c->oct;
+    if (cells) {   // cellCQT['linear'] [linBins][W] -> frame-major scratch, nothing dropped
+      k_cqt_transpose<<<dim3((g.W + 15) / 16, (c->lin_bins + 15) / 16), 256, 0, s>>>(
+          cells + cell_offset(c, g, c->oct), c->sp.p, c->lin_bins, g.W);
+      FASST_LAUNCH_CHECK();
+      dropped0 = 0;
+      lF = c->lin_bins;
+      lrow0 = 0;
+    }
+    const long len_lin = (long)c->atom_hop * (g.W - 1) + c->lin_N - c->lin_N / 2;
+    const long off = g.maxBlock - c->first_center;
+    if (off < 0 || off + L > len_lin) {
+      set_error("linear inverse: %ld samples < %ld", len_lin, off + L);
+      return FASST_ERR_SHAPE;
+    }
+    k_icqt_lin_frames<<<g.W, 256, c->lin_N * sizeof(double2), s>>>(
+        lsp, lF, lrow0, c->kmax, dropped0, c->lwin.p, c->ltw_i.p, c->lin_N,
+        c->lin_logN, c->frames.p);
+    FASST_LAUNCH_CHECK();
+    k_icqt_lin_ola<<<(int)((L + 255) / 256), 256, 0, s>>>(c->frames.p, g.W, c->lin_N, c->atom_hop,
+                                                          c->lwin.p, off + c->lin_N / 2, yout, L);
+    FASST_LAUNCH_CHECK();
+  }
+  return FASST_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -695,8 +977,13 @@ int cqt_create(int device, int bins, int octave_nr, int win_nr, int fft_len, int
   }
   const int big = std::max(fft_len, lin_ft_len);
   if ((st = set_smem((const void *)k_cqt_frames, (size_t)fft_len * sizeof(double2))) ||
-      (st = set_smem((const void *)k_icqt_frames, ((size_t)fft_len + M) * sizeof(double2))) ||
+      (st = set_smem((const void *)k_icqt_frames<false>,
+                     ((size_t)fft_len + M) * sizeof(double2))) ||
+      (st = set_smem((const void *)k_icqt_frames<true>,
+                     ((size_t)fft_len + M) * sizeof(double2))) ||
       (st = set_smem((const void *)k_cqt_band, (size_t)kBandFrames * c->nbp * sizeof(double2))) ||
+      (st = set_smem((const void *)k_cqt_band_cells,
+                     (size_t)kBandFrames * c->nbp * sizeof(double2))) ||
       (lin_ft_len &&
        ((st = set_smem((const void *)k_cqt_linear, (size_t)lin_ft_len * sizeof(double2))) ||
         (st = set_smem((const void *)k_icqt_lin_frames, (size_t)lin_ft_len * sizeof(double2))))))
@@ -764,102 +1051,181 @@ int cqt_inverse(cqt_ctx *c, const double *sp, long L, double *y) {
   DeviceGuard dg(c->device);
   if ((st = ensure_work(c, g, L))) return st;
   hipStream_t s = c->stream;
-  const bool rast = c->lin_N != 0;   // MinQT: invertFromSpCQTRast; CQT: invertFromCellCQT
   FASST_HIP(hipMemcpyAsync(c->sph.p, sp, (size_t)g.W * g.F * sizeof(double2),
                            hipMemcpyHostToDevice, s));
   FASST_HIP(hipEventRecord(c->ev[2], s));
   k_cqt_transpose<<<dim3((g.W + 15) / 16, (g.F + 15) / 16), 256, 0, s>>>(c->sph.p, c->sp.p, g.F,
                                                                           g.W);
   FASST_LAUNCH_CHECK();
-  const double empty_hops = (double)c->first_center / (double)c->atom_hop;
-  long ysize = (long)std::ceil((double)L / std::ldexp(1.0, c->oct - 1));
-  const long ycap = (long)c->yb.n;
-  double *ycur = c->yb.p, *yalt = c->yc.p;
-  FASST_HIP(hipMemsetAsync(ycur, 0, ycap * sizeof(double), s));
-  for (int noct = c->oct - 1; noct >= 0; --noct) {
-    const long step = 1L << noct;
-    const int ns = rast ? (int)step : 1;
-    const double inc = (double)c->atom_hop / std::ldexp(1.0, noct);
-    const long dropped = (long)(empty_hops * (std::ldexp(1.0, c->oct - noct - 1) - 1.0));
-    const long ncolx = (g.W + step - 1) / step;
-    const long ncell = (dropped + ncolx + c->win_nr - 1) / c->win_nr;
-    int nfr = g.nfr[noct];
-    if (ncell < nfr) {
-      if (rast) {
-        set_error("octave %d: %ld cells < %d frames", noct, ncell, nfr);
-        return FASST_ERR_SHAPE;
-      }
-      nfr = (int)ncell;
-    }
-    const double ylen = (double)c->fft_hop * (nfr - 1) + c->N + (rast ? ns * inc : 0.0);
-    if (ylen > (double)ysize) ysize += (long)(ylen - (double)ysize);
-    if (ysize > ycap) {
-      set_error("inverse CQT buffer overflow (%ld > %ld)", ysize, ycap);
-      return FASST_ERR_SHAPE;
-    }
-    for (int sh = 0; sh < ns; ++sh) {
-      ICellArgs a;
-      a.sp = c->sp.p;
-      a.S = c->S.p;
-      a.frames = c->frames.p;
-      a.tw = c->tw_i.p;
-      a.N = c->N;
-      a.logN = c->logN;
-      a.kb = c->kb;
-      a.nb = c->nb;
-      a.M = c->M;
-      a.F = g.F;
-      a.W = g.W;
-      a.win_nr = c->win_nr;
-      a.row0 = c->bins * (c->oct - noct - 1);
-      a.step = (int)step;
-      a.shift = sh;
-      a.nfr = nfr;
-      a.dropped = dropped;
-      a.ncolx = ncolx;
-      a.ns = (double)ns;
-      k_icqt_frames<<<nfr, 256, ((size_t)c->N + c->M) * sizeof(double2), s>>>(a);
-      FASST_LAUNCH_CHECK();
-      k_icqt_ola<<<(int)((ysize + 255) / 256), 256, 0, s>>>(c->frames.p, nfr, c->N, c->fft_hop,
-                                                            rast ? sh * inc : 0.0, ycur, ysize);
-      FASST_LAUNCH_CHECK();
-    }
-    if (noct != 0) {
-      if (2 * ysize > ycap) {
-        set_error("inverse CQT buffer overflow (%ld > %ld)", 2 * ysize, ycap);
-        return FASST_ERR_SHAPE;
-      }
-      FASST_HIP(hipMemsetAsync(yalt, 0, ycap * sizeof(double), s));
-      if ((st = filtfilt(c, ycur, 2 * ysize, 1, yalt, 0, 2.0))) return st;
-      std::swap(ycur, yalt);
-      ysize *= 2;
-    }
-  }
-  if (ysize < g.maxBlock + L) {
-    set_error("inverse CQT: %ld samples < prefix %ld + %ld", ysize, g.maxBlock, L);
-    return FASST_ERR_SHAPE;
-  }
-  double *yout = ycur + g.maxBlock;   // y[prefixZeros:][:datalen_init]
-  if (c->lin_N) {                     // + invertLinearPart (minqt.py:1469-1485)
-    const long dropped0 = (long)(empty_hops * (std::ldexp(1.0, c->oct - 1) - 1.0));
-    const long len_lin = (long)c->atom_hop * (g.W - 1) + c->lin_N - c->lin_N / 2;
-    const long off = g.maxBlock - c->first_center;
-    if (off < 0 || off + L > len_lin) {
-      set_error("linear inverse: %ld samples < %ld", len_lin, off + L);
-      return FASST_ERR_SHAPE;
-    }
-    k_icqt_lin_frames<<<g.W, 256, c->lin_N * sizeof(double2), s>>>(
-        c->sp.p, g.F, c->bins * c->oct, c->kmax, dropped0, c->lwin.p, c->ltw_i.p, c->lin_N,
-        c->lin_logN, c->frames.p);
-    FASST_LAUNCH_CHECK();
-    k_icqt_lin_ola<<<(int)((L + 255) / 256), 256, 0, s>>>(c->frames.p, g.W, c->lin_N, c->atom_hop,
-                                                          c->lwin.p, off + c->lin_N / 2, yout, L);
-    FASST_LAUNCH_CHECK();
-  }
+  double *yout = nullptr;
+  if ((st = inverse_dev(c, g, L, nullptr, s, &yout))) return st;
   FASST_HIP(hipEventRecord(c->ev[3], s));
   FASST_HIP(hipMemcpyAsync(y, yout, L * sizeof(double), hipMemcpyDeviceToHost, s));
   FASST_HIP(hipStreamSynchronize(s));
   FASST_HIP(hipEventElapsedTime(&c->ms_inv, c->ev[2], c->ev[3]));
+  return FASST_OK;
+}
+int cqt_cell_shape(cqt_ctx *c, long L, int *nframes, int *lin_frames) {
+  if (!c) return FASST_ERR_SHAPE;
+  Geo g;
+  int st = geometry(c, L, g);
+  if (st) return st;
+  if (nframes)
+    for (int i = 0; i < c->oct; ++i) nframes[i] = g.nfr[i];
+  if (lin_frames) *lin_frames = c->lin_N ? g.W : 0;
+  return FASST_OK;
+}
+
+int cqt_forward_cells(cqt_ctx *c, const double *x, long L, double *cells) {
+  if (!c || !x || !cells) return FASST_ERR_SHAPE;
+  Geo g;
+  int st = geometry(c, L, g);
+  if (st) return st;
+  DeviceGuard dg(c->device);
+  if ((st = ensure_work(c, g, L)) || (st = ensure_cells(c, g, L))) return st;
+  hipStream_t s = c->stream;
+  FASST_HIP(hipMemsetAsync(c->xp.p, 0, g.Lp * sizeof(double), s));
+  FASST_HIP(hipMemcpyAsync(c->xp.p + g.maxBlock, x, L * sizeof(double), hipMemcpyHostToDevice, s));
+  FASST_HIP(hipEventRecord(c->ev[0], s));
+  if (c->lin_N) {   // cellCQT['linear'] = stft(xpad[first_center:])[Kmax:, :W]  (minqt.py:1420-1435)
+    const long off = (long)c->first_center - c->lin_N / 2;
+    k_cqt_linear<<<g.W, 256, c->lin_N * sizeof(double2), s>>>(
+        c->xp.p, g.Lp, off, c->lwin.p, c->ltw_f.p, c->lin_N, c->lin_logN, c->atom_hop, 0, c->kmax,
+        0, c->lin_bins, c->sp.p);
+    FASST_LAUNCH_CHECK();
+    k_cqt_transpose<<<dim3((c->lin_bins + 15) / 16, (g.W + 15) / 16), 256, 0, s>>>(
+        c->sp.p, c->cells.p + cell_offset(c, g, c->oct), g.W, c->lin_bins);
+    FASST_LAUNCH_CHECK();
+  }
+  const double *cur = c->xp.p;
+  double *next = c->sa.p;
+  for (int i = 0; i < c->oct; ++i) {
+    const int nfr = g.nfr[i];
+    double2 *cell = c->cells.p + cell_offset(c, g, i);
+    if (c->nb > 0) {
+      k_cqt_frames<<<nfr, 256, c->N * sizeof(double2), s>>>(cur, g.len[i], c->fft_hop, c->tw_f.p,
+                                                           c->N, c->logN, c->kb, c->nb, c->nbp,
+                                                           c->XX.p);
+      FASST_LAUNCH_CHECK();
+      k_cqt_band_cells<<<(nfr + kBandFrames - 1) / kBandFrames, 256,
+                         kBandFrames * c->nbp * sizeof(double2), s>>>(c->K.p, c->XX.p, c->M, c->nb,
+                                                                      c->nbp, nfr, cell);
+      FASST_LAUNCH_CHECK();
+    } else {
+      FASST_HIP(hipMemsetAsync(cell, 0, (size_t)c->M * nfr * sizeof(double2), s));
+    }
+    // The reference's guard `i != self.octaveNr` (minqt.py:520) is always true,
+    // so it also filters and decimates after the last octave; nothing reads
+    // that signal, and it is not computed here.
+    if (i != c->oct - 1) {
+      if ((st = filtfilt(c, cur, g.len[i], 0, next, 1, 1.0))) return st;
+      cur = next;
+      next = (next == c->sa.p) ? c->sb.p : c->sa.p;
+    }
+  }
+  FASST_HIP(hipEventRecord(c->ev[1], s));
+  FASST_HIP(hipMemcpyAsync(cells, c->cells.p, cells_total(c, g) * sizeof(double2),
+                           hipMemcpyDeviceToHost, s));
+  FASST_HIP(hipStreamSynchronize(s));
+  FASST_HIP(hipEventElapsedTime(&c->ms_fwd, c->ev[0], c->ev[1]));
+  return FASST_OK;
+}
+
+int cqt_cells_to_raster(cqt_ctx *c, const double *cells, long L, double *sp) {
+  if (!c || !cells || !sp) return FASST_ERR_SHAPE;
+  Geo g;
+  int st = geometry(c, L, g);
+  if (st) return st;
+  DeviceGuard dg(c->device);
+  if ((st = ensure_work(c, g, L)) || (st = ensure_cells(c, g, L))) return st;
+  hipStream_t s = c->stream;
+  FASST_HIP(hipMemcpyAsync(c->cells.p, cells, cells_total(c, g) * sizeof(double2),
+                           hipMemcpyHostToDevice, s));
+  FASST_HIP(hipEventRecord(c->ev[0], s));
+  const int gx = (g.W + 255) / 256;
+  for (int i = 0; i < c->oct; ++i) {   // every element of sp is written: no memset
+    RasterArgs a;
+    a.cell = c->cells.p + cell_offset(c, g, i);
+    a.sp = c->sph.p;
+    a.bins = c->bins;
+    a.win_nr = c->win_nr;
+    a.nfr = g.nfr[i];
+    a.ns = 1 << i;
+    a.row0 = c->bins * (c->oct - i - 1);
+    a.W = g.W;
+    a.d = g.d[i];
+    k_cqt_cell_raster<<<dim3(gx, c->bins), 256, 0, s>>>(a);
+    FASST_LAUNCH_CHECK();
+  }
+  if (c->lin_N) {
+    k_cqt_lin_raster<<<dim3(gx, c->lin_bins), 256, 0, s>>>(
+        c->cells.p + cell_offset(c, g, c->oct), g.W, g.drop0, c->bins * c->oct, c->sph.p);
+    FASST_LAUNCH_CHECK();
+  }
+  FASST_HIP(hipEventRecord(c->ev[1], s));
+  FASST_HIP(hipMemcpyAsync(sp, c->sph.p, (size_t)g.W * g.F * sizeof(double2),
+                           hipMemcpyDeviceToHost, s));
+  FASST_HIP(hipStreamSynchronize(s));
+  FASST_HIP(hipEventElapsedTime(&c->ms_rast, c->ev[0], c->ev[1]));
+  return FASST_OK;
+}
+
+int cqt_raster_to_cells(cqt_ctx *c, const double *sp, long L, double *cells) {
+  if (!c || !sp || !cells) return FASST_ERR_SHAPE;
+  Geo g;
+  int st = geometry(c, L, g);
+  if (st) return st;
+  DeviceGuard dg(c->device);
+  if ((st = ensure_work(c, g, L)) || (st = ensure_cells(c, g, L))) return st;
+  hipStream_t s = c->stream;
+  FASST_HIP(hipMemcpyAsync(c->sph.p, sp, (size_t)g.W * g.F * sizeof(double2),
+                           hipMemcpyHostToDevice, s));
+  FASST_HIP(hipEventRecord(c->ev[2], s));
+  const double empty_hops = (double)c->first_center / (double)c->atom_hop;
+  for (int i = 0; i < c->oct; ++i) {
+    const long dropped = (long)(empty_hops * (std::ldexp(1.0, c->oct - i - 1) - 1.0));
+    k_cqt_raster_cell<<<dim3((g.nfr[i] + 255) / 256, c->M), 256, 0, s>>>(
+        c->sph.p, g.W, c->bins * (c->oct - i - 1), c->win_nr, g.nfr[i], 1 << i, dropped,
+        c->cells.p + cell_offset(c, g, i));
+    FASST_LAUNCH_CHECK();
+  }
+  if (c->lin_N) {
+    k_cqt_raster_lin<<<dim3((g.W + 255) / 256, c->lin_bins), 256, 0, s>>>(
+        c->sph.p, g.W, c->bins * c->oct, g.drop0, c->cells.p + cell_offset(c, g, c->oct));
+    FASST_LAUNCH_CHECK();
+  }
+  FASST_HIP(hipEventRecord(c->ev[3], s));
+  FASST_HIP(hipMemcpyAsync(cells, c->cells.p, cells_total(c, g) * sizeof(double2),
+                           hipMemcpyDeviceToHost, s));
+  FASST_HIP(hipStreamSynchronize(s));
+  FASST_HIP(hipEventElapsedTime(&c->ms_cell, c->ev[2], c->ev[3]));
+  return FASST_OK;
+}
+
+int cqt_inverse_cells(cqt_ctx *c, const double *cells, long L, double *y) {
+  if (!c || !cells || !y) return FASST_ERR_SHAPE;
+  Geo g;
+  int st = geometry(c, L, g);
+  if (st) return st;
+  DeviceGuard dg(c->device);
+  if ((st = ensure_work(c, g, L)) || (st = ensure_cells(c, g, L))) return st;
+  hipStream_t s = c->stream;
+  FASST_HIP(hipMemcpyAsync(c->cells.p, cells, cells_total(c, g) * sizeof(double2),
+                           hipMemcpyHostToDevice, s));
+  FASST_HIP(hipEventRecord(c->ev[2], s));
+  double *yout = nullptr;
+  if ((st = inverse_dev(c, g, L, c->cells.p, s, &yout))) return st;
+  FASST_HIP(hipEventRecord(c->ev[3], s));
+  FASST_HIP(hipMemcpyAsync(y, yout, L * sizeof(double), hipMemcpyDeviceToHost, s));
+  FASST_HIP(hipStreamSynchronize(s));
+  FASST_HIP(hipEventElapsedTime(&c->ms_inv, c->ev[2], c->ev[3]));
+  return FASST_OK;
+}
+
+int cqt_raster_device_ms(cqt_ctx *c, double *to_raster_ms, double *to_cells_ms) {
+  if (!c) return FASST_ERR_SHAPE;
+  if (to_raster_ms) *to_raster_ms = c->ms_rast;
+  if (to_cells_ms) *to_cells_ms = c->ms_cell;
   return FASST_OK;
 }
 

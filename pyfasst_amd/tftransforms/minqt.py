@@ -2,21 +2,33 @@
 
 Same classes, constructor arguments and attributes as the reference:
 `CQTKernel` (minqt.py:31-233), `MinQTKernel` (:309-335), `CQTransfo`
-(:402-1070) and `MinQTransfo` (:1369-1550).  FASST builds them with
-perfRast=1 (audioModel.py:206-214); that rasterised transform and its
-inverse run on the GPU (pyfasst_amd/csrc/fasst_cqt.hip, C ABI
-include/fasst_cqt.h).
+(:402-1070) and `MinQTransfo` (:1369-1550).  Both modes run on the GPU
+(pyfasst_amd/csrc/fasst_cqt.hip, C ABI include/fasst_cqt.h):
+
+perfRast=1, which FASST builds (audioModel.py:206-214): the rasterised
+transform; `_spCQT` is the primary state and `cellCQT` a re-indexing view of
+it (spCQT2CellCQT, :949-1011), derived when asked for.
+
+perfRast=0, the constructors' default: the plain Schoerkhuber-Klapuri
+transform.  `cellCQT` ({0..octaveNr-1: [bins*winNr, nframes_i], 'linear':
+[linBins, nframes_0*winNr]}, host arrays) is the primary state, as in the
+reference: computeTransform fills it and leaves no `_spCQT`; the `spCQT` /
+`transfo` getters build the interpolated raster from the cells on first use
+(cellCQT2spCQT, :870-947); assigning `transfo` / `spCQT` stores the matrix and
+re-derives the cells at once (:648-658, :731-735); `del transfo` removes both
+(:665-669), so a getter after it raises AttributeError, while `del t._spCQT`
+alone makes the next getter rebuild the raster; invertTransform inverts
+`cellCQT` (invertFromCellCQT, :1013-1055, plus invertLinearPart, :1452-1485).
+The cells are packed into one buffer for each device call, so arrays the
+caller replaced or edited in `cellCQT` are what the device sees.
 
 Host side (setup constants only, as the reference designs them): the
 one-octave spectral kernel (a few hundred FFTs of single atoms, thresholded
 at `thresh` -- computed with NumPy so that the thresholding and the
 normalisation weight are the reference's to the bit) and the anti-aliasing
-Butterworth filter (scipy.signal.butter / lfilter_zi).  `cellCQT` is a pure
-re-indexing view of spCQT (spCQT2CellCQT, :949-1011).
+Butterworth filter (scipy.signal.butter / lfilter_zi).
 
-Not on the GPU path: perfRast=0 (its spCQT is an interpolated view of
-per-octave cells, :870-947; no FASST configuration builds it) raises
-NotImplementedError.  Deliberate deviation: `lowPassCoeffs=(B, A)` is used
+Deliberate deviation: `lowPassCoeffs=(B, A)` is used
 as the anti-aliasing filter (the reference accepts the argument but then
 never defines B, A and fails at the first octave).
 """
@@ -130,7 +142,7 @@ class MinQTKernel(CQTKernel):
 
 
 class CQTransfo(object):
-    """Constant-Q transform (minqt.py:402-1070); perfRast=1 runs on the GPU."""
+    """Constant-Q transform (minqt.py:402-1070), on the GPU in both modes."""
     transformname = 'cqt'
 
     def __init__(self, fmin, fmax, bins, fs, q=1, atomHopFactor=0.25, thresh=0.0005,
@@ -173,9 +185,6 @@ class CQTransfo(object):
     def _context(self):
         if self._h is not None:
             return self._h
-        if not self.perfRast:
-            raise NotImplementedError("perfRast=0 (interpolated cell raster) is outside the "
-                                      "GPU path; FASST builds perfRast=1 transforms")
         k = self.cqtkernel
         B = np.ascontiguousarray(self.B, dtype=np.float64)
         A = np.ascontiguousarray(self.A, dtype=np.float64)
@@ -216,11 +225,14 @@ class CQTransfo(object):
         return self.computeCQT(data)
 
     def computeCQT(self, data):
-        """Rasterised CQT of data on the GPU (minqt.py:471-646)."""
+        """CQT of data on the GPU (minqt.py:471-646): the raster with
+        perfRast=1, the per-octave cells with perfRast=0."""
         if hasattr(self, '_spCQT'):
             del self._spCQT
         if hasattr(self, 'cellCQT'):
             del self.cellCQT
+        if not self.perfRast:
+            return self._compute_cells(data)
         x = np.ascontiguousarray(np.asarray(data, dtype=np.float64).ravel())
         k = self.cqtkernel
         self.datalen_init = x.shape[0]
@@ -233,11 +245,101 @@ class CQTransfo(object):
         check(lib.cqt_forward(self._context(), dptr(x), x.size, dptr(sp)), "cqt_forward")
         self._spCQT = sp
 
+    # ------------------------------------------------------ perfRast=0 cells
+    def _cell_layout(self):
+        """Shapes of the packed cells of a signal of datalen_init samples."""
+        k = self.cqtkernel
+        nfr = np.zeros(int(self.octaveNr), dtype=np.int32)
+        lin = ctypes.c_int(0)
+        check(lib.cqt_cell_shape(self._context(), int(self.datalen_init), _lib.iptr(nfr),
+                                 ctypes.byref(lin)), "cqt_cell_shape")
+        M = int(k.bins * k.winNr)
+        shapes = [(noct, (M, int(n))) for noct, n in enumerate(nfr)]
+        if lin.value:
+            shapes.append(('linear', (int(k.linBins), lin.value)))
+        return nfr, shapes
+
+    def _unpack_cells(self, buf, shapes):
+        cells, off = {}, 0
+        for key, shp in shapes:
+            n = shp[0] * shp[1]
+            cells[key] = buf[off:off + n].reshape(shp)
+            off += n
+        return cells
+
+    def _pack_cells(self):
+        """self.cellCQT as the one buffer the device calls take."""
+        _, shapes = self._cell_layout()
+        parts = []
+        for key, shp in shapes:
+            c = np.asarray(self.cellCQT[key])
+            if c.shape != shp:
+                raise ValueError("cellCQT[%r] has shape %s instead of %s" % (key, c.shape, shp))
+            parts.append(np.asarray(c, dtype=np.complex128).ravel())
+        return np.ascontiguousarray(np.concatenate(parts)), shapes
+
+    def _compute_cells(self, data):
+        """computeCQT, non-raster branch (minqt.py:495-522), and for MinQT the
+        linear cell of computeLinearPart (:1410-1435), in one GPU pass."""
+        x = np.ascontiguousarray(np.asarray(data, dtype=np.float64).ravel())
+        k = self.cqtkernel
+        self.datalen_init = x.shape[0]
+        self.maxBlock = int(k.FFTLen * (2 ** (self.octaveNr - 1)))
+        self.suffixZeros = self.maxBlock
+        self.prefixZeros = self.maxBlock
+        nfr, shapes = self._cell_layout()
+        self.nframes = [np.float64(n) for n in nfr]
+        buf = np.empty(sum(a * b for _, (a, b) in shapes), dtype=np.complex128)
+        check(lib.cqt_forward_cells(self._context(), dptr(x), x.size, dptr(buf)),
+              "cqt_forward_cells")
+        self.cellCQT = self._unpack_cells(buf, shapes)
+
+    def cellCQT2spCQT(self):
+        """The full matrix from self.cellCQT (minqt.py:870-947; for MinQT with
+        linCellCQT2LinSpCQT, :1527-1549), on the GPU."""
+        if self.perfRast:
+            raise NotImplementedError("with perfRast=1 the raster is the transform itself")
+        buf, _ = self._pack_cells()
+        F, W, _ = self._shape(int(self.datalen_init))
+        sp = np.empty((F, W), dtype=np.complex128)
+        check(lib.cqt_cells_to_raster(self._context(), dptr(buf), int(self.datalen_init),
+                                      dptr(sp)), "cqt_cells_to_raster")
+        self._spCQT = sp
+
+    def _cells_from_raster(self):
+        """spCQT2CellCQT (minqt.py:949-1011, 1500-1525) on the GPU."""
+        F, W, _ = self._shape(int(self.datalen_init))
+        sp = np.ascontiguousarray(self._spCQT, dtype=np.complex128)
+        if sp.shape != (F, W):
+            raise ValueError("spCQT has shape %s instead of %s" % (sp.shape, (F, W)))
+        _, shapes = self._cell_layout()
+        buf = np.empty(sum(a * b for _, (a, b) in shapes), dtype=np.complex128)
+        check(lib.cqt_raster_to_cells(self._context(), dptr(sp), int(self.datalen_init),
+                                      dptr(buf)), "cqt_raster_to_cells")
+        self.cellCQT = self._unpack_cells(buf, shapes)
+        return self.cellCQT
+
+    def invertFromCellCQT(self):
+        """Inverse of self.cellCQT's octaves (minqt.py:1019-1055), on the GPU."""
+        return self._invert_cells(linear=False)
+
+    def _invert_cells(self, linear):
+        self._check_attr_inversion()
+        buf, shapes = self._pack_cells()
+        if shapes[-1][0] == 'linear' and not linear:
+            buf[-shapes[-1][1][0] * shapes[-1][1][1]:] = 0
+        y = np.empty(int(self.datalen_init))
+        check(lib.cqt_inverse_cells(self._context(), dptr(buf), y.size, dptr(y)),
+              "cqt_inverse_cells")
+        return y
+
     # ---------------------------------------------------------------- transfo
     def _set_transfo(self, X):
         if X.shape[0] == self.freqbins:
             self._spCQT = np.copy(X)
-            if hasattr(self, 'cellCQT'):
+            if not self.perfRast:
+                self.spCQT2CellCQT()
+            elif hasattr(self, 'cellCQT'):
                 del self.cellCQT
         else:
             raise ValueError('Transfo not of the right size: ' + str(X.shape) +
@@ -248,7 +350,9 @@ class CQTransfo(object):
 
     def _del_transfo(self):
         del self._spCQT
-        if hasattr(self, 'cellCQT'):
+        if not self.perfRast:
+            del self.cellCQT     # "erasing everything" (minqt.py:665-669)
+        elif hasattr(self, 'cellCQT'):
             del self.cellCQT
 
     transfo = property(fget=_get_transfo, fdel=_del_transfo, fset=_set_transfo,
@@ -256,12 +360,16 @@ class CQTransfo(object):
 
     def _get_spCQT(self):
         if not hasattr(self, '_spCQT'):
-            raise AttributeError("Some CQT should be computed before getting it.")
+            if self.perfRast or not hasattr(self, 'cellCQT'):
+                raise AttributeError("Some CQT should be computed before getting it.")
+            self.cellCQT2spCQT()     # minqt.py:722-729
         return self._spCQT
 
     def _set_spCQT(self, value):
         self._spCQT = value
-        if hasattr(self, 'cellCQT'):
+        if not self.perfRast:
+            self.spCQT2CellCQT()     # minqt.py:731-735
+        elif hasattr(self, 'cellCQT'):
             del self.cellCQT
 
     spCQT = property(fget=_get_spCQT, fset=_set_spCQT,
@@ -269,6 +377,8 @@ class CQTransfo(object):
 
     def spCQT2CellCQT(self):
         """Per-octave cells from spCQT (minqt.py:949-1011): re-indexing only."""
+        if not self.perfRast:
+            return self._cells_from_raster()
         k = self.cqtkernel
         bins, winNr = int(k.bins), int(k.winNr)
         emptyHops = k.first_center * 1. / k.atomHOP
@@ -325,12 +435,14 @@ class CQTransfo(object):
 
     def invertTransform(self):
         """invertFromCellCQT (minqt.py:1013-1055), on the GPU."""
+        if not self.perfRast:
+            return self.invertFromCellCQT()
         return self._invert()
 
 
 class MinQTransfo(CQTransfo):
     """Minimum-Q transform (minqt.py:1369-1550): CQT below the split
-    frequency, linear STFT bins above; perfRast=1 runs on the GPU."""
+    frequency, linear STFT bins above; on the GPU in both modes."""
     transformname = 'minqt'
 
     def __init__(self, fmax, bins, linFTLen, fs, fmin=70, **kwargs):
@@ -351,11 +463,45 @@ class MinQTransfo(CQTransfo):
         super(MinQTransfo, self).computeTransform(data)
         self.offsetSTFT = self.cqtkernel.first_center
 
+    def computeLinearPart(self, data):
+        """cellCQT['linear'] of data (minqt.py:1410-1435).  computeTransform
+        already fills it; this recomputes it alone, as the reference allows."""
+        if self.perfRast:
+            raise NotImplementedError("with perfRast=1 the linear rows are part of spCQT")
+        if not hasattr(self, 'cellCQT'):
+            raise AttributeError("computeCQT should be called before computeLinearPart")
+        cells = self.cellCQT
+        self._compute_cells(data)
+        cells['linear'] = self.cellCQT['linear']
+        self.cellCQT = cells
+        self.offsetSTFT = self.cqtkernel.first_center
+
     def invertTransform(self):
-        """invertFromSpCQTRast + invertLinearPart (minqt.py:1452-1485), on the GPU."""
+        """perfRast=1: invertFromSpCQTRast + invertLinearPart; perfRast=0:
+        invertFromCellCQT + invertLinearPart (minqt.py:1452-1485), on the GPU."""
         if not self.perfRast:
-            raise NotImplementedError("perfRast=0 is outside the GPU path")
+            return self._invert_cells(linear=True)
         return self._invert()
+
+    def invertLinearPart(self):
+        """Inverse of cellCQT['linear'] alone (minqt.py:1469-1485), on the GPU."""
+        if self.perfRast:
+            raise NotImplementedError("with perfRast=1 the linear rows are inverted with spCQT")
+        saved = self.cellCQT
+        try:
+            self.cellCQT = dict(saved)
+            for noct in range(int(self.octaveNr)):
+                self.cellCQT[noct] = np.zeros_like(saved[noct])
+            return self._invert_cells(linear=True)
+        finally:
+            self.cellCQT = saved
+
+    def linCellCQT2LinSpCQT(self):
+        """cellCQT['linear'] into the linear rows of spCQT (minqt.py:1534-1549);
+        cellCQT2spCQT does both parts in one device call."""
+        if self.perfRast:
+            raise NotImplementedError("with perfRast=1 the linear rows are part of spCQT")
+        self.cellCQT2spCQT()
 
     def _compute_frequencies(self):
         freqs = super(MinQTransfo, self)._compute_frequencies()
@@ -365,6 +511,8 @@ class MinQTransfo(CQTransfo):
 
     def spCQT2CellCQT(self):
         """CQT cells plus the linear part (minqt.py:1500-1525): re-indexing only."""
+        if not self.perfRast:
+            return self._cells_from_raster()
         super(MinQTransfo, self).spCQT2CellCQT()
         k = self.cqtkernel
         emptyHops = k.first_center * 1. / k.atomHOP

@@ -278,6 +278,44 @@ def bench_nmf(steps, warmup, F=1025, N=2000, K=64, seed=0):
             "reference_cpu": "0.0318 s/iter = 31.4 it/s (SURVEY §6, measured on CPU)"}
 
 
+def _bench_cqt_cells(x, steps, warmup, fs, wlen, hop):
+    """The same MinQT with perfRast=0: forward to cells, cells -> raster,
+    raster -> cells (the transfo setter) and the inverse from the cells."""
+    from pyfasst_amd import _lib
+    from pyfasst_amd.tftransforms import minqt
+    t = minqt.MinQTransfo(fmin=25, fmax=18000, bins=48, fs=fs, linFTLen=wlen,
+                          atomHopFactor=hop / float(wlen))
+    ms = {"forward_ms": [], "raster_ms": [], "raster_to_cells_ms": [], "inverse_ms": []}
+    for i in range(warmup + steps):
+        t.computeTransform(x)
+        sp = t.transfo
+        t.transfo = sp
+        y = t.invertTransform()
+        f, b, r, c = (ctypes.c_double() for _ in range(4))
+        _lib.check(_lib.lib.cqt_device_ms(t._context(), ctypes.byref(f), ctypes.byref(b)), "ms")
+        _lib.check(_lib.lib.cqt_raster_device_ms(t._context(), ctypes.byref(r), ctypes.byref(c)),
+                   "ms")
+        if i >= warmup:
+            for key, v in zip(("forward_ms", "raster_ms", "raster_to_cells_ms", "inverse_ms"),
+                              (f, r, c, b)):
+                ms[key].append(v.value)
+    out = {key: round(float(np.median(v)), 3) for key, v in ms.items()}
+    n_cells = sum(c.size for c in t.cellCQT.values())
+    # complex128 elements moved at the least: every cell element and every
+    # raster element once (the strided gather of raster -> cells touches more
+    # cache lines than it uses: at most the whole raster)
+    out["cells_bytes"] = 16 * n_cells
+    out["raster_bytes"] = 16 * sp.size
+    out["raster_gbps_min"] = round(16e-6 * (n_cells + sp.size) / out["raster_ms"], 1)
+    out["raster_to_cells_gbps_min"] = round(16e-6 * 2 * n_cells / out["raster_to_cells_ms"], 1)
+    out["raster_to_cells_gbps_max"] = round(16e-6 * (n_cells + sp.size) /
+                                            out["raster_to_cells_ms"], 1)
+    out["roundtrip_rel_err"] = float(np.abs(y - x).max() / np.abs(x).max())
+    out["cells"] = "%d octaves + linear, %d elements; raster %dx%d" % (
+        int(t.octaveNr), n_cells, sp.shape[0], sp.shape[1])
+    return out
+
+
 def bench_cqt(steps, warmup, fs=44100, wlen=4096, hop=512, T=10000, seed=0):
     from pyfasst_amd import _lib
     from pyfasst_amd.tftransforms import minqt
@@ -298,7 +336,9 @@ def bench_cqt(steps, warmup, fs=44100, wlen=4096, hop=512, T=10000, seed=0):
             inv.append(b.value)
     k = t.cqtkernel
     fm, im = float(np.median(fwd)), float(np.median(inv))
+    cells_run = _bench_cqt_cells(x, steps, warmup, fs, wlen, hop)
     return {"metric": "MinQT forward transforms/sec (device time)", "value": round(1e3 / fm, 3),
+            "perfRast0": cells_run,
             "unit": "transforms/s", "forward_ms": round(fm, 3), "inverse_ms": round(im, 3),
             "msamples_per_s_forward": round(L / fm / 1e3, 1), "steps": steps, "warmup": warmup,
             "dtype": "f64", "data": "synthetic modulated noise, RandomState(0)",
