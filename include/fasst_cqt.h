@@ -102,6 +102,47 @@ int cqt_device_ms(cqt_ctx *ctx, double *forward_ms, double *inverse_ms);
 /* The same for the last cqt_cells_to_raster and cqt_raster_to_cells.       */
 int cqt_raster_device_ms(cqt_ctx *ctx, double *to_raster_ms, double *to_cells_ms);
 
+/* ---- a FASST model on this transform, without leaving the device ----------
+ *
+ * The rasterised (perfRast=1) transform as the model context's front and back
+ * end: the forward chain writes the channel transforms into the model's
+ * observation planes, the inverse chain reads the separated images where the
+ * Wiener kernel left them, and every signal of a call (2 channels; 2 nsrc or
+ * 2 J images) goes through ONE chain whose kernels carry a batch dimension.
+ * No freqbins x width array crosses to the host.  `cqt` must be on the model's
+ * device and cqt_shape(cqt, L) must give the model's F x T: otherwise
+ * FASST_ERR_SHAPE, and the model is left as it was.
+ *
+ *   fasst_set_audio_cqt   comp_transf_Cx for transf = 'mqt' / 'minqt' / 'cqt'
+ *                         (audioModel.py:266-302): data [L][2] -> the resident
+ *                         channel transforms (what cqt_forward computes, bit
+ *                         for bit) and Cx, packed as fasst_set_stft packs it.
+ *   fasst_separate_waveforms_cqt
+ *                         separate_comps up to its waveforms (:1088-1233):
+ *                         the images of fasst_wiener_images (sources as last
+ *                         set by fasst_set_sources), inverted; y [nsrc][2][L].
+ *   fasst_sf_separate_waveforms_cqt
+ *                         the same from fasst_sf_wiener_images (two-factor
+ *                         model; nsrc, src_of as there); y [nsrc][2][L].
+ *   fasst_spatial_filter_waveforms_cqt
+ *                         separate_spatial_filter_comp (:891-1061): the gains
+ *                         of fasst_spatial_filter_gains applied to the resident
+ *                         transforms as the inverse loads them (the images are
+ *                         never stored); y [J][2][L].
+ * cqt_device_ms reports the device time of these chains like that of
+ * cqt_forward / cqt_inverse.                                                */
+int fasst_set_audio_cqt(fasst_ctx *ctx, cqt_ctx *cqt, const double *data, long L);
+int fasst_separate_waveforms_cqt(fasst_ctx *ctx, cqt_ctx *cqt, const double *psd, long L,
+                                 double *y);
+int fasst_sf_separate_waveforms_cqt(fasst_ctx *ctx, cqt_ctx *cqt, const double *psd, int nsrc,
+                                    const int *src_of, long L, double *y);
+int fasst_spatial_filter_waveforms_cqt(fasst_ctx *ctx, cqt_ctx *cqt, long L, double *y);
+/* Signals and kernel launches of the last forward or inverse transform chain
+ * on this context (a counter of its own; the layout transposes of the host
+ * entry points cqt_forward / cqt_inverse are not part of the chain): a batch
+ * of B signals reports the launch count of one signal.  Any may be NULL.    */
+int cqt_batch_info(cqt_ctx *ctx, int *signals, long *launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,12 @@ SIGNATURES = {
     "cqt_raster_to_cells": (ctypes.c_int, [_vp, _dp, ctypes.c_long, _dp]),
     "cqt_inverse_cells": (ctypes.c_int, [_vp, _dp, ctypes.c_long, _dp]),
     "cqt_raster_device_ms": (ctypes.c_int, [_vp, _dp, _dp]),
+    "fasst_set_audio_cqt": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_long]),
+    "fasst_separate_waveforms_cqt": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_long, _dp]),
+    "fasst_sf_separate_waveforms_cqt": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, _ip,
+                                                       ctypes.c_long, _dp]),
+    "fasst_spatial_filter_waveforms_cqt": (ctypes.c_int, [_vp, _vp, ctypes.c_long, _dp]),
+    "cqt_batch_info": (ctypes.c_int, [_vp, _ip, ctypes.POINTER(ctypes.c_long)]),
     "dict_wf0_cqt": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, _ip, ctypes.c_int, _dp,
                                     ctypes.c_double, ctypes.c_long, ctypes.c_int, _dp]),
     # include/fasst_viterbi.h

@@ -131,15 +131,14 @@ class FASST(object):
             data = np.asarray(aud.data, dtype=np.float64)
             L = data.shape[0]
             if self.sig_repr_params['transf'] != 'stft':
-                # MinQT / CQT of each channel on the GPU (audioModel.py:266-280), then
-                # the channel transforms become the engine's resident observation
-                X = []
-                for n in range(nc):
-                    self.tft.computeTransform(data[:, n])
-                    X.append(self.tft.transfo)
-                F, T = X[0].shape
+                # MinQT / CQT of both channels in one batched chain on the GPU
+                # (audioModel.py:266-280), written straight into the engine's
+                # resident observation: no F x T array reaches the host.
+                # self.tft is left as after computeTransform(), without a host
+                # copy of the last channel's transform
+                F, T = self.tft.prepare_resident(L)
                 self._engine = Engine(F, T, self.device)
-                self._engine.set_stft(np.array(X))
+                self._engine.set_audio_cqt(self.tft._context(), data)
                 self.nbFreqsSigRepr, self.nbFramesSigRepr = F, T
                 self._Cx = None
                 self._finish_noise_limits()
@@ -844,14 +843,19 @@ class FASST(object):
         return S[src_spat]
 
     def separated_waveforms(self, spec_comp_ind=None):
-        """The per-source, per-channel iSTFT of separated_images() without the
-        images leaving the GPU (STFT transform only): [n, channel, sample],
-        trimmed to the input length as tft.invertTransform() does
-        (audioModel.py:1187-1217, tftransforms/stft.py:71-131)."""
+        """The per-source, per-channel inverse transform of separated_images()
+        without the images leaving the GPU: [n, channel, sample], trimmed to
+        the input length as tft.invertTransform() does (audioModel.py:1187-1217,
+        tftransforms/stft.py:71-131).  With a MinQT / CQT every image goes
+        through one batched inverse chain (minqt.py:794-868, :1013-1055)."""
         t = self.tft
         if getattr(t, 'transformname', None) != 'stft':
-            raise NotImplementedError("device-resident separation needs the STFT transform "
-                                      "(use separated_images() + tft.invertTransform())")
+            cqt, L = self._resident_cqt()
+            if self._is_sf():
+                src_of, psd = self._separation_plan_sf(spec_comp_ind)
+                return self._engine.sf_separate_waveforms_cqt(cqt, psd, src_of, L)
+            src_spat, psd = self._separation_plan(spec_comp_ind)
+            return self._engine.separate_waveforms_cqt(cqt, psd, L)[src_spat]
         if self._is_sf():
             src_of, psd = self._separation_plan_sf(spec_comp_ind)
             Y = self._engine.sf_separate_waveforms(psd, src_of, t.synthWindow, t.window, t.ftlen,
@@ -860,6 +864,13 @@ class FASST(object):
         src_spat, psd = self._separation_plan(spec_comp_ind)
         Y = self._engine.separate_waveforms(psd, t.synthWindow, t.window, t.ftlen, t.fthop)
         return Y[src_spat][:, :, :t.datalen_init]
+
+    def _resident_cqt(self):
+        """(device context, signal length) of the rasterised MinQT / CQT whose
+        frame bookkeeping tft holds (comp_transf_Cx or computeTransform)."""
+        t = self.tft
+        t._check_attr_inversion()
+        return t._context(), int(t.datalen_init)
 
     def _separation_plan_sf(self, spec_comp_ind):
         """Two-factor model: upload, and (src_of, last annealed PSD), src_of[j]
@@ -927,27 +938,14 @@ class FASST(object):
         nc = self.audioObject.channels
         if nc != 2:
             raise NotImplementedError()
-        if getattr(self.tft, 'transformname', None) == 'stft':
-            Y = self.separated_waveforms(spec_comp_ind)   # iSTFT on the device
-            S = None
-            nbSources = Y.shape[0]
-        else:
-            S = self.separated_images(spec_comp_ind)
-            nbSources = S.shape[0]
+        Y = self.separated_waveforms(spec_comp_ind)   # inverse transform on the device
+        nbSources = Y.shape[0]
         if not hasattr(self, "files"):
             self.files = {}
         self.files['spat_comp'] = []
         fileroot = self.audioObject.filename.split('/')[-1][:-4]
         for n in range(nbSources):
-            if S is None:
-                ndata = Y[n].T
-            else:
-                ndata = []
-                for chan1 in range(nc):
-                    self.tft.transfo = S[n, chan1]
-                    ndata.append(self.tft.invertTransform())
-                    del self.tft.transfo
-                ndata = np.array(ndata).T
+            ndata = Y[n].T
             _suffix = ''
             if suffix is not None and n in suffix:
                 _suffix = '_' + suffix[n]
@@ -986,47 +984,35 @@ class FASST(object):
         return self._engine.spatial_filter_images()
 
     def spatial_filter_waveforms(self):
-        """The iSTFT of spatial_filter_images() with the gains applied as the
-        device iSTFT loads each frame (STFT transform only): [J, channel,
-        sample], trimmed as tft.invertTransform() does."""
+        """The inverse transform of spatial_filter_images() with the gains
+        applied as the device inverse loads the observation (the iSTFT's frame
+        loader; the MinQT / CQT inverse's raster gather, all 2 J images in one
+        batched chain): [J, channel, sample], trimmed as tft.invertTransform()
+        does."""
         t = self.tft
-        if getattr(t, 'transformname', None) != 'stft':
-            raise NotImplementedError("the fused spatial filter needs the STFT transform "
-                                      "(use spatial_filter_images() + tft.invertTransform())")
         self._spatial_filter_plan()
+        if getattr(t, 'transformname', None) != 'stft':
+            cqt, L = self._resident_cqt()
+            return self._engine.spatial_filter_waveforms_cqt(cqt, L)
         Y = self._engine.spatial_filter_waveforms(t.synthWindow, t.window, t.ftlen, t.fthop)
         return Y[:, :, :t.datalen_init]
 
     def separate_spatial_filter_comp(self, dir_results=None, suffix=None):
         """Separate with the spatial filter of the mixing parameters alone, one
         WAV per spatial component (audioModel.py:891-1061).  With the STFT the
-        gains are applied inside the device iSTFT; other transforms take the
-        device images and tft.invertTransform()."""
+        gains are applied inside the device iSTFT, with a MinQT / CQT inside
+        the batched device inverse."""
         if dir_results is None:
             dir_results = '/'.join(self.audioObject.filename.split('/')[:-1])
         self._spatial_filter_plan()
-        nc = self.audioObject.channels
-        if getattr(self.tft, 'transformname', None) == 'stft':
-            Y = self.spatial_filter_waveforms()
-            S = None
-            nbSources = Y.shape[0]
-        else:
-            S = self._engine.spatial_filter_images()
-            nbSources = S.shape[0]
+        Y = self.spatial_filter_waveforms()
+        nbSources = Y.shape[0]
         if not hasattr(self, 'files'):
             self.files = {}
         self.files['spatial'] = []
         fileroot = self.audioObject.filename.split('/')[-1][:-4]
         for n in range(nbSources):
-            if S is None:
-                ndata = Y[n].T
-            else:
-                ndata = []
-                for chan1 in range(nc):
-                    self.tft.transfo = S[n, chan1]
-                    ndata.append(self.tft.invertTransform())
-                    del self.tft.transfo
-                ndata = np.array(ndata).T
+            ndata = Y[n].T
             _suffix = '_spatial'
             if suffix is not None and n in suffix:
                 _suffix += '_' + suffix[n]

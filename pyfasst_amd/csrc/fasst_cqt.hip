@@ -50,8 +50,15 @@
 //
 // Internal spCQT layout: frame-major [W][F] (bins contiguous, the FASST
 // engine's device layout); the C ABI hands out [F][W].
+//
+// Batch: every kernel of the rasterised chains takes the signal index from a
+// grid dimension and per-signal strides, and the raster's row pitch; a batch
+// of one is the single-signal transform.  A FASST model's two channels, and
+// its 2 nsrc separated images, go through one chain in the model's own
+// planes (fasst_cqt_dev.h).
 #include "fasst_fft.h"
 #include "fasst_odgd.h"
+#include "fasst_cqt_dev.h"
 #include "../../include/fasst_cqt.h"
 
 #include <algorithm>
@@ -94,8 +101,13 @@ __device__ __forceinline__ double iir_step(const Iir &f, double *z, double x) {
 }
 
 // forward pass: y1 = lfilter(b, a, ext, zi * ext[0]), ne = n + 42 samples
+// (blockIdx.y: the signal of a batch, xs / ys samples apart; each signal's
+// initial state scales with its own first sample)
 __global__ __launch_bounds__(256) void k_iir_fwd(const double *__restrict__ x, long n, int up,
-                                                 const Iir f, int warm, double *__restrict__ y1) {
+                                                 const Iir f, int warm, double *__restrict__ y1,
+                                                 size_t xs, size_t ys) {
+  x += blockIdx.y * xs;
+  y1 += blockIdx.y * ys;
   const long ne = n + 2 * kIirPad;
   const long j1 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * kIirChunk;
   if (j1 >= ne) return;
@@ -116,7 +128,9 @@ __global__ __launch_bounds__(256) void k_iir_fwd(const double *__restrict__ x, l
 // (x[::2], minqt.py:646); else out[p] = scale * y.
 __global__ __launch_bounds__(256) void k_iir_bwd(const double *__restrict__ y1, long n,
                                                  const Iir f, int warm, double *__restrict__ out,
-                                                 int decim, double scale) {
+                                                 int decim, double scale, size_t ys, size_t os) {
+  y1 += blockIdx.y * ys;
+  out += blockIdx.y * os;
   const long ne = n + 2 * kIirPad;
   const long j1 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * kIirChunk;
   if (j1 >= ne) return;
@@ -143,8 +157,11 @@ __global__ __launch_bounds__(256) void k_iir_bwd(const double *__restrict__ y1, 
 __global__ __launch_bounds__(256) void k_cqt_frames(const double *__restrict__ x, long len, int hop,
                                                     const double2 *__restrict__ tw, int N, int logN,
                                                     int kb, int nb, int nbp,
-                                                    double2 *__restrict__ XX) {
+                                                    double2 *__restrict__ XX, size_t xs,
+                                                    size_t XXs) {
   extern __shared__ __attribute__((aligned(16))) double2 buf[];
+  x += blockIdx.y * xs;   // signal blockIdx.y of a batch
+  XX += blockIdx.y * XXs;
   const long s0 = (long)blockIdx.x * hop;
   for (int i = threadIdx.x; i < N; i += blockDim.x) {
     const long s = s0 + i;
@@ -159,8 +176,9 @@ __global__ __launch_bounds__(256) void k_cqt_frames(const double *__restrict__ x
 struct BandArgs {
   const double2 *K;   // [M][nbp]: conj(sparKernel.T), band columns
   const double2 *XX;  // [nfr][nbp]
-  double2 *sp;        // [W][F] frame-major spCQT
-  int M, nb, nbp, kb, N, nfr, win_nr, nshifts, row0, W, F;
+  double2 *sp;        // [W][ld] frame-major spCQT (ld >= F: the row pitch)
+  size_t XXs, sps;    // batch (blockIdx.z): elements between the signals' XX / sp
+  int M, nb, nbp, kb, N, nfr, win_nr, nshifts, row0, W, ld;
   long d;             // drop alignment of this octave, int(drop * nshifts)
   double inc;         // atomHOP / 2^i
 };
@@ -173,6 +191,8 @@ struct BandArgs {
 __global__ __launch_bounds__(256) void k_cqt_band(const BandArgs a) {
   extern __shared__ __attribute__((aligned(16))) double2 sx[];  // [kBandFrames][nbp]
   const int n0 = blockIdx.x * kBandFrames, s = blockIdx.y;
+  const double2 *XX = a.XX + blockIdx.z * a.XXs;
+  double2 *sp = a.sp + blockIdx.z * a.sps;
   const double shift = (double)s * a.inc;
   for (int idx = threadIdx.x; idx < kBandFrames * a.nb; idx += blockDim.x) {
     const int fr = idx / a.nb, kk = idx - fr * a.nb;
@@ -183,7 +203,7 @@ __global__ __launch_bounds__(256) void k_cqt_band(const BandArgs a) {
       const double ang = 2.0 * M_PI * (double)(a.kb + kk) * shift / (double)a.N;
       double sn, cs;
       sincos(ang, &sn, &cs);
-      const double2 xx = a.XX[(size_t)n * a.nbp + kk];
+      const double2 xx = XX[(size_t)n * a.nbp + kk];
       v = make_double2(xx.x * cs - xx.y * sn, xx.x * sn + xx.y * cs);
     }
     sx[fr * a.nbp + kk] = v;
@@ -205,8 +225,8 @@ __global__ __launch_bounds__(256) void k_cqt_band(const BandArgs a) {
     const long c = (long)s + (long)at * a.nshifts + (long)n * a.win_nr * a.nshifts;
     const double2 v = make_double2(re, im);
     const size_t row = (size_t)(a.row0 + nbin);
-    if (c >= a.d) a.sp[(size_t)(c - a.d) * a.F + row] = v;
-    if (c >= (long)a.W - a.d && c < a.W) a.sp[(size_t)c * a.F + row] = v;
+    if (c >= a.d) sp[(size_t)(c - a.d) * a.ld + row] = v;
+    if (c >= (long)a.W - a.d && c < a.W) sp[(size_t)c * a.ld + row] = v;
   }
 }
 
@@ -350,9 +370,12 @@ __global__ __launch_bounds__(256) void k_cqt_raster_lin(const double2 *__restric
 __global__ __launch_bounds__(256) void k_cqt_linear(const double *__restrict__ xp, long lp, long off,
                                                     const double *__restrict__ win,
                                                     const double2 *__restrict__ tw, int N, int logN,
-                                                    int hop, int drop, int kmax, int row0, int F,
-                                                    double2 *__restrict__ sp) {
+                                                    int hop, int drop, int kmax, int row0, int ld,
+                                                    double2 *__restrict__ sp, size_t xs,
+                                                    size_t sps) {
   extern __shared__ __attribute__((aligned(16))) double2 buf[];
+  xp += blockIdx.y * xs;   // signal blockIdx.y of a batch
+  sp += blockIdx.y * sps;
   const int n = drop + blockIdx.x;
   for (int i = threadIdx.x; i < N; i += blockDim.x) {
     const long s = off + (long)n * hop + i;
@@ -361,7 +384,7 @@ __global__ __launch_bounds__(256) void k_cqt_linear(const double *__restrict__ x
   }
   __syncthreads();
   lds_fft(buf, tw, N, logN);
-  double2 *o = sp + (size_t)blockIdx.x * F + row0 - kmax;
+  double2 *o = sp + (size_t)blockIdx.x * ld + row0 - kmax;
   for (int k = kmax + threadIdx.x; k <= N / 2; k += blockDim.x) o[k] = buf[k];
 }
 
@@ -378,12 +401,13 @@ __global__ __launch_bounds__(256) void k_cqt_transpose(const double2 *__restrict
 }
 
 struct ICellArgs {
-  const double2 *sp;   // [W][F]
+  CqtImages im;        // the rasters [W][ld], one per signal of the batch (blockIdx.y)
   const double2 *cells;  // [M][nfr] of this octave (k_icqt_frames<true>), else unused
   const double2 *S;    // [nb][M]: sparKernel rows kb..ke-1
-  double *frames;      // [nfr][N]
+  double *frames;      // [nfr][N], frs doubles between the signals
+  size_t frs;
   const double2 *tw;   // inverse twiddles
-  int N, logN, kb, nb, M, F, W, win_nr, row0, step, shift, nfr;
+  int N, logN, kb, nb, M, W, win_nr, row0, step, shift, nfr;
   long dropped, ncolx;
   double ns;           // divisor of the rasterised inverse (nshifts), 1 for cells
 };
@@ -391,14 +415,14 @@ struct ICellArgs {
 // cell[m][n] of spCQT2CellCQT (minqt.py:966-1011) for the octave whose rows
 // start at row0 (step = 2^noct), from spCQT shifted left `shift` times
 // (minqt.py:845-851: the last column repeats)
-__device__ __forceinline__ double2 cell_at(const ICellArgs &a, int m, int n) {
+__device__ __forceinline__ double2 cell_at(const ICellArgs &a, int b, int m, int n) {
   const int nbin = m / a.win_nr, at = m - nbin * a.win_nr;
   const long j = (long)n * a.win_nr + at;
   if (j < a.dropped) return make_double2(0.0, 0.0);
   const long q = j - a.dropped;
   if (q >= a.ncolx) return make_double2(0.0, 0.0);
   const long c = min(q * a.step + a.shift, (long)a.W - 1);
-  return a.sp[(size_t)c * a.F + a.row0 + nbin];
+  return image_at(a.im, b, c, a.row0 + nbin);
 }
 
 // frame n: 2 Re(ifft(sparKernel . cell[:, n])) / ns   (minqt.py:829-839, :1028-1041);
@@ -408,10 +432,10 @@ template <bool kGiven>
 __global__ __launch_bounds__(256) void k_icqt_frames(const ICellArgs a) {
   extern __shared__ __attribute__((aligned(16))) double2 buf[];  // [N] + [M] cell column
   double2 *cell = buf + a.N;
-  const int n = blockIdx.x;
+  const int n = blockIdx.x, b = blockIdx.y;
   for (int i = threadIdx.x; i < a.N; i += blockDim.x) buf[i] = make_double2(0.0, 0.0);
   for (int m = threadIdx.x; m < a.M; m += blockDim.x)
-    cell[m] = kGiven ? a.cells[(size_t)m * a.nfr + n] : cell_at(a, m, n);
+    cell[m] = kGiven ? a.cells[(size_t)m * a.nfr + n] : cell_at(a, b, m, n);
   __syncthreads();
   for (int kk = threadIdx.x; kk < a.nb; kk += blockDim.x) {
     const double2 *sr = a.S + (size_t)kk * a.M;
@@ -426,16 +450,19 @@ __global__ __launch_bounds__(256) void k_icqt_frames(const ICellArgs a) {
   __syncthreads();
   lds_fft(buf, a.tw, a.N, a.logN);
   const double invN = 1.0 / (double)a.N;
-  double *o = a.frames + (size_t)n * a.N;
+  double *o = a.frames + b * a.frs + (size_t)n * a.N;
   for (int t = threadIdx.x; t < a.N; t += blockDim.x) o[t] = 2.0 * ((buf[t].x * invN) / a.ns);
 }
 
 // y[p] += sum_n frame_n[p - a_n], a_n = int(n hop + off), frames in order
-// (the reference's y[a:a+N] += yoct, minqt.py:840, :1042)
+// (the reference's y[a:a+N] += yoct, minqt.py:840, :1042); blockIdx.y: the
+// signal of a batch, with its own frames (frs apart) and accumulator (ys apart)
 __global__ void k_icqt_ola(const double *__restrict__ frames, int nfr, int N, int hop, double off,
-                           double *__restrict__ y, long ylen) {
+                           double *__restrict__ y, long ylen, size_t frs, size_t ys) {
   const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= ylen) return;
+  frames += blockIdx.y * frs;
+  y += blockIdx.y * ys;
   long nlo = (long)floor(((double)p - (double)N + 1.0 - off) / hop) - 1;
   long nhi = (long)floor(((double)p - off) / hop) + 1;
   nlo = max(nlo, 0L);
@@ -449,19 +476,21 @@ __global__ void k_icqt_ola(const double *__restrict__ frames, int nfr, int N, in
 }
 
 // MinQT linear inverse frames: window * irfft(Y[:, n])[:N] with
-// Y[kmax + r][n] = spCQT[row0 + r][n - dropped] (minqt.py:1476-1482, stft.py:108-113)
-__global__ __launch_bounds__(256) void k_icqt_lin_frames(const double2 *__restrict__ sp, int F,
-                                                         int row0, int kmax, long dropped,
+// Y[kmax + r][n] = spCQT[row0 + r][n - dropped] (minqt.py:1476-1482, stft.py:108-113);
+// blockIdx.y: the signal of a batch (frames frs apart)
+__global__ __launch_bounds__(256) void k_icqt_lin_frames(const CqtImages im, int row0, int kmax,
+                                                         long dropped,
                                                          const double *__restrict__ win,
                                                          const double2 *__restrict__ tw, int N,
-                                                         int logN, double *__restrict__ frames) {
+                                                         int logN, double *__restrict__ frames,
+                                                         size_t frs) {
   extern __shared__ __attribute__((aligned(16))) double2 buf[];
-  const int n = blockIdx.x, h = N / 2;
-  const double2 *col = n >= dropped ? sp + (size_t)(n - dropped) * F + row0 - kmax : nullptr;
+  const int n = blockIdx.x, b = blockIdx.y, h = N / 2;
+  frames += b * frs;
   for (int i = threadIdx.x; i < N; i += blockDim.x) {
     const int k = i <= h ? i : N - i;
     double2 v = make_double2(0.0, 0.0);
-    if (col && k >= kmax) v = col[k];
+    if (n >= dropped && k >= kmax) v = image_at(im, b, n - dropped, row0 - kmax + k);
     if (i == 0 || i == h) v.y = 0.0;
     else if (i > h) v.y = -v.y;
     buf[bitrev(i, logN)] = v;
@@ -476,9 +505,11 @@ __global__ __launch_bounds__(256) void k_icqt_lin_frames(const double2 *__restri
 // y[p] += istft(...)[p + off] with the window-product normalisation (stft.py:114-129)
 __global__ void k_icqt_lin_ola(const double *__restrict__ frames, int nfr, int N, int hop,
                                const double *__restrict__ win, long off, double *__restrict__ y,
-                               long L) {
+                               long L, size_t frs, size_t ys) {
   const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= L) return;
+  frames += blockIdx.y * frs;   // signal blockIdx.y of a batch
+  y += blockIdx.y * ys;
   const long s = p + off;
   long nlo = (s - N) / hop + 1;
   if (s - N < 0) nlo = 0;
@@ -545,10 +576,19 @@ struct cqt_ctx {
   int warm = 256;
   DBuf<double2> K, S, tw_f, tw_i, ltw_f, ltw_i;
   DBuf<double> lwin;
-  // work space, sized for the last signal length
+  // work space, sized for the last signal length and the largest batch so
+  // far: signal b of a batch owns [b * n_x, (b + 1) * n_x) of xp, and so on
+  // (sp / sph, the host entry points' raster and its transpose, are single)
   long cap_L = -1;
+  int cap_B = 0;
+  size_t n_xp = 0, n_s = 0, n_y1 = 0, n_fr = 0, n_y = 0, n_XX = 0;
   DBuf<double> xp, sa, sb, y1, frames, yb, yc;
   DBuf<double2> XX, sp, sph;
+  // signals and kernel launches of the last forward / inverse chain
+  // (cqt_batch_info); the host entry points' layout transposes are not part
+  // of the chain
+  int signals = 0;
+  long launches = 0;
   // perfRast=0: the packed per-octave cells (+ linear cell), allocated by the
   // first cell call only
   long cap_cells = -1;
@@ -620,8 +660,8 @@ int geometry(const cqt_ctx *c, long L, Geo &g) {
   return FASST_OK;
 }
 
-int ensure_work(cqt_ctx *c, const Geo &g, long L) {
-  if (c->cap_L == L) return FASST_OK;
+int ensure_work(cqt_ctx *c, const Geo &g, long L, int B = 1) {
+  if (c->cap_L == L && B <= c->cap_B) return FASST_OK;
   int st;
   const long ext = g.Lp + 2 * kIirPad;
   // inverse y: at most Lp grown by one frame extent per octave, doubled per octave
@@ -629,27 +669,49 @@ int ensure_work(cqt_ctx *c, const Geo &g, long L) {
   size_t fr = 0;
   for (int i = 0; i < c->oct; ++i) fr = std::max(fr, (size_t)g.nfr[i] * c->N);
   if (c->lin_N) fr = std::max(fr, (size_t)g.W * c->lin_N);
-  if ((st = c->xp.alloc(g.Lp)) || (st = c->sa.alloc(g.Lp / 2 + 2)) ||
-      (st = c->sb.alloc(g.Lp / 2 + 2)) || (st = c->y1.alloc(std::max(ext, 2 * ycap + 64))) ||
-      (st = c->XX.alloc((size_t)g.nfr[0] * c->nbp)) || (st = c->sp.alloc((size_t)g.W * g.F)) ||
-      (st = c->sph.alloc((size_t)g.W * g.F)) || (st = c->frames.alloc(fr)) ||
-      (st = c->yb.alloc(ycap)) || (st = c->yc.alloc(ycap)))
+  c->cap_L = -1;
+  c->cap_B = 0;
+  c->n_xp = g.Lp;
+  c->n_s = g.Lp / 2 + 2;
+  c->n_y1 = std::max(ext, 2 * ycap + 64);
+  c->n_XX = (size_t)g.nfr[0] * c->nbp;
+  c->n_fr = fr;
+  c->n_y = ycap;
+  if ((st = c->xp.alloc(B * c->n_xp)) || (st = c->sa.alloc(B * c->n_s)) ||
+      (st = c->sb.alloc(B * c->n_s)) || (st = c->y1.alloc(B * c->n_y1)) ||
+      (st = c->XX.alloc(B * c->n_XX)) || (st = c->sp.alloc((size_t)g.W * g.F)) ||
+      (st = c->sph.alloc((size_t)g.W * g.F)) || (st = c->frames.alloc(B * c->n_fr)) ||
+      (st = c->yb.alloc(B * c->n_y)) || (st = c->yc.alloc(B * c->n_y)))
     return st;
   c->cap_L = L;
+  c->cap_B = B;
   return FASST_OK;
 }
 
-int filtfilt(cqt_ctx *c, const double *src, long n, int up, double *out, int decim, double scale) {
+#define CQT_LAUNCH_CHECK() \
+  do {                     \
+    FASST_LAUNCH_CHECK();  \
+    ++c->launches;         \
+  } while (0)
+
+// filtfilt of B signals in one launch per pass: src / out srcs / outs samples
+// apart, the intermediate y1 in the context's own per-signal slices
+int filtfilt(cqt_ctx *c, hipStream_t s, int B, const double *src, size_t srcs, long n, int up,
+             double *out, size_t outs, int decim, double scale) {
   if (n <= kIirPad) {
     set_error("filtfilt: %ld samples <= padlen %d", n, kIirPad);
     return FASST_ERR_SHAPE;
   }
   const long ne = n + 2 * kIirPad;
-  const int grid = (int)((ne + (long)kIirChunk * 256 - 1) / ((long)kIirChunk * 256));
-  k_iir_fwd<<<grid, 256, 0, c->stream>>>(src, n, up, c->iir, c->warm, c->y1.p);
-  FASST_LAUNCH_CHECK();
-  k_iir_bwd<<<grid, 256, 0, c->stream>>>(c->y1.p, n, c->iir, c->warm, out, decim, scale);
-  FASST_LAUNCH_CHECK();
+  if ((size_t)ne > c->n_y1) {
+    set_error("filtfilt: %ld samples exceed the work space (%zu)", ne, c->n_y1);
+    return FASST_ERR_SHAPE;
+  }
+  const dim3 grid((unsigned)((ne + (long)kIirChunk * 256 - 1) / ((long)kIirChunk * 256)), B);
+  k_iir_fwd<<<grid, 256, 0, s>>>(src, n, up, c->iir, c->warm, c->y1.p, srcs, c->n_y1);
+  CQT_LAUNCH_CHECK();
+  k_iir_bwd<<<grid, 256, 0, s>>>(c->y1.p, n, c->iir, c->warm, out, decim, scale, c->n_y1, outs);
+  CQT_LAUNCH_CHECK();
   return FASST_OK;
 }
 
@@ -659,30 +721,35 @@ int set_smem(const void *fn, size_t bytes) {
   return FASST_OK;
 }
 
-// the transform of the padded signal in c->xp into c->sp ([W][F], frame-major)
-int forward_dev(cqt_ctx *c, const Geo &g, hipStream_t s) {
+// the transforms of the B padded signals in c->xp (n_xp apart) into sp: signal
+// b's raster at sp + b * sps, [W][ld] frame-major, already zero
+int forward_dev(cqt_ctx *c, const Geo &g, hipStream_t s, int B, double2 *sp, int ld, size_t sps) {
   int st;
-  FASST_HIP(hipMemsetAsync(c->sp.p, 0, (size_t)g.W * g.F * sizeof(double2), s));
+  c->signals = B;
+  c->launches = 0;
   if (c->lin_N && g.W > g.drop0) {   // computeLinearPart on the padded signal
     const long off = (long)c->first_center - c->lin_N / 2;
-    k_cqt_linear<<<g.W - g.drop0, 256, c->lin_N * sizeof(double2), s>>>(
+    k_cqt_linear<<<dim3(g.W - g.drop0, B), 256, c->lin_N * sizeof(double2), s>>>(
         c->xp.p, g.Lp, off, c->lwin.p, c->ltw_f.p, c->lin_N, c->lin_logN, c->atom_hop, g.drop0,
-        c->kmax, c->bins * c->oct, g.F, c->sp.p);
-    FASST_LAUNCH_CHECK();
+        c->kmax, c->bins * c->oct, ld, sp, c->n_xp, sps);
+    CQT_LAUNCH_CHECK();
   }
   const double *cur = c->xp.p;
+  size_t curs = c->n_xp;
   double *next = c->sa.p;
   for (int i = 0; i < c->oct; ++i) {
     const int nfr = g.nfr[i];
     if (c->nb > 0) {
-      k_cqt_frames<<<nfr, 256, c->N * sizeof(double2), s>>>(cur, g.len[i], c->fft_hop, c->tw_f.p,
-                                                           c->N, c->logN, c->kb, c->nb, c->nbp,
-                                                           c->XX.p);
-      FASST_LAUNCH_CHECK();
+      k_cqt_frames<<<dim3(nfr, B), 256, c->N * sizeof(double2), s>>>(
+          cur, g.len[i], c->fft_hop, c->tw_f.p, c->N, c->logN, c->kb, c->nb, c->nbp, c->XX.p, curs,
+          c->n_XX);
+      CQT_LAUNCH_CHECK();
       BandArgs a;
       a.K = c->K.p;
       a.XX = c->XX.p;
-      a.sp = c->sp.p;
+      a.sp = sp;
+      a.XXs = c->n_XX;
+      a.sps = sps;
       a.M = c->M;
       a.nb = c->nb;
       a.nbp = c->nbp;
@@ -693,20 +760,27 @@ int forward_dev(cqt_ctx *c, const Geo &g, hipStream_t s) {
       a.nshifts = 1 << i;
       a.row0 = c->bins * (c->oct - i - 1);
       a.W = g.W;
-      a.F = g.F;
+      a.ld = ld;
       a.d = g.d[i];
       a.inc = (double)c->atom_hop / (double)(1L << i);
-      k_cqt_band<<<dim3((nfr + kBandFrames - 1) / kBandFrames, 1 << i), 256,
+      k_cqt_band<<<dim3((nfr + kBandFrames - 1) / kBandFrames, 1 << i, B), 256,
                    kBandFrames * c->nbp * sizeof(double2), s>>>(a);
-      FASST_LAUNCH_CHECK();
+      CQT_LAUNCH_CHECK();
     }
     if (i != c->oct - 1) {
-      if ((st = filtfilt(c, cur, g.len[i], 0, next, 1, 1.0))) return st;
+      if ((st = filtfilt(c, s, B, cur, curs, g.len[i], 0, next, c->n_s, 1, 1.0))) return st;
       cur = next;
+      curs = c->n_s;
       next = (next == c->sa.p) ? c->sb.p : c->sa.p;
     }
   }
   return FASST_OK;
+}
+
+// one signal into the context's own raster c->sp ([W][F])
+int forward_dev(cqt_ctx *c, const Geo &g, hipStream_t s) {
+  FASST_HIP(hipMemsetAsync(c->sp.p, 0, (size_t)g.W * g.F * sizeof(double2), s));
+  return forward_dev(c, g, s, 1, c->sp.p, g.F, 0);
 }
 
 // offset of octave noct's cell (noct == oct: the linear cell) in the packed cells
@@ -732,15 +806,19 @@ int ensure_cells(cqt_ctx *c, const Geo &g, long L) {
 // from the raster in c->sp (MinQT: invertFromSpCQTRast; CQT: invertFromCellCQT
 // on the cells spCQT2CellCQT derives).  cells given (perfRast=0): invertFromCellCQT
 // on them (minqt.py:1019-1055), then invertLinearPart on the linear cell.
+// The B rasters of a batch are `im`; signal b's result is at *yout_p + b * n_y.
 int inverse_dev(cqt_ctx *c, const Geo &g, long L, const double2 *cells, hipStream_t s,
-                double **yout_p) {
+                double **yout_p, const CqtImages &im, int B) {
   int st;
+  c->signals = B;
+  c->launches = 0;
   const bool rast = !cells && c->lin_N != 0;
   const double empty_hops = (double)c->first_center / (double)c->atom_hop;
   long ysize = (long)std::ceil((double)L / std::ldexp(1.0, c->oct - 1));
-  const long ycap = (long)c->yb.n;
+  const long ycap = (long)c->n_y;
   double *ycur = c->yb.p, *yalt = c->yc.p;
-  FASST_HIP(hipMemsetAsync(ycur, 0, ycap * sizeof(double), s));
+  // every signal's overlap-add accumulator starts from zero
+  FASST_HIP(hipMemsetAsync(ycur, 0, (size_t)B * ycap * sizeof(double), s));
   for (int noct = c->oct - 1; noct >= 0; --noct) {
     const long step = 1L << noct;
     const int ns = rast ? (int)step : 1;
@@ -765,17 +843,17 @@ int inverse_dev(cqt_ctx *c, const Geo &g, long L, const double2 *cells, hipStrea
     }
     for (int sh = 0; sh < ns; ++sh) {
       ICellArgs a;
-      a.sp = c->sp.p;
+      a.im = im;
       a.cells = cells ? cells + cell_off : nullptr;
       a.S = c->S.p;
       a.frames = c->frames.p;
+      a.frs = c->n_fr;
       a.tw = c->tw_i.p;
       a.N = c->N;
       a.logN = c->logN;
       a.kb = c->kb;
       a.nb = c->nb;
       a.M = c->M;
-      a.F = g.F;
       a.W = g.W;
       a.win_nr = c->win_nr;
       a.row0 = c->bins * (c->oct - noct - 1);
@@ -785,22 +863,24 @@ int inverse_dev(cqt_ctx *c, const Geo &g, long L, const double2 *cells, hipStrea
       a.dropped = dropped;
       a.ncolx = ncolx;
       a.ns = (double)ns;
+      const dim3 gfr(nfr, B);
       if (cells)
-        k_icqt_frames<true><<<nfr, 256, ((size_t)c->N + c->M) * sizeof(double2), s>>>(a);
+        k_icqt_frames<true><<<gfr, 256, ((size_t)c->N + c->M) * sizeof(double2), s>>>(a);
       else
-        k_icqt_frames<false><<<nfr, 256, ((size_t)c->N + c->M) * sizeof(double2), s>>>(a);
-      FASST_LAUNCH_CHECK();
-      k_icqt_ola<<<(int)((ysize + 255) / 256), 256, 0, s>>>(c->frames.p, nfr, c->N, c->fft_hop,
-                                                            rast ? sh * inc : 0.0, ycur, ysize);
-      FASST_LAUNCH_CHECK();
+        k_icqt_frames<false><<<gfr, 256, ((size_t)c->N + c->M) * sizeof(double2), s>>>(a);
+      CQT_LAUNCH_CHECK();
+      k_icqt_ola<<<dim3((unsigned)((ysize + 255) / 256), B), 256, 0, s>>>(
+          c->frames.p, nfr, c->N, c->fft_hop, rast ? sh * inc : 0.0, ycur, ysize, c->n_fr,
+          c->n_y);
+      CQT_LAUNCH_CHECK();
     }
     if (noct != 0) {
       if (2 * ysize > ycap) {
         set_error("inverse CQT buffer overflow (%ld > %ld)", 2 * ysize, ycap);
         return FASST_ERR_SHAPE;
       }
-      FASST_HIP(hipMemsetAsync(yalt, 0, ycap * sizeof(double), s));
-      if ((st = filtfilt(c, ycur, 2 * ysize, 1, yalt, 0, 2.0))) return st;
+      FASST_HIP(hipMemsetAsync(yalt, 0, (size_t)B * ycap * sizeof(double), s));
+      if ((st = filtfilt(c, s, B, ycur, c->n_y, 2 * ysize, 1, yalt, c->n_y, 0, 2.0))) return st;
       std::swap(ycur, yalt);
       ysize *= 2;
     }
@@ -813,14 +893,16 @@ int inverse_dev(cqt_ctx *c, const Geo &g, long L, const double2 *cells, hipStrea
   *yout_p = yout;
   if (c->lin_N) {                     // + invertLinearPart (minqt.py:1469-1485)
     long dropped0 = (long)(empty_hops * (std::ldexp(1.0, c->oct - 1) - 1.0));
-    const double2 *lsp = c->sp.p;
-    int lF = g.F, lrow0 = c->bins * c->oct;
+    CqtImages lim = im;
+    int lrow0 = c->bins * c->oct;
     if (cells) {   // cellCQT['linear'] [linBins][W] -> frame-major scratch, nothing dropped
       k_cqt_transpose<<<dim3((g.W + 15) / 16, (c->lin_bins + 15) / 16), 256, 0, s>>>(
           cells + cell_offset(c, g, c->oct), c->sp.p, c->lin_bins, g.W);
-      FASST_LAUNCH_CHECK();
+      CQT_LAUNCH_CHECK();
       dropped0 = 0;
-      lF = c->lin_bins;
+      lim = CqtImages();
+      lim.S = c->sp.p;
+      lim.ld = c->lin_bins;
       lrow0 = 0;
     }
     const long len_lin = (long)c->atom_hop * (g.W - 1) + c->lin_N - c->lin_N / 2;
@@ -829,15 +911,25 @@ int inverse_dev(cqt_ctx *c, const Geo &g, long L, const double2 *cells, hipStrea
       set_error("linear inverse: %ld samples < %ld", len_lin, off + L);
       return FASST_ERR_SHAPE;
     }
-    k_icqt_lin_frames<<<g.W, 256, c->lin_N * sizeof(double2), s>>>(
-        lsp, lF, lrow0, c->kmax, dropped0, c->lwin.p, c->ltw_i.p, c->lin_N,
-        c->lin_logN, c->frames.p);
-    FASST_LAUNCH_CHECK();
-    k_icqt_lin_ola<<<(int)((L + 255) / 256), 256, 0, s>>>(c->frames.p, g.W, c->lin_N, c->atom_hop,
-                                                          c->lwin.p, off + c->lin_N / 2, yout, L);
-    FASST_LAUNCH_CHECK();
+    k_icqt_lin_frames<<<dim3(g.W, B), 256, c->lin_N * sizeof(double2), s>>>(
+        lim, lrow0, c->kmax, dropped0, c->lwin.p, c->ltw_i.p, c->lin_N, c->lin_logN, c->frames.p,
+        c->n_fr);
+    CQT_LAUNCH_CHECK();
+    k_icqt_lin_ola<<<dim3((unsigned)((L + 255) / 256), B), 256, 0, s>>>(
+        c->frames.p, g.W, c->lin_N, c->atom_hop, c->lwin.p, off + c->lin_N / 2, yout, L, c->n_fr,
+        c->n_y);
+    CQT_LAUNCH_CHECK();
   }
   return FASST_OK;
+}
+
+// one signal from the context's own raster c->sp ([W][F]) or the given cells
+int inverse_dev(cqt_ctx *c, const Geo &g, long L, const double2 *cells, hipStream_t s,
+                double **yout_p) {
+  CqtImages im;
+  im.S = c->sp.p;
+  im.ld = g.F;
+  return inverse_dev(c, g, L, cells, s, yout_p, im, 1);
 }
 
 }  // namespace
@@ -1091,7 +1183,7 @@ int cqt_forward_cells(cqt_ctx *c, const double *x, long L, double *cells) {
     const long off = (long)c->first_center - c->lin_N / 2;
     k_cqt_linear<<<g.W, 256, c->lin_N * sizeof(double2), s>>>(
         c->xp.p, g.Lp, off, c->lwin.p, c->ltw_f.p, c->lin_N, c->lin_logN, c->atom_hop, 0, c->kmax,
-        0, c->lin_bins, c->sp.p);
+        0, c->lin_bins, c->sp.p, 0, 0);
     FASST_LAUNCH_CHECK();
     k_cqt_transpose<<<dim3((c->lin_bins + 15) / 16, (g.W + 15) / 16), 256, 0, s>>>(
         c->sp.p, c->cells.p + cell_offset(c, g, c->oct), g.W, c->lin_bins);
@@ -1105,7 +1197,7 @@ int cqt_forward_cells(cqt_ctx *c, const double *x, long L, double *cells) {
     if (c->nb > 0) {
       k_cqt_frames<<<nfr, 256, c->N * sizeof(double2), s>>>(cur, g.len[i], c->fft_hop, c->tw_f.p,
                                                            c->N, c->logN, c->kb, c->nb, c->nbp,
-                                                           c->XX.p);
+                                                           c->XX.p, 0, 0);
       FASST_LAUNCH_CHECK();
       k_cqt_band_cells<<<(nfr + kBandFrames - 1) / kBandFrames, 256,
                          kBandFrames * c->nbp * sizeof(double2), s>>>(c->K.p, c->XX.p, c->M, c->nb,
@@ -1118,7 +1210,7 @@ int cqt_forward_cells(cqt_ctx *c, const double *x, long L, double *cells) {
     // so it also filters and decimates after the last octave; nothing reads
     // that signal, and it is not computed here.
     if (i != c->oct - 1) {
-      if ((st = filtfilt(c, cur, g.len[i], 0, next, 1, 1.0))) return st;
+      if ((st = filtfilt(c, s, 1, cur, 0, g.len[i], 0, next, 0, 1, 1.0))) return st;
       cur = next;
       next = (next == c->sa.p) ? c->sb.p : c->sa.p;
     }
@@ -1297,4 +1389,82 @@ int cqt_device_ms(cqt_ctx *c, double *forward_ms, double *inverse_ms) {
   return FASST_OK;
 }
 
+int cqt_batch_info(cqt_ctx *c, int *signals, long *launches) {
+  if (!c) return FASST_ERR_SHAPE;
+  if (signals) *signals = c->signals;
+  if (launches) *launches = c->launches;
+  return FASST_OK;
+}
+
 }  // extern "C"
+
+// ---- the model-resident transform (fasst_cqt_dev.h) -------------------------
+namespace fasst {
+
+int cqt_ctx_device(const cqt_ctx *c) { return c->device; }
+
+int cqt_match_model(cqt_ctx *c, long L, int device, int F, int T, const char *fn) {
+  if (!c) return FASST_ERR_SHAPE;
+  if (c->device != device) {
+    set_error("%s: transform context on device %d, model on device %d", fn, c->device, device);
+    return FASST_ERR_SHAPE;
+  }
+  Geo g;
+  int st = geometry(c, L, g);
+  if (st) return st;
+  if (g.F != F || g.W != T) {
+    set_error("%s: the transform of %ld samples is %dx%d, the model %dx%d", fn, L, g.F, g.W, F, T);
+    return FASST_ERR_SHAPE;
+  }
+  return FASST_OK;
+}
+
+int cqt_forward_pair(cqt_ctx *c, hipStream_t s, const double *data, long L, double2 *X, int ld,
+                     size_t plane) {
+  Geo g;
+  int st = geometry(c, L, g);
+  if (st) return st;
+  if (ld < g.F || plane < (size_t)g.W * ld) {
+    set_error("cqt_forward_pair: planes of pitch %d too small for %dx%d", ld, g.F, g.W);
+    return FASST_ERR_SHAPE;
+  }
+  if ((st = ensure_work(c, g, L, 2))) return st;
+  std::vector<double> chans((size_t)2 * L);
+  for (long i = 0; i < L; ++i) {
+    chans[i] = data[(size_t)i * 2];
+    chans[(size_t)L + i] = data[(size_t)i * 2 + 1];
+  }
+  FASST_HIP(hipMemsetAsync(c->xp.p, 0, 2 * c->n_xp * sizeof(double), s));
+  for (int ch = 0; ch < 2; ++ch)
+    FASST_HIP(hipMemcpyAsync(c->xp.p + ch * c->n_xp + g.maxBlock, chans.data() + (size_t)ch * L,
+                             L * sizeof(double), hipMemcpyHostToDevice, s));
+  FASST_HIP(hipStreamSynchronize(s));   // chans is read until here
+  FASST_HIP(hipEventRecord(c->ev[0], s));
+  if ((st = forward_dev(c, g, s, 2, X, ld, plane))) return st;
+  FASST_HIP(hipEventRecord(c->ev[1], s));
+  FASST_HIP(hipStreamSynchronize(s));
+  FASST_HIP(hipEventElapsedTime(&c->ms_fwd, c->ev[0], c->ev[1]));
+  return FASST_OK;
+}
+
+int cqt_inverse_batch(cqt_ctx *c, hipStream_t s, const CqtImages &im, int B, long L, double *y) {
+  Geo g;
+  int st = geometry(c, L, g);
+  if (st) return st;
+  if (B < 1 || B > 65535 || im.ld < g.F) {
+    set_error("cqt_inverse_batch: %d images of pitch %d for %d bins", B, im.ld, g.F);
+    return FASST_ERR_SHAPE;
+  }
+  if ((st = ensure_work(c, g, L, B))) return st;
+  FASST_HIP(hipEventRecord(c->ev[2], s));
+  double *yout = nullptr;
+  if ((st = inverse_dev(c, g, L, nullptr, s, &yout, im, B))) return st;
+  FASST_HIP(hipEventRecord(c->ev[3], s));
+  FASST_HIP(hipMemcpy2DAsync(y, L * sizeof(double), yout, c->n_y * sizeof(double),
+                             L * sizeof(double), B, hipMemcpyDeviceToHost, s));
+  FASST_HIP(hipStreamSynchronize(s));
+  FASST_HIP(hipEventElapsedTime(&c->ms_inv, c->ev[2], c->ev[3]));
+  return FASST_OK;
+}
+
+}  // namespace fasst

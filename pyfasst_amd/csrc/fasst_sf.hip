@@ -18,7 +18,9 @@
 //             from factor to factor as the reference does)
 // Every reduction has a fixed order: two runs are bit-equal.
 #include "fasst_sf.h"
+#include "fasst_cqt_dev.h"
 #include "fasst_fft.h"
+#include "../../include/fasst_cqt.h"
 #include "fasst_gemm.h"
 
 #include <algorithm>
@@ -791,6 +793,35 @@ int fasst_sf_separate_waveforms(fasst_ctx *c, const double *psd, int nsrc, const
   FASST_HIP(hipMemcpyAsync(y, dy.p, dy.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
+}
+
+// fasst_sf_separate_waveforms for a model on a CQT / MinQT (include/fasst_cqt.h):
+// the 2 nsrc images stay in HBM and go through one batched inverse chain
+int fasst_sf_separate_waveforms_cqt(fasst_ctx *c, cqt_ctx *q, const double *psd, int nsrc,
+                                    const int *src_of, long L, double *y) {
+  int st = need_sf(c, 0);
+  if (st) return st;
+  if (!q || !psd || !y) return FASST_ERR_SHAPE;
+  if ((st = sf_check_sources(c, nsrc, src_of))) return st;
+  if ((st = cqt_match_model(q, L, c->device, c->F, c->T, "fasst_sf_separate_waveforms_cqt")))
+    return st;
+  if (!c->have_X) {
+    set_error("fasst_sf_separate_waveforms_cqt: no transform resident (set_audio_cqt / set_stft)");
+    return FASST_ERR_SHAPE;
+  }
+  DeviceGuard g(c->device);
+  const size_t plane = (size_t)c->Tp * c->Fp;
+  DBuf<double> dpsd;
+  DBuf<double2> dS;
+  if ((st = dpsd.alloc_uninit(c->F)) || (st = dS.alloc((size_t)nsrc * 2 * plane))) return st;
+  FASST_HIP(hipMemcpyAsync(dpsd.p, psd, c->F * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if ((st = sf_all_powers(c))) return st;
+  if ((st = sf_launch_wiener(c, dpsd.p, nsrc, src_of, dS.p, plane, 1, (size_t)c->Fp))) return st;
+  CqtImages im;
+  im.S = dS.p;
+  im.plane = plane;
+  im.ld = c->Fp;
+  return cqt_inverse_batch(q, c->stream, im, 2 * nsrc, L, y);
 }
 
 }  // extern "C"

@@ -9,7 +9,9 @@
 //   k_wiener<J>     Sigma_n = R_n V_n, Sigma_x^-1, WG_n = Sigma_n Sigma_x^-1,
 //                   S_n = WG_n X  (audioModel.py:1327-1467, :1205-1214)
 #include "fasst_ctx.h"
+#include "fasst_cqt_dev.h"
 #include "fasst_fft.h"
+#include "../../include/fasst_cqt.h"
 
 #include <cmath>
 
@@ -542,11 +544,8 @@ __global__ void k_spatial_gain(const double2 *__restrict__ A, const int *__restr
   }
 }
 
-// one row of a 2x2 gain applied to the two channels: g0 x0 + g1 x1 (:1026-1029)
-__device__ __forceinline__ double2 gain_apply(double2 g0, double2 g1, double2 x0, double2 x1) {
-  return make_double2(g0.x * x0.x - g0.y * x0.y + (g1.x * x1.x - g1.y * x1.y),
-                      g0.x * x0.y + g0.y * x0.x + (g1.x * x1.y + g1.y * x1.x));
-}
+// one row of a 2x2 gain applied to the two channels, g0 x0 + g1 x1
+// (:1026-1029): gain_apply, fasst_cqt_dev.h
 
 // STFT-domain images S [J][2][Tp][Fp] = G_n X: X streamed once, G from cache
 __global__ void k_spatial_images(const double2 *__restrict__ X, const double2 *__restrict__ G,
@@ -1280,6 +1279,93 @@ int fasst_inv_herm_mat_2d(int device, int n, const double *diag, const double *o
   FASST_HIP(hipMemcpy(inv_off, dioff.p, (size_t)n * sizeof(double2), hipMemcpyDeviceToHost));
   FASST_HIP(hipMemcpy(det, ddet.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   return FASST_OK;
+}
+
+}  // extern "C"
+
+// ---- CQT / MinQT models: observation and separation on the device ----------
+// (include/fasst_cqt.h; the batched transform chains are in fasst_cqt.hip)
+extern "C" {
+
+int fasst_set_audio_cqt(fasst_ctx *c, cqt_ctx *q, const double *data, long L) {
+  if (!c || !q || !data) return FASST_ERR_SHAPE;
+  int st = cqt_match_model(q, L, c->device, c->F, c->T, "fasst_set_audio_cqt");
+  if (st) return st;
+  DeviceGuard g(c->device);
+  if (!c->X.p && (st = c->X.alloc((size_t)2 * c->Tp * c->Fp))) return st;
+  const size_t plane = (size_t)c->Tp * c->Fp;
+  // the observation is replaced: not valid again before the transform is in
+  c->have_X = false;
+  c->cx_ready = false;
+  FASST_HIP(hipMemsetAsync(c->X.p, 0, c->X.n * sizeof(double2), c->stream));
+  if ((st = cqt_forward_pair(q, c->stream, data, L, c->X.p, c->Fp, plane))) return st;
+  k_cx_from_X<<<2048, 256, 0, c->stream>>>(c->X.p, c->cx.p, plane);
+  FASST_LAUNCH_CHECK();
+  FASST_HIP(hipStreamSynchronize(c->stream));
+  c->have_X = true;
+  c->cx_ready = true;
+  return FASST_OK;
+}
+
+int fasst_separate_waveforms_cqt(fasst_ctx *c, cqt_ctx *q, const double *psd, long L, double *y) {
+  if (!c || !c->configured || !q || !psd || !y) {
+    set_error("fasst_separate_waveforms_cqt: context not configured");
+    return FASST_ERR_SHAPE;
+  }
+  int st = cqt_match_model(q, L, c->device, c->F, c->T, "fasst_separate_waveforms_cqt");
+  if (st) return st;
+  if (!c->have_X) {
+    set_error("fasst_separate_waveforms_cqt: no transform resident (set_audio_cqt / set_stft)");
+    return FASST_ERR_SHAPE;
+  }
+  DeviceGuard g(c->device);
+  const int J = c->J, NS = c->nsrc > 0 ? c->nsrc : J;
+  const size_t plane = (size_t)c->Tp * c->Fp;
+  DBuf<double> dpsd, coef;
+  DBuf<int> droff;
+  DBuf<double2> dS;
+  if ((st = dpsd.alloc(c->Fp)) || (st = coef.alloc((size_t)J * 4 * c->Fp)) ||
+      (st = droff.alloc(kMaxJ + 1)) || (st = dS.alloc((size_t)NS * 2 * plane)))
+    return st;
+  FASST_HIP(hipMemcpyAsync(dpsd.p, psd, c->F * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  FASST_HIP(hipMemcpyAsync(droff.p, c->roff, (J + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if ((st = build_inst_A(c))) return st;
+  if ((st = launch_w_old(c))) return st;
+  k_mixcoef<<<(c->Fp + 255) / 256, 256, 0, c->stream>>>(c->A.p, coef.p, J, droff.p, c->F, c->Fp);
+  FASST_LAUNCH_CHECK();
+  if ((st = launch_wiener(c, coef.p, dpsd.p, dS.p))) return st;
+  // image q = (source, channel) is a [Tp][Fp] plane: the frame-major raster the
+  // inverse reads, with the model's row pitch; all 2 NS go through one chain
+  CqtImages im;
+  im.S = dS.p;
+  im.plane = plane;
+  im.ld = c->Fp;
+  return cqt_inverse_batch(q, c->stream, im, 2 * NS, L, y);
+}
+
+int fasst_spatial_filter_waveforms_cqt(fasst_ctx *c, cqt_ctx *q, long L, double *y) {
+  int st = need_conv_model(c, "fasst_spatial_filter_waveforms_cqt");
+  if (st) return st;
+  if (!q || !y) return FASST_ERR_SHAPE;
+  if ((st = cqt_match_model(q, L, c->device, c->F, c->T, "fasst_spatial_filter_waveforms_cqt")))
+    return st;
+  if (!c->have_X) {
+    set_error("fasst_spatial_filter_waveforms_cqt: no transform resident (set_audio_cqt / set_stft)");
+    return FASST_ERR_SHAPE;
+  }
+  DeviceGuard g(c->device);
+  DBuf<int> droff;
+  DBuf<double2> G;
+  if ((st = spatial_gains(c, droff, G))) return st;
+  // the gains are applied as the inverse gathers its cells from the resident
+  // channel transforms: no image array exists
+  CqtImages im;
+  im.S = c->X.p;
+  im.plane = (size_t)c->Tp * c->Fp;
+  im.ld = c->Fp;
+  im.G = G.p;
+  im.gp = c->Fp;
+  return cqt_inverse_batch(q, c->stream, im, 2 * c->J, L, y);
 }
 
 }  // extern "C"

@@ -372,6 +372,40 @@ class Engine(object):
               "fasst_spatial_filter_waveforms")
         return out
 
+    # ------------------------------------------------------------ CQT / MinQT models
+    # cqt: the handle of a rasterised transform context (CQTransfo._context())
+    # on this engine's device; L: the signal length it transforms to F x T
+    def set_audio_cqt(self, cqt, data):
+        """Both channel transforms straight into the resident observation."""
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        if data.ndim != 2 or data.shape[1] != 2:
+            raise ValueError("stereo samples [L, 2] expected, got %s" % (data.shape,))
+        check(lib.fasst_set_audio_cqt(self._h, cqt, dptr(data), data.shape[0]),
+              "fasst_set_audio_cqt")
+
+    def separate_waveforms_cqt(self, cqt, psd, L):
+        """Wiener images + one batched inverse transform: [nsrc, 2, L] float64."""
+        psd = np.ascontiguousarray(psd, dtype=np.float64)
+        out = np.empty((self._nsrc(), 2, max(int(L), 0)))
+        check(lib.fasst_separate_waveforms_cqt(self._h, cqt, dptr(psd), int(L), dptr(out)),
+              "fasst_separate_waveforms_cqt")
+        return out
+
+    def sf_separate_waveforms_cqt(self, cqt, psd, src_of, L):
+        psd = np.ascontiguousarray(psd, dtype=np.float64)
+        s, n = self._src_of(src_of)
+        out = np.empty((n, 2, max(int(L), 0)))
+        check(lib.fasst_sf_separate_waveforms_cqt(self._h, cqt, dptr(psd), n, iptr(s), int(L),
+                                                  dptr(out)), "fasst_sf_separate_waveforms_cqt")
+        return out
+
+    def spatial_filter_waveforms_cqt(self, cqt, L):
+        """Gain on load + one batched inverse transform: [J, 2, L] float64."""
+        out = np.empty((len(self.structure[0]), 2, max(int(L), 0)))
+        check(lib.fasst_spatial_filter_waveforms_cqt(self._h, cqt, int(L), dptr(out)),
+              "fasst_spatial_filter_waveforms_cqt")
+        return out
+
     def gcc_phat(self, nfft):
         """irfft(Cx01 / |Cx01|, n=nfft, axis=0) of the observation: [nfft, T]."""
         out = np.empty((int(nfft), self.T))

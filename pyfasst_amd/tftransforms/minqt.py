@@ -234,16 +234,43 @@ class CQTransfo(object):
         if not self.perfRast:
             return self._compute_cells(data)
         x = np.ascontiguousarray(np.asarray(data, dtype=np.float64).ravel())
-        k = self.cqtkernel
-        self.datalen_init = x.shape[0]
-        self.maxBlock = int(k.FFTLen * (2 ** (self.octaveNr - 1)))
-        self.suffixZeros = self.maxBlock
-        self.prefixZeros = self.maxBlock
-        F, W, nfr = self._shape(x.size)
-        self.nframes = [np.float64(n) for n in nfr]
+        F, W = self._bookkeeping(x.size)
         sp = np.empty((F, W), dtype=np.complex128)
         check(lib.cqt_forward(self._context(), dptr(x), x.size, dptr(sp)), "cqt_forward")
         self._spCQT = sp
+
+    def _bookkeeping(self, L):
+        """The attributes computeCQT leaves for a signal of L samples
+        (minqt.py:523-556), without the transform; returns (freqbins, width)."""
+        k = self.cqtkernel
+        F, W, nfr = self._shape(int(L))
+        self.datalen_init = int(L)
+        self.maxBlock = int(k.FFTLen * (2 ** (self.octaveNr - 1)))
+        self.suffixZeros = self.maxBlock
+        self.prefixZeros = self.maxBlock
+        self.nframes = [np.float64(n) for n in nfr]
+        return F, W
+
+    def prepare_resident(self, L):
+        """State as after computeTransform() of a signal of L samples whose
+        transform stays on the device (FASST.comp_transf_Cx): the frame
+        bookkeeping is set, no host copy of the transform exists.  Returns
+        (freqbins, width).  Needs perfRast=1."""
+        if not self.perfRast:
+            raise NotImplementedError("the device-resident transform is the rasterised one")
+        F, W = self._shape(int(L))[:2]    # raises before any attribute moves
+        for attr in ('_spCQT', 'cellCQT'):
+            if hasattr(self, attr):
+                delattr(self, attr)
+        return self._bookkeeping(L)
+
+    def batch_info(self):
+        """(signals, kernel launches) of the last forward / inverse chain on
+        this transform's device context (cqt_batch_info)."""
+        n, k = ctypes.c_int(0), ctypes.c_long(0)
+        check(lib.cqt_batch_info(self._context(), ctypes.byref(n), ctypes.byref(k)),
+              "cqt_batch_info")
+        return n.value, k.value
 
     # ------------------------------------------------------ perfRast=0 cells
     def _cell_layout(self):
@@ -462,6 +489,11 @@ class MinQTransfo(CQTransfo):
         """CQT part and linear part in one GPU pass (minqt.py:1404-1450)."""
         super(MinQTransfo, self).computeTransform(data)
         self.offsetSTFT = self.cqtkernel.first_center
+
+    def prepare_resident(self, L):
+        out = super(MinQTransfo, self).prepare_resident(L)
+        self.offsetSTFT = self.cqtkernel.first_center
+        return out
 
     def computeLinearPart(self, data):
         """cellCQT['linear'] of data (minqt.py:1410-1435).  computeTransform

@@ -12,6 +12,9 @@
   --workload wf0    SIMM source dictionary generate_WF0_TR_chirped at config
                     5 (44.1 kHz, NFT 4096, 1092 KLGLOTT88 combs, STFT middle
                     frame): device time per dictionary
+  --workload separate_cqt  separation and front end of a MinQT model at the C3
+                    clip length: the device-resident calls against the
+                    host-side route they replace (profiles/cqt_resident_bench.jsonl)
   --workload spatial  the time-invariant spatial filter at C3
                     (separate_spatial_filter_comp, audioModel.py:891-1061):
                     per-bin gains + the 2 J iSTFTs with the gain applied on
@@ -165,6 +168,117 @@ def bench_separate(steps, warmup):
             "images_path_ms": round(di * 1e3, 3), "image_bytes_to_host": int(S.nbytes),
             "front_end_ms": round(ds * 1e3, 3), "front_end": "fasst_set_audio: %d x 2 samples -> "
             "resident STFTs + Cx, host-inclusive" % L}
+
+
+def bench_separate_cqt(steps, warmup, fs=44100, wlen=4096, hop=512, T=10000, J=4, K=32, seed=0):
+    """Separation of a MinQT model at the length of the `separate` workload's
+    C3 clip: the device-resident call (fasst_separate_waveforms_cqt: the 2 J
+    images stay in HBM and go through one batched inverse) against the route
+    it replaces (fasst_wiener_images to the host, then 2 J cqt_inverse calls),
+    in one session, host-inclusive; beside them the device time of the inverse
+    chains (cqt_device_ms) and the same pair for the front end
+    (fasst_set_audio_cqt against 2 cqt_forward + fasst_set_stft)."""
+    from pyfasst_amd import _lib
+    from pyfasst_amd.engine import Engine
+    from pyfasst_amd.tftransforms import minqt
+    L = hop * (T - 2)
+    rs = np.random.RandomState(seed)
+    x = rs.randn(L, 2) * (1 + np.sin(np.arange(L) / 7000.0))[:, None]
+    x[:, 1] = 0.6 * x[:, 1] + 0.4 * np.roll(x[:, 0], 5)
+    t = minqt.MinQTransfo(fmin=25, fmax=18000, bins=48, fs=fs, perfRast=1, linFTLen=wlen,
+                          atomHopFactor=hop / float(wlen))
+    cqt = t._context()
+    F, W = t.prepare_resident(L)
+    eng = Engine(F, W)
+
+    def dev_ms():
+        f, b = ctypes.c_double(), ctypes.c_double()
+        _lib.check(_lib.lib.cqt_device_ms(cqt, ctypes.byref(f), ctypes.byref(b)), "ms")
+        return f.value, b.value
+
+    def timed(fn):
+        """(median wall ms, median of fn's own return value) over the steps"""
+        wall, own = [], []
+        for i in range(warmup + steps):
+            t0 = time.perf_counter()
+            r = fn()
+            dt = time.perf_counter() - t0
+            if i >= warmup:
+                wall.append(dt * 1e3)
+                own.append(r)
+        return float(np.median(wall)), float(np.median(own))
+
+    # ---- front end
+    def front_new():
+        eng.set_audio_cqt(cqt, x)
+        return dev_ms()[0]
+
+    def front_old():
+        X, ms = [], 0.0
+        for c in range(2):
+            t.computeTransform(x[:, c])
+            ms += dev_ms()[0]
+            X.append(t.transfo)
+        eng.set_stft(np.array(X))
+        return ms
+    fo_wall, fo_dev = timed(front_old)
+    cx_old = eng.get_cx()
+    fn_wall, fn_dev = timed(front_new)
+    front_equal = bool(np.array_equal(cx_old, eng.get_cx()))
+    del cx_old
+    fwd_info = t.batch_info()
+
+    # ---- the model: J 'conv' components of rank 2, K NMF components each
+    eng.configure([2] * J, [K] * J, True)
+    for j in range(J):
+        eng.set_spatial(j, rs.randn(2, 2, F) + 1j * rs.randn(2, 2, F), False)
+        eng.set_spectral(j, rs.gamma(1.0, 1.0, (F, K)), np.eye(K), rs.gamma(1.0, 1.0, (K, W)),
+                         True, True)
+    eng.set_sources(None)
+    psd = np.full(F, 1e-6)
+    keep = {}
+
+    def sep_new():
+        keep['new'] = eng.separate_waveforms_cqt(cqt, psd, L)
+        return dev_ms()[1]
+
+    def sep_old():
+        S = eng.wiener_images(psd)
+        Y, ms = np.empty((J, 2, L)), 0.0
+        for n in range(J):
+            for c in range(2):
+                t.transfo = S[n, c]
+                Y[n, c] = t.invertTransform()
+                ms += dev_ms()[1]
+                del t.transfo
+        keep['old'], keep['image_bytes'] = Y, int(S.nbytes)
+        return ms
+    so_wall, so_dev = timed(sep_old)
+    sn_wall, sn_dev = timed(sep_new)
+    inv_info = t.batch_info()
+    err = float(np.max(np.abs(keep['new'] - keep['old'])) / np.max(np.abs(keep['old'])))
+    return {"metric": "MinQT model separation (Wiener images + inverse MinQT) per clip, "
+                      "host-inclusive",
+            "value": round(sn_wall, 3), "unit": "ms", "higher_is_better": False,
+            "steps": steps, "warmup": warmup, "dtype": "f64",
+            "data": "synthetic modulated stereo noise, random 'conv' model, RandomState(0)",
+            "config": {"workload": "MinQT fs=%d linFTLen=%d hop=%d bins=48 fmin=25: %d samples, "
+                                   "spCQT %dx%d, %d octaves; J=%d sources x 2 channels, K=%d"
+                                   % (fs, wlen, hop, L, F, W, int(t.octaveNr), J, K)},
+            "old_route_ms": round(so_wall, 3),
+            "old_route": "fasst_wiener_images + %d x cqt_inverse, host-inclusive" % (2 * J),
+            "speedup_vs_old_route": round(so_wall / sn_wall, 2),
+            "inverse_device_ms": {"batched": round(sn_dev, 3),
+                                  "singles_sum": round(so_dev, 3),
+                                  "signals": inv_info[0], "launches": inv_info[1]},
+            "waveform_bytes_to_host": int(keep['new'].nbytes),
+            "image_bytes_to_host_old_route": keep['image_bytes'],
+            "rel_diff_vs_old_route": err,
+            "front_end_ms": round(fn_wall, 3), "front_end_old_route_ms": round(fo_wall, 3),
+            "front_end_old_route": "2 x cqt_forward to the host + fasst_set_stft, host-inclusive",
+            "front_end_device_ms": {"batched": round(fn_dev, 3), "singles_sum": round(fo_dev, 3),
+                                    "signals": fwd_info[0], "launches": fwd_info[1]},
+            "front_end_cx_bit_equal": front_equal}
 
 
 def bench_spatial(steps, warmup):
@@ -641,7 +755,8 @@ def bench_sigtools(steps, warmup, F=2049, N=10000, seed=0):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=("simm", "nmf", "cqt", "viterbi", "wf0", "separate",
-                                           "nnls", "spatial", "hmm", "sf", "sfnmf", "sigtools"),
+                                           "nnls", "spatial", "hmm", "sf", "sfnmf", "sigtools",
+                                           "separate_cqt"),
                     required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -653,7 +768,8 @@ def main():
     fn = {"simm": bench_simm, "nmf": bench_nmf, "cqt": bench_cqt, "viterbi": bench_viterbi,
           "wf0": bench_wf0, "separate": bench_separate, "nnls": bench_nnls,
           "spatial": bench_spatial, "hmm": bench_hmm, "sf": bench_sf,
-          "sfnmf": bench_sfnmf, "sigtools": bench_sigtools}[a.workload]
+          "sfnmf": bench_sfnmf, "sigtools": bench_sigtools,
+          "separate_cqt": bench_separate_cqt}[a.workload]
     out = fn(a.steps, a.warmup)
     if NO_CPU:
         out["cpu_baseline"] = None   # not measured (the sample above timed nothing)
