@@ -1,6 +1,7 @@
 """ctypes binding of libfasst_hip.so (declared in include/fasst_hip.h,
 include/fasst_simm.h, include/fasst_nmf.h, include/fasst_cqt.h,
-include/fasst_viterbi.h, include/fasst_dict.h and include/fasst_sigtools.h).
+include/fasst_viterbi.h, include/fasst_dict.h, include/fasst_sigtools.h and
+include/fasst_filter.h).
 
 The product path has no CPU fallback: if the HIP library is missing this
 module raises at import time, and every compute call raises if the device
@@ -82,6 +83,15 @@ SIGNATURES = {
                                    ctypes.c_int, ctypes.c_int, _dp]),
     "fasst_istft_simm": (ctypes.c_int, [ctypes.c_int, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int, _dp]),
+    # include/fasst_filter.h
+    "fasst_filter_stft": (ctypes.c_int, [ctypes.c_int, _dp] + [ctypes.c_int] * 3 +
+                          [_dp, ctypes.c_int, ctypes.c_int, _dp, _dp] + [ctypes.c_int] * 3 +
+                          [_dp, _ip]),
+    "fasst_filter_stft_dev": (ctypes.c_int, [ctypes.c_int, _dp] + [ctypes.c_int] * 3 +
+                              [_dp, ctypes.c_int, ctypes.c_int, _dp, _dp] + [ctypes.c_int] * 3 +
+                              [_dp, _ip, ctypes.c_int, _vp]),
+    "fasst_filter_set_timing": (ctypes.c_int, [ctypes.c_int]),
+    "fasst_filter_last_ms": (ctypes.c_int, [_dp, _dp]),
     "fasst_set_profiling": (ctypes.c_int, [_vp, ctypes.c_int]),
     "fasst_kernel_times": (ctypes.c_int, [_vp, _dp, ctypes.POINTER(ctypes.c_long), ctypes.c_int]),
     "fasst_kernel_name": (ctypes.c_char_p, [ctypes.c_int]),

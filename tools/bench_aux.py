@@ -752,11 +752,96 @@ def bench_sigtools(steps, warmup, F=2049, N=10000, seed=0):
                                        "(cases[*].cpu_restatement_ms)"}}
 
 
+def bench_filter(steps, warmup, M=2, L=5120000, wlen=4096, hop=512, seed=0):
+    """filter_stft at the C3 clip (2 channels, 5.12 M samples, wlen = nfft =
+    4096, hop 512: 10000 frames), time-invariant and time-varying W, against
+    the route it replaces: stft() per channel, a host product, istft() per
+    channel."""
+    import ctypes
+    from pyfasst_amd import _lib
+    from pyfasst_amd.tftransforms.stft import filter_stft, istft, stft
+    rs = np.random.RandomState(seed)
+    F, N = wlen // 2 + 1, -(-L // hop)
+    x = rs.randn(L, M)
+    sw = np.sin(np.pi * np.arange(wlen) / (1.0 * wlen))
+    aw = np.hanning(wlen) + 0.1
+    kw = dict(analysisWindow=aw, synthWindow=sw, hopsize=float(hop), nfft=float(wlen))
+    rows = (N - 1) * hop + wlen - wlen // 2
+
+    _lib.lib.fasst_filter_set_timing(1)
+
+    def last_ms():
+        tot, tr = ctypes.c_double(0), ctypes.c_double(0)
+        _lib.lib.fasst_filter_last_ms(ctypes.byref(tot), ctypes.byref(tr))
+        return tot.value, tr.value
+
+    def replaced(W):
+        X = np.array([stft(x[:, c], window=aw, hopsize=hop, nfft=wlen)[0] for c in range(M)])
+        Wn = W[..., :X.shape[2]] if W.ndim == 4 else W[..., None]
+        Y = np.einsum('ocfn,cfn->ofn', Wn, X)
+        return np.stack([istft(Y[c], window=sw, analysisWindow=aw, hopsize=hop, nfft=wlen)
+                         for c in range(M)], axis=1)
+
+    cases = []
+    for tv in (False, True):
+        # the replaced route frames with ceil(L/hop) + 2 frames: W covers them
+        shape = (M, M, F) + ((N + 2,) if tv else ())
+        W = np.empty(shape, dtype=np.complex128)
+        W.real = rs.randn(*shape)
+        W.imag = rs.randn(*shape)
+        for _ in range(warmup):
+            filter_stft(x, W, **kw)
+        dev, tr, wall = [], [], []
+        for _ in range(steps):
+            t0 = time.perf_counter()
+            filter_stft(x, W, **kw)
+            wall.append(time.perf_counter() - t0)
+            a, b = last_ms()
+            dev.append(a)
+            tr.append(b)
+        t1 = time.perf_counter()
+        replaced(W)
+        old_s = time.perf_counter() - t1
+        t1 = time.perf_counter()
+        replaced(W)
+        old_s = min(old_s, time.perf_counter() - t1)
+        w_bytes = 16 * W.size
+        nbytes = (w_bytes * (3 if tv else 1) + 2 * 8 * M * N * wlen + 8 * M * L + 8 * M * rows)
+        dev_ms = float(np.median(dev))
+        gbs = nbytes / (dev_ms * 1e-3) / 1e9
+        cases.append({"case": "filter_stft M=%d L=%d wlen=nfft=%d hop=%d (%d frames), W %s"
+                              % (M, L, wlen, hop, N, "time-varying" if tv else "time-invariant"),
+                      "device_ms": round(dev_ms, 3),
+                      "of_which_w_transpose_ms": round(float(np.median(tr)), 3),
+                      "host_inclusive_ms": round(float(np.median(wall)) * 1e3, 1),
+                      "replaced_route_host_inclusive_ms": round(old_s * 1e3, 1),
+                      "w_bytes": int(w_bytes), "hbm_bytes": int(nbytes),
+                      "hbm_gb_per_s": round(gbs, 1),
+                      "frac_of_measured_copy_6290": round(gbs / 6290., 4),
+                      "bytes_counted": "W read once%s, frames written and read (2*8*M*N*wlen), "
+                                       "data read, output written"
+                                       % (" plus the transpose's read and write" if tv else "")})
+        del W
+    return {"metric": "filter_stft device ms (time-invariant W)", "value": cases[0]["device_ms"],
+            "unit": "ms", "ms_per_step": cases[0]["device_ms"], "steps": steps, "warmup": warmup,
+            "dtype": "f64", "data": "synthetic, RandomState(0)",
+            "config": {"workload": "filter_stft, C3 clip", "M": M, "L": L, "wlen": wlen, "hop": hop},
+            "cases": cases,
+            "roofline": {"bound": "hbm", "achieved": cases[0]["hbm_gb_per_s"], "peak": 6290.,
+                         "unit": "GB/s", "frac": cases[0]["frac_of_measured_copy_6290"],
+                         "traffic": cases[0]["hbm_bytes"],
+                         "scope": "transpose + k_filter_frames + k_ola_ch, device events"},
+            "cpu_baseline": {"value": cases[0]["replaced_route_host_inclusive_ms"], "unit": "ms",
+                             "cores": _blas_threads(), "kind": "replaced route",
+                             "sample": "stft() per channel on the GPU, NumPy product on the host, "
+                                       "istft() per channel on the GPU, best of two"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=("simm", "nmf", "cqt", "viterbi", "wf0", "separate",
                                            "nnls", "spatial", "hmm", "sf", "sfnmf", "sigtools",
-                                           "separate_cqt"),
+                                           "separate_cqt", "filter"),
                     required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -769,7 +854,7 @@ def main():
           "wf0": bench_wf0, "separate": bench_separate, "nnls": bench_nnls,
           "spatial": bench_spatial, "hmm": bench_hmm, "sf": bench_sf,
           "sfnmf": bench_sfnmf, "sigtools": bench_sigtools,
-          "separate_cqt": bench_separate_cqt}[a.workload]
+          "separate_cqt": bench_separate_cqt, "filter": bench_filter}[a.workload]
     out = fn(a.steps, a.warmup)
     if NO_CPU:
         out["cpu_baseline"] = None   # not measured (the sample above timed nothing)
