@@ -48,8 +48,9 @@ typedef struct fasst_ctx fasst_ctx;
  * (fasst_set_tw_constr / fasst_get_tw_constr).  Revision 5 adds the two-factor
  * (source / filter) spectral components (fasst_sf_* and fasst_set_factors /
  * fasst_get_factors).  Revision 6 adds fasst_estep_partition.  Revision 7 adds
- * the source / filter IS-NMF (sfnmf_*, fasst_nmf.h). */
-#define FASST_ABI_VERSION 7
+ * the source / filter IS-NMF (sfnmf_*, fasst_nmf.h).  Revision 8 adds the
+ * stereo accompaniment IS-NMF (snmf_*, fasst_simm.h). */
+#define FASST_ABI_VERSION 8
 int fasst_abi_version(void);
 
 /* The E-step's balanced schedule, host arithmetic only (no device call;

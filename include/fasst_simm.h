@@ -75,6 +75,31 @@ int simm_get_params(simm_ctx *ctx, double *HGAMMA, double *HPHI, double *HF0, do
  * (FASST_SIMM_GEMM=2); either pointer may be NULL */
 int simm_nf0_product_counts(long *dgemm2_launches, long *kgemm_launches);
 
+/*
+ * stereo_NMF (SIMM.py:945-1104): the accompaniment model on its own,
+ *   SXR ~ WM diag(betaR^2) HM,  SXL ~ WM diag(betaL^2) HM,  betaL = 1 - betaR,
+ * a stereo Itakura-Saito NMF with one panning gain per component.  The
+ * initial draw stays on the host (pyfasst_amd/SeparateLeadStereo/SIMM/SIMM.py
+ * stereo_NMF); the loop body (:1009-1102) runs on the device with no model
+ * plane stored (pyfasst_amd/csrc/fasst_snmf.hip).
+ *   SXR, SXL [F][N], WM [F][R], HM [R][N], betaR / betaL [R] (the diagonals)
+ */
+typedef struct snmf_ctx snmf_ctx;
+
+/* 1 <= R <= 128, else FASST_ERR_UNSUPPORTED */
+int snmf_create(int device, int F, int N, int R, snmf_ctx **out);
+int snmf_destroy(snmf_ctx *ctx);
+int snmf_set_data(snmf_ctx *ctx, const double *SXR, const double *SXL);
+/* initial parameters (SIMM.py:968-991); betaL = 1 - betaR */
+int snmf_set_params(snmf_ctx *ctx, const double *WM, const double *HM, const double *betaR);
+/* n_iter iterations; omega = updateRulePower.  reco_err (may be NULL):
+ * [3 * n_iter + 1], ISDistortion(SXR, hatSXR) + ISDistortion(SXL, hatSXL)
+ * before the loop and after the HM, WM and beta step of each iteration
+ * (:1001, :1036, :1065, :1095), computed on the device only when asked for */
+int snmf_run(snmf_ctx *ctx, int n_iter, double omega, double *reco_err);
+/* current parameters; any pointer may be NULL */
+int snmf_get_params(snmf_ctx *ctx, double *WM, double *HM, double *betaR, double *betaL);
+
 #ifdef __cplusplus
 }
 #endif

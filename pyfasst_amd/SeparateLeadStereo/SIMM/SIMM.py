@@ -10,6 +10,9 @@ fallback: without the HIP library the import fails.
 
 Display options (displayEvolution, makeMovie, imageCanvas, progressBar) are
 accepted and ignored: they only draw figures in the reference.
+
+`stereo_NMF` (SIMM.py:945-1104), the accompaniment model on its own, runs in
+the same library (snmf_*, csrc/fasst_snmf.hip); its displayEvolution raises.
 """
 import ctypes
 
@@ -18,7 +21,7 @@ from numpy.random import randn
 
 from ... import _lib
 
-__all__ = ["db", "ISDistortion", "SIMM", "Stereo_SIMM"]
+__all__ = ["db", "ISDistortion", "SIMM", "Stereo_SIMM", "stereo_NMF"]
 
 
 def db(positiveValue):
@@ -175,3 +178,83 @@ def Stereo_SIMM(SXR, SXL, WF0, WGAMMA, numberOfFilters=4,
         [SXR, SXL], WF0, WGAMMA, K, R, (HGAMMA, HPHI, HF0, HM, WM), alpha, betaR,
         numberOfIterations, updateRulePower, updateHGAMMA, computeError, dev)
     return (a[0], a[1], HGAMMA, HPHI, HF0, np.diag(bR), np.diag(bL), HM, WM, recoError)
+
+
+STEREO_NMF_MAX_R = 128      # include/fasst_simm.h snmf_create
+
+
+class _SnmfContext(object):
+    def __init__(self, F, N, R, device):
+        self.ptr = ctypes.c_void_p()
+        _lib.check(_lib.lib.snmf_create(device, F, N, R, ctypes.byref(self.ptr)), "snmf_create")
+
+    def __del__(self):
+        if getattr(self, "ptr", None) is not None and self.ptr.value:
+            _lib.lib.snmf_destroy(self.ptr)
+            self.ptr = None
+
+
+def _stereo_nmf_run(SXR, SXL, WM, HM, betaR, n_iter, omega, compute_error, device):
+    """The loop of SIMM.py:1009-1102 on the device: (betaR, betaL, HM, WM,
+    recoError) with the betas as vectors; recoError is None unless asked for."""
+    F, N = SXR.shape
+    R = WM.shape[1]
+    ctx = _SnmfContext(F, N, R, device)
+    SXR, SXL, WM, HM, bR = _c(SXR), _c(SXL), _c(WM).copy(), _c(HM).copy(), _c(betaR).copy()
+    _lib.check(_lib.lib.snmf_set_data(ctx.ptr, _lib.dptr(SXR), _lib.dptr(SXL)), "snmf_set_data")
+    _lib.check(_lib.lib.snmf_set_params(ctx.ptr, _lib.dptr(WM), _lib.dptr(HM), _lib.dptr(bR)),
+               "snmf_set_params")
+    recoError = np.zeros(3 * n_iter + 1) if compute_error else None
+    _lib.check(_lib.lib.snmf_run(ctx.ptr, int(n_iter), float(omega),
+                                 _lib.dptr(recoError) if compute_error else None), "snmf_run")
+    bL = np.zeros(R)
+    _lib.check(_lib.lib.snmf_get_params(ctx.ptr, _lib.dptr(WM), _lib.dptr(HM), _lib.dptr(bR),
+                                        _lib.dptr(bL)), "snmf_get_params")
+    return bR, bL, HM, WM, recoError
+
+
+def stereo_NMF(SXR, SXL, numberOfAccompanimentSpectralShapes, WM0=None, HM0=None,
+               numberOfIterations=50, updateRulePower=1.0, verbose=False,
+               displayEvolution=False, device=None):
+    """Stereo accompaniment IS-NMF (reference SIMM.py:945-1104):
+    SXR ~ WM betaR^2 HM, SXL ~ WM betaL^2 HM, betaL = 1 - betaR.
+
+    Returns (betaR, betaL, HM, WM), the betas as R x R diagonal matrices.
+    HM0, WM0 and betaR are drawn from NumPy's global stream in the
+    reference's order, a matrix only when it is not given (or given with the
+    wrong shape).  The iterations run on the device without a host round
+    trip, so with verbose=True the reference's lines are printed after the
+    run, from the device's error vector, not as the loop goes.
+    displayEvolution=True only draws figures in the reference and raises
+    NotImplementedError here, as does R above 128; neither touches the
+    random stream.
+    """
+    R = numberOfAccompanimentSpectralShapes
+    if displayEvolution:
+        raise NotImplementedError("stereo_NMF: displayEvolution only plots in the reference "
+                                  "(SIMM.py:953-957, :1014-1018) and is not provided")
+    if R > STEREO_NMF_MAX_R:
+        raise NotImplementedError("stereo_NMF: %d accompaniment spectral shapes, the device "
+                                  "engine holds at most %d" % (R, STEREO_NMF_MAX_R))
+    omega = updateRulePower
+    F, N = SXR.shape
+    if (F, N) != SXL.shape:
+        print("The input STFT matrices do not have the same dimension.\n")
+        print("Please check what happened...")
+        raise ValueError("Dimension of STFT matrices must be the same.")
+    HM = _given_or_random(HM0, (R, N), "HM0", verbose)      # SIMM.py:968-977
+    WM = _given_or_random(WM0, (F, R), "WM0", verbose)      # :979-988
+    betaR = np.random.rand(R)                               # :990
+    dev = _lib.default_device() if device is None else device
+    bR, bL, HM, WM, recoError = _stereo_nmf_run(SXR, SXL, WM, HM, betaR, numberOfIterations,
+                                                omega, verbose, dev)
+    if verbose:
+        print("Reconstruction error at beginning: ", recoError[0])
+        steps = ("HM    ", "WM    ", "BETA  ")
+        for n in range(numberOfIterations):
+            print("iteration ", n, " over ", numberOfIterations)
+            for k in range(3):
+                c = 3 * n + k + 1
+                print("Reconstruction error difference after %s: " % steps[k],
+                      recoError[c] - recoError[c - 1])
+    return np.diag(bR), np.diag(bL), HM, WM

@@ -191,6 +191,17 @@ SFNMF_SIGNATURES = {
     "sfnmf_get_params": (ctypes.c_int, [_vp] + [_dp] * 6),
 }
 
+# include/fasst_simm.h, the stereo accompaniment IS-NMF (stereo_NMF); `snmf_`
+# is not on that list of prefixes either
+SNMF_SIGNATURES = {
+    "snmf_create": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(_vp)]),
+    "snmf_destroy": (ctypes.c_int, [_vp]),
+    "snmf_set_data": (ctypes.c_int, [_vp, _dp, _dp]),
+    "snmf_set_params": (ctypes.c_int, [_vp, _dp, _dp, _dp]),
+    "snmf_run": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, _dp]),
+    "snmf_get_params": (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp]),
+}
+
 # include/fasst_sigtools.h, the signal tools (`sig_` is not on that list either).
 # Each call also exists as `<name>_dev` with the same arguments, every array a
 # device pointer (sig_hsum_dev takes the length of bin_idx after it).
@@ -212,7 +223,7 @@ SIG_SIGNATURES = {
 }
 
 for _name, (_res, _args) in (list(SIGNATURES.items()) + list(SFNMF_SIGNATURES.items()) +
-                             list(SIG_SIGNATURES.items())):
+                             list(SNMF_SIGNATURES.items()) + list(SIG_SIGNATURES.items())):
     _fn = getattr(lib, _name)
     _fn.restype = _res
     _fn.argtypes = _args
@@ -222,8 +233,8 @@ for _name, (_res, _args) in (list(SIGNATURES.items()) + list(SFNMF_SIGNATURES.it
 # revision 3: fasst_spatial_filter_* and fasst_gcc_phat; revision 4:
 # fasst_set_tw_constr / fasst_get_tw_constr; revision 5: the two-factor model,
 # fasst_sf_* and fasst_set_factors / fasst_get_factors; revision 6:
-# fasst_estep_partition; revision 7: sfnmf_*)
-ABI_VERSION = 7
+# fasst_estep_partition; revision 7: sfnmf_*; revision 8: snmf_*)
+ABI_VERSION = 8
 if lib.fasst_abi_version() != ABI_VERSION:
     raise ImportError("pyfasst_amd: %s has ABI revision %d, this binding expects %d; rebuild it "
                       "(make -C pyfasst_amd/csrc)" % (LIB_PATH, lib.fasst_abi_version(), ABI_VERSION))

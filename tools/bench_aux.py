@@ -33,6 +33,11 @@
                     N = 10000 on the default F0 dictionary's width K = 1093,
                     Kf = 10, Kr = 2: ms per iteration (sfnmf_run), and the
                     CPU restatement's one iteration at the same size
+  --workload stereo_nmf  stereo_NMF (SIMM.py:945-1104) at F = 2049, N = 10000,
+                    R = 40 (--steps 20): ms per iteration (snmf_run), the same
+                    with the error vector, the IS-NMF engine at K = 40 and 48
+                    in the same process, and the CPU restatement's one
+                    iteration at the same size
   --workload sigtools  tools/signalTools.py: prinComp2D at F = 2049, N = 10000,
                     neighborNb = 20; harmonicSum at F = 2049, T = 10000 on the
                     default F0 grid; medianFilter at 3 rows of N = 10000,
@@ -685,6 +690,76 @@ def bench_sfnmf(steps, warmup, F=2049, N=10000, K=1093, Kf=10, Kr=2, seed=0):
                                        "full size"}}
 
 
+def bench_stereo_nmf(steps, warmup, F=2049, N=10000, R=40, seed=0):
+    from pyfasst_amd import _lib
+    from pyfasst_amd.SeparateLeadStereo.SIMM.SIMM import _SnmfContext
+    from pyfasst_amd.tools.nmf import _NmfContext
+    rs = np.random.RandomState(seed)
+    SXR = rs.gamma(0.7, 1.0, size=(F, N))
+    SXL = rs.gamma(0.7, 1.0, size=(F, N))
+    WM = np.abs(rs.randn(F, R))
+    HM = np.abs(rs.randn(R, N))
+    bR = rs.rand(R)
+    dev = _lib.default_device()
+    ctx = _SnmfContext(F, N, R, dev)
+    _lib.check(_lib.lib.snmf_set_data(ctx.ptr, _lib.dptr(SXR), _lib.dptr(SXL)), "set_data")
+    _lib.check(_lib.lib.snmf_set_params(ctx.ptr, _lib.dptr(WM), _lib.dptr(HM), _lib.dptr(bR)),
+               "set_params")
+    if warmup:
+        _lib.check(_lib.lib.snmf_run(ctx.ptr, warmup, 1.0, None), "run")
+    t0 = time.perf_counter()
+    _lib.check(_lib.lib.snmf_run(ctx.ptr, steps, 1.0, None), "run")
+    dt = time.perf_counter() - t0
+    errs = np.zeros(3 * steps + 1)
+    t0 = time.perf_counter()
+    _lib.check(_lib.lib.snmf_run(ctx.ptr, steps, 1.0, _lib.dptr(errs)), "run")
+    dt_err = time.perf_counter() - t0
+    del ctx
+    # three steps, each two hat products and four contractions of 2 F N Rp flops
+    Rp = (R + 15) // 16 * 16
+    flops = 2.0 * F * N * Rp * 18
+    achieved = flops / (dt / steps) / 1e12
+
+    # the yardstick: the IS-NMF engine (one plane, two contractions) in this
+    # process, at K = R (its stored-plane GEMM path unless K is a multiple of
+    # 16) and at K padded to 16 (its fused path)
+    def isnmf(K):
+        W = rs.randn(F, K) ** 2
+        H = rs.randn(K, N) ** 2
+        W /= W.sum(axis=0)
+        c = _NmfContext(F, N, K, dev)
+        _lib.check(_lib.lib.nmf_set_data(c.ptr, _lib.dptr(SXR)), "set_data")
+        _lib.check(_lib.lib.nmf_set_params(c.ptr, _lib.dptr(W), _lib.dptr(H)), "set_params")
+        if warmup:
+            _lib.check(_lib.lib.nmf_run(c.ptr, warmup, 1, 1), "run")
+        t = time.perf_counter()
+        _lib.check(_lib.lib.nmf_run(c.ptr, steps, 1, 1), "run")
+        return (time.perf_counter() - t) / steps * 1e3
+    nmf_ms = {str(K): round(isnmf(K), 4) for K in sorted({R, Rp})}
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import stereo_nmf_ref
+    cpu_s = None
+    if not NO_CPU:
+        t1 = time.perf_counter()
+        stereo_nmf_ref.iterate(SXR, SXL, WM, HM, np.diag(bR), 1, 1.0)
+        cpu_s = time.perf_counter() - t1
+    ms = dt / steps * 1e3
+    return {"metric": "stereo_NMF ms per iteration", "value": round(ms, 4), "unit": "ms/it",
+            "ms_per_step": round(ms, 4), "steps": steps, "warmup": warmup, "dtype": "f64",
+            "ms_per_step_with_error_vector": round(dt_err / steps * 1e3, 4),
+            "data": "synthetic gamma spectrograms, RandomState(0)",
+            "config": {"workload": "stereo IS-NMF F=%d N=%d R=%d" % (F, N, R)},
+            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": FP64_PEAK / 1e12,
+                         "unit": "TFLOP/s", "frac": round(achieved * 1e12 / FP64_PEAK, 4),
+                         "traffic": None, "scope": "whole iteration, MFMA flops 36 F N Rp"},
+            "isnmf_ms_per_step": nmf_ms,
+            "ratio_to_isnmf": {k: round(ms / v, 3) for k, v in nmf_ms.items()},
+            "cpu_baseline": {"value": round(cpu_s * 1e3, 1) if cpu_s else None, "unit": "ms/it",
+                             "cores": _blas_threads(), "kind": "port",
+                             "sample": "tests/stereo_nmf_ref.py iterate, 1 iteration (and the "
+                                       "initial model and error) at the full size"}}
+
+
 def bench_sigtools(steps, warmup, F=2049, N=10000, seed=0):
     from pyfasst_amd.tools import signalTools as st
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -841,7 +916,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=("simm", "nmf", "cqt", "viterbi", "wf0", "separate",
                                            "nnls", "spatial", "hmm", "sf", "sfnmf", "sigtools",
-                                           "separate_cqt", "filter"),
+                                           "separate_cqt", "filter", "stereo_nmf"),
                     required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -854,7 +929,8 @@ def main():
           "wf0": bench_wf0, "separate": bench_separate, "nnls": bench_nnls,
           "spatial": bench_spatial, "hmm": bench_hmm, "sf": bench_sf,
           "sfnmf": bench_sfnmf, "sigtools": bench_sigtools,
-          "separate_cqt": bench_separate_cqt, "filter": bench_filter}[a.workload]
+          "separate_cqt": bench_separate_cqt, "filter": bench_filter,
+          "stereo_nmf": bench_stereo_nmf}[a.workload]
     out = fn(a.steps, a.warmup)
     if NO_CPU:
         out["cpu_baseline"] = None   # not measured (the sample above timed nothing)
