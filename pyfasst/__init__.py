@@ -4,9 +4,11 @@ package ``pyfasst_amd``.
 
 Every ``pyfasst.<name>`` import is served by the SAME module object as
 ``pyfasst_amd.<name>`` (one class identity, one loaded HIP library), through a
-meta-path alias finder; modules the MI355X package does not provide (DEMIX,
-NSGT, plotting, ... — out of scope) raise ``ImportError`` as any
-missing module would.
+meta-path alias finder; modules the MI355X package does not provide (NSGT,
+plotting, ... — out of scope) raise ``ImportError`` as any
+missing module would.  ``pyfasst.demixTF`` is not aliased yet either: DEMIX is
+imported as ``pyfasst_amd.demixTF`` until it is wired into
+``initializeConvParams('demix')``.
 """
 import importlib
 import importlib.abc
@@ -14,6 +16,7 @@ import importlib.util
 import sys
 
 _TARGET = "pyfasst_amd"
+_NOT_ALIASED = ("demixTF",)
 
 
 class _AliasLoader(importlib.abc.Loader):
@@ -34,6 +37,8 @@ class _AliasLoader(importlib.abc.Loader):
 class _AliasFinder(importlib.abc.MetaPathFinder):
     def find_spec(self, fullname, path=None, target=None):
         if not fullname.startswith(__name__ + "."):
+            return None
+        if fullname[len(__name__) + 1:] in _NOT_ALIASED:
             return None
         real = _TARGET + fullname[len(__name__):]
         if importlib.util.find_spec(real) is None:

@@ -1,7 +1,7 @@
 """ctypes binding of libfasst_hip.so (declared in include/fasst_hip.h,
 include/fasst_simm.h, include/fasst_nmf.h, include/fasst_cqt.h,
-include/fasst_viterbi.h, include/fasst_dict.h, include/fasst_sigtools.h and
-include/fasst_filter.h).
+include/fasst_viterbi.h, include/fasst_dict.h, include/fasst_sigtools.h,
+include/fasst_filter.h and include/fasst_demix.h).
 
 The product path has no CPU fallback: if the HIP library is missing this
 module raises at import time, and every compute call raises if the device
@@ -222,8 +222,33 @@ SIG_SIGNATURES = {
     "sig_last_ms": (ctypes.c_int, [_dp]),
 }
 
+# include/fasst_demix.h, DEMIX's device side (`demix_` is not on that list either)
+_ucp = ctypes.POINTER(ctypes.c_ubyte)
+_lp = ctypes.POINTER(ctypes.c_long)
+DEMIX_SIGNATURES = {
+    "demix_create": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(_vp)]),
+    "demix_destroy": (ctypes.c_int, [_vp]),
+    "demix_features": (ctypes.c_int, [_vp, _dp, _dp]),
+    "demix_features_dev": (ctypes.c_int, [_vp, _dp, _dp]),
+    "demix_get_plane": (ctypes.c_int, [_vp, ctypes.c_int, _dp]),
+    "demix_set_plane": (ctypes.c_int, [_vp, ctypes.c_int, _dp]),
+    "demix_get_mask": (ctypes.c_int, [_vp, ctypes.c_int, _ucp]),
+    "demix_set_mask": (ctypes.c_int, [_vp, ctypes.c_int, _ucp]),
+    "demix_init_subset": (ctypes.c_int, [_vp]),
+    "demix_argmax": (ctypes.c_int, [_vp, _dp]),
+    "demix_theta_pass": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, _dp]),
+    "demix_delta_pass": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, _dp, ctypes.c_double,
+                                        ctypes.c_double, ctypes.c_long, ctypes.c_int, _lp]),
+    "demix_exclusive": (ctypes.c_int, [_vp, ctypes.c_int, _ip, _lp]),
+    "demix_cluster_sums": (ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _dp]),
+    "demix_last_ms": (ctypes.c_int, [_dp]),
+    "demix_launch_count": (ctypes.c_int, [_lp]),
+    "demix_transfer_count": (ctypes.c_int, [_lp]),
+}
+
 for _name, (_res, _args) in (list(SIGNATURES.items()) + list(SFNMF_SIGNATURES.items()) +
-                             list(SNMF_SIGNATURES.items()) + list(SIG_SIGNATURES.items())):
+                             list(SNMF_SIGNATURES.items()) + list(SIG_SIGNATURES.items()) +
+                             list(DEMIX_SIGNATURES.items())):
     _fn = getattr(lib, _name)
     _fn.restype = _res
     _fn.argtypes = _args

@@ -43,6 +43,12 @@
                     default F0 grid; medianFilter at 3 rows of N = 10000,
                     length = 10: device ms (HIP events), host-inclusive ms,
                     and the CPU restatement once per case
+  --workload demix  DEMIX (demixTF.py) at F = 1025, N = 5002 frames (5000 hops
+                    of 1024 samples at 44.1 kHz, wlen = 2048), neighbors = 20,
+                    three delayed sources (--steps 3): device ms of the
+                    feature stage and per clustering round, the two mask
+                    passes' bytes per second, host-inclusive comp_clusters()
+                    and refine_clusters(), and the restatement once
   --workload viterbi  melody tracking (_tracking.pyx:11-93) at config 5:
                     S = 1092 F0 states, N = 20000 frames (runViterbi's
                     transitions, stepNotes 16): tracks/s, device time
@@ -827,6 +833,99 @@ def bench_sigtools(steps, warmup, F=2049, N=10000, seed=0):
                                        "(cases[*].cpu_restatement_ms)"}}
 
 
+def bench_demix(steps, warmup, fs=44100, wlen=2048, hop=1024, frames=5000, neighbors=20, seed=0):
+    """DEMIX (demixTF.py) on about two minutes of synthetic stereo: three band
+    noises with pans and integer delays plus white noise, 5000 hops of 1024
+    samples at 44.1 kHz (5.12 M samples, under the two-minute crop): F = 1025,
+    N = 5002 frames, L = 4983 windows with neighbors = 20.  Device times are
+    HIP events around the kernels (DEMIX.features_ms, round_pass_ms); the
+    restatement (tests/demix_ref.py, direct PCA sums) runs once on this host."""
+    import tempfile
+    import warnings
+    import scipy.io.wavfile as wf
+    import pyfasst_amd.demixTF as dm
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import demix_ref as D
+    n = frames * hop
+    x = D.live_mixture(n, seed, fs=fs)
+    samples = np.round(x / np.abs(x).max() * 30000).astype(np.int16)
+    kw = dict(nsources=3, wlen=wlen, hopsize=hop, neighbors=neighbors)
+    runs = []
+    with tempfile.TemporaryDirectory() as tmp, warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        wav = os.path.join(tmp, "demix.wav")
+        wf.write(wav, fs, samples)
+        for it in range(warmup + steps):
+            d = dm.DEMIX(wav, **kw)
+            t0 = time.perf_counter()
+            d.comp_clusters()
+            t1 = time.perf_counter()
+            passes = np.array(d.round_pass_ms)
+            full = ~np.isnan([c.delta for c in d.clusterCentroids])
+            npts = d._F * d._L
+            shape = (d._F, d._L)
+            d.refine_clusters()
+            t2 = time.perf_counter()
+            if it >= warmup:
+                runs.append(dict(features=d.features_ms, round=float(np.mean(d.round_ms)),
+                                 argmax=float(np.mean(passes[:, 0])),
+                                 theta=float(np.mean(passes[:, 1])),
+                                 delta=float(np.mean(passes[full, 2])) if full.any() else None,
+                                 rounds=len(d.round_ms), rounds_with_delta=int(full.sum()),
+                                 comp=(t1 - t0) * 1e3, refine=(t2 - t1) * 1e3))
+            result = [(float(c.theta), float(c.delta)) for c in d.clusterCentroids]
+            del d
+    med = lambda k: float(np.median([r[k] for r in runs if r[k] is not None]))
+    cpu = None
+    if not NO_CPU:
+        print("restatement: comp_clusters ...", file=sys.stderr, flush=True)
+        r = D.RefDEMIX(D.read_scaled(samples), fs, pca='direct', **kw)
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            t0 = time.perf_counter()
+            r.comp_clusters()
+            t1 = time.perf_counter()
+            print("restatement: refine_clusters ...", file=sys.stderr, flush=True)
+            r.refine_clusters()
+            t2 = time.perf_counter()
+        cpu = {"comp_clusters_ms": round((t1 - t0) * 1e3, 1),
+               "refine_clusters_ms": round((t2 - t1) * 1e3, 1), "rounds": len(r.rounds),
+               "centroids": [(float(c.theta), float(c.delta)) for c in r.clusterCentroids]}
+    theta_bytes, delta_bytes = 26 * npts, 35 * npts
+    gbs = lambda b, ms: round(b / (ms * 1e-3) / 1e9, 1)
+    th, de = med('theta'), med('delta')
+    return {"metric": "DEMIX device ms per clustering round", "value": round(med('round'), 4),
+            "unit": "ms", "ms_per_step": round(med('round'), 4), "steps": steps, "warmup": warmup,
+            "dtype": "f64", "data": "synthetic, demix_ref.live_mixture(%d, %d, fs=%d)" % (n, seed, fs),
+            "config": {"workload": "DEMIX F=%d N=%d L=%d neighbors=%d nsources=3 maxclusters=100"
+                                   % (shape[0], frames + 2, shape[1], neighbors)},
+            "features_device_ms": round(med('features'), 4),
+            "round_device_ms": round(med('round'), 4),
+            "argmax_device_ms": round(med('argmax'), 4),
+            "theta_pass_device_ms": round(th, 4), "delta_pass_device_ms": round(de, 4),
+            "rounds": runs[-1]['rounds'], "rounds_with_delta": runs[-1]['rounds_with_delta'],
+            "comp_clusters_host_inclusive_ms": round(med('comp'), 1),
+            "refine_clusters_host_inclusive_ms": round(med('refine'), 1),
+            "centroids": result,
+            "passes": [
+                {"pass": "k_theta_pass", "hbm_bytes": theta_bytes, "hbm_gb_per_s": gbs(theta_bytes, th),
+                 "frac_of_measured_copy_6290": round(gbs(theta_bytes, th) / 6290., 4),
+                 "bytes_counted": "theta, phi, var and the subset byte read, the candidate byte "
+                                  "written (26 B per point)"},
+                {"pass": "k_delta_pass", "hbm_bytes": delta_bytes, "hbm_gb_per_s": gbs(delta_bytes, de),
+                 "frac_of_measured_copy_6290": round(gbs(delta_bytes, de) / 6290., 4),
+                 "bytes_counted": "four planes and the subset byte read, the mask byte and the "
+                                  "subset byte written (35 B per point); rounds with a delta"}],
+            "roofline": {"bound": "hbm", "achieved": gbs(delta_bytes, de), "peak": 6290.,
+                         "unit": "GB/s", "frac": round(gbs(delta_bytes, de) / 6290., 4),
+                         "traffic": delta_bytes, "scope": "k_delta_pass, device events"},
+            "cpu_baseline": {"value": cpu["comp_clusters_ms"] if cpu else None, "unit": "ms",
+                             "cores": _blas_threads(), "kind": "port",
+                             "sample": "tests/demix_ref.py comp_clusters() then refine_clusters() "
+                                       "on the same samples, once", "detail": cpu}}
+
+
 def bench_filter(steps, warmup, M=2, L=5120000, wlen=4096, hop=512, seed=0):
     """filter_stft at the C3 clip (2 channels, 5.12 M samples, wlen = nfft =
     4096, hop 512: 10000 frames), time-invariant and time-varying W, against
@@ -916,7 +1015,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=("simm", "nmf", "cqt", "viterbi", "wf0", "separate",
                                            "nnls", "spatial", "hmm", "sf", "sfnmf", "sigtools",
-                                           "separate_cqt", "filter", "stereo_nmf"),
+                                           "separate_cqt", "filter", "stereo_nmf", "demix"),
                     required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -930,7 +1029,7 @@ def main():
           "spatial": bench_spatial, "hmm": bench_hmm, "sf": bench_sf,
           "sfnmf": bench_sfnmf, "sigtools": bench_sigtools,
           "separate_cqt": bench_separate_cqt, "filter": bench_filter,
-          "stereo_nmf": bench_stereo_nmf}[a.workload]
+          "stereo_nmf": bench_stereo_nmf, "demix": bench_demix}[a.workload]
     out = fn(a.steps, a.warmup)
     if NO_CPU:
         out["cpu_baseline"] = None   # not measured (the sample above timed nothing)
