@@ -172,6 +172,9 @@ SIGNATURES = {
     "dict_wf0_stft": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, ctypes.c_int, _dp,
                                      ctypes.c_double, ctypes.c_int, _dp, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_long, _dp]),
+    "dict_odgd": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, ctypes.c_int, _dp, _dp,
+                                 ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _ip,
+                                 ctypes.c_int, _dp, _dp, _dp]),
     "dict_last_ms": (ctypes.c_int, [_dp]),
     # include/fasst_nnls.h
     "nnls_columns": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int,

@@ -55,6 +55,72 @@ __global__ __launch_bounds__(256) void k_wf0_column(const DictArgs a) {
   }
 }
 
+// The public ODGD family (generate_ODGD_spec :888-949, _chirped :1010-1072,
+// generate_WF0_chirped :237-345): per column the whole complex waveform at
+// ts = n / fs + t_off, the full nfft-point spectrum of Re(odgd * window)
+// (cropped to the first nfft samples or zero-padded, as np.fft.fft(x, n) does)
+// and its power.  The windowed signal is real: bins 0 .. nfft/2 come out of
+// the LDS FFT and the upper half is their Hermitian mirror, so power[k] and
+// power[nfft - k] are the same double.  Columns pick their window by index
+// (generate_WF0_chirped mixes two).
+struct OdgdArgs {
+  const double *f1, *f2, *toff;
+  const int *np_, *wsel;
+  const double2 *amps;   // [n_cols][max_partials]
+  const double *win;     // [n_windows][length_odgd]
+  const double2 *tw;
+  double2 *odgd;         // [n_cols][length_odgd] or null
+  double2 *spec;         // [n_cols][nfft] or null
+  double *power;         // [nfft][n_cols] or null
+  double fs;
+  int n_cols, max_partials, length_odgd, nfft, logn;
+};
+
+__global__ __launch_bounds__(256) void k_odgd_column(const OdgdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double2 sm[];
+  double2 *buf = sm;                 // [nfft]
+  double2 *amp = sm + a.nfft;        // [max_partials]
+  const int j = blockIdx.x;
+  const int P = a.np_[j];
+  const double F1 = a.f1[j], F2 = a.f2[j], t_off = a.toff[j];
+  const int L = a.length_odgd;
+  const bool transform = a.spec || a.power;
+  for (int h = threadIdx.x; h < P; h += blockDim.x) amp[h] = a.amps[(size_t)j * a.max_partials + h];
+  __syncthreads();
+  const double den = 2.0 * (double)L / a.fs;
+  const double *win = a.win + (size_t)a.wsel[j] * L;
+  // samples past nfft only matter to the waveform
+  const int n_syn = a.odgd ? L : min(L, a.nfft);
+  const int n_buf = transform ? a.nfft : 0;
+  for (int i = threadIdx.x; i < max(n_syn, n_buf); i += blockDim.x) {
+    double v = 0.0;
+    if (i < n_syn) {
+      const double2 z = odgd_sample_at(amp, P, F1, F2, den, (double)i / a.fs + t_off);
+      if (a.odgd) a.odgd[(size_t)j * L + i] = z;
+      v = z.x * win[i];
+    }
+    if (i < n_buf) buf[bitrev(i, a.logn)] = make_double2(v, 0.0);
+  }
+  if (!transform) return;
+  __syncthreads();
+  lds_fft(buf, a.tw, a.nfft, a.logn);
+  const int N = a.nfft;
+  for (int k = threadIdx.x; k <= N / 2; k += blockDim.x) {
+    double2 X = buf[k];
+    if (k == 0 || 2 * k == N) X.y = 0.0;   // real input: DC and Nyquist are real
+    const int km = (N - k) & (N - 1);      // mirror bin (k itself for DC and Nyquist)
+    if (a.spec) {
+      a.spec[(size_t)j * N + k] = X;
+      if (km != k) a.spec[(size_t)j * N + km] = make_double2(X.x, -X.y);
+    }
+    if (a.power) {
+      const double m = hypot(X.x, X.y);    // np.abs(X) ** 2
+      a.power[(size_t)k * a.n_cols + j] = m * m;
+      if (km != k) a.power[(size_t)km * a.n_cols + j] = m * m;
+    }
+  }
+}
+
 static float g_dict_ms = 0.f;
 
 }  // namespace fasst
@@ -132,6 +198,94 @@ int dict_wf0_stft(int device, int n_cols, const double *f1, const double *f2,
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   FASST_HIP(hipMemcpy(wf0, dout.p, (size_t)F * n_cols * sizeof(double), hipMemcpyDeviceToHost));
+  return FASST_OK;
+}
+
+int dict_odgd(int device, int n_cols, const double *f1, const double *f2, const int *n_partials,
+              int max_partials, const double *amps, const double *t_offset, double fs,
+              int length_odgd, int n_windows, const double *windows, const int *window_sel,
+              int nfft, double *odgd, double *spectrum, double *power) {
+  if (n_cols < 1 || max_partials < 1 || !f1 || !f2 || !n_partials || !amps || !t_offset ||
+      n_windows < 1 || !windows || !window_sel || ilog2(nfft) < 1 || nfft > 8192 ||
+      length_odgd < 1 || !(fs > 0) || (!odgd && !spectrum && !power)) {
+    set_error("dict_odgd: bad shape (cols %d, partials %d, nfft %d not a power of two in "
+              "2..8192, length %d, windows %d) or no output requested", n_cols, max_partials,
+              nfft, length_odgd, n_windows);
+    return FASST_ERR_SHAPE;
+  }
+  for (int j = 0; j < n_cols; ++j) {
+    if (n_partials[j] < 0 || n_partials[j] > max_partials) {
+      set_error("dict_odgd: column %d has %d partials > %d", j, n_partials[j], max_partials);
+      return FASST_ERR_SHAPE;
+    }
+    if (window_sel[j] < 0 || window_sel[j] >= n_windows) {
+      set_error("dict_odgd: column %d selects window %d of %d", j, window_sel[j], n_windows);
+      return FASST_ERR_SHAPE;
+    }
+  }
+  const size_t smem = ((size_t)nfft + max_partials) * sizeof(double2);
+  if (smem > 160 * 1024) {
+    set_error("dict_odgd: nfft %d + %d partials exceed the LDS", nfft, max_partials);
+    return FASST_ERR_SHAPE;
+  }
+  DeviceGuard g(device);
+  int st;
+  const size_t L = (size_t)length_odgd, C = (size_t)n_cols, N = (size_t)nfft;
+  DBuf<double> d1, d2, dt, dw, dpow;
+  DBuf<int> dnp, dsel;
+  DBuf<double2> damps, dtw, dodgd, dspec;
+  if ((st = d1.alloc(C)) || (st = d2.alloc(C)) || (st = dt.alloc(C)) || (st = dnp.alloc(C)) ||
+      (st = dsel.alloc(C)) || (st = damps.alloc(C * max_partials)) ||
+      (st = dw.alloc((size_t)n_windows * L)) || (st = dtw.alloc(N / 2)) ||
+      (st = dodgd.alloc(odgd ? C * L : 0)) || (st = dspec.alloc(spectrum ? C * N : 0)) ||
+      (st = dpow.alloc(power ? N * C : 0)))
+    return st;
+  auto tw = twiddles(nfft, -1);
+  FASST_HIP(hipMemcpy(d1.p, f1, C * sizeof(double), hipMemcpyHostToDevice));
+  FASST_HIP(hipMemcpy(d2.p, f2, C * sizeof(double), hipMemcpyHostToDevice));
+  FASST_HIP(hipMemcpy(dt.p, t_offset, C * sizeof(double), hipMemcpyHostToDevice));
+  FASST_HIP(hipMemcpy(dnp.p, n_partials, C * sizeof(int), hipMemcpyHostToDevice));
+  FASST_HIP(hipMemcpy(dsel.p, window_sel, C * sizeof(int), hipMemcpyHostToDevice));
+  FASST_HIP(hipMemcpy(damps.p, amps, C * max_partials * sizeof(double2), hipMemcpyHostToDevice));
+  FASST_HIP(hipMemcpy(dw.p, windows, (size_t)n_windows * L * sizeof(double),
+                      hipMemcpyHostToDevice));
+  FASST_HIP(hipMemcpy(dtw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
+  if (smem > 64 * 1024)
+    FASST_HIP(hipFuncSetAttribute((const void *)k_odgd_column,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  OdgdArgs a;
+  a.f1 = d1.p;
+  a.f2 = d2.p;
+  a.toff = dt.p;
+  a.np_ = dnp.p;
+  a.wsel = dsel.p;
+  a.amps = damps.p;
+  a.win = dw.p;
+  a.tw = dtw.p;
+  a.odgd = dodgd.p;
+  a.spec = dspec.p;
+  a.power = dpow.p;
+  a.fs = fs;
+  a.n_cols = n_cols;
+  a.max_partials = max_partials;
+  a.length_odgd = length_odgd;
+  a.nfft = nfft;
+  a.logn = ilog2(nfft);
+  hipEvent_t e0, e1;
+  FASST_HIP(hipEventCreate(&e0));
+  FASST_HIP(hipEventCreate(&e1));
+  FASST_HIP(hipEventRecord(e0, 0));
+  k_odgd_column<<<n_cols, 256, smem>>>(a);
+  FASST_LAUNCH_CHECK();
+  FASST_HIP(hipEventRecord(e1, 0));
+  FASST_HIP(hipEventSynchronize(e1));
+  FASST_HIP(hipEventElapsedTime(&g_dict_ms, e0, e1));
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (odgd) FASST_HIP(hipMemcpy(odgd, dodgd.p, C * L * sizeof(double2), hipMemcpyDeviceToHost));
+  if (spectrum)
+    FASST_HIP(hipMemcpy(spectrum, dspec.p, C * N * sizeof(double2), hipMemcpyDeviceToHost));
+  if (power) FASST_HIP(hipMemcpy(power, dpow.p, N * C * sizeof(double), hipMemcpyDeviceToHost));
   return FASST_OK;
 }
 

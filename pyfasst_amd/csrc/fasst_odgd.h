@@ -33,4 +33,27 @@ __device__ __forceinline__ double2 odgd_sample(const double2 *amp, int P, double
   return make_double2(re, im);
 }
 
+// The same sum at the time stamp ts = n / fs + t0 / F0 of the public
+// generate_ODGD_spec / _chirped (:936, :1058), handed in by the caller.
+// A form of its own: odgd_sample keeps its arithmetic (ts = t / fs there).
+__device__ __forceinline__ double2 odgd_sample_at(const double2 *amp, int P, double F1, double F2,
+                                                  double den, double ts) {
+  const double two_pi = 2.0 * M_PI;
+  const double w1 = two_pi * F1;
+  const double dF = F2 - F1;
+  const bool chirp = F1 != F2;
+  double re = 0.0, im = 0.0;
+  for (int h = 0; h < P; ++h) {
+    const double fh = (double)(h + 1);
+    const double th = chirp ? two_pi * ((F1 * fh) * ts + ((dF * fh) * (ts * ts)) / den)
+                            : (w1 * fh) * ts;
+    double s, c;
+    sincos(th, &s, &c);
+    const double2 am = amp[h];
+    re += c * am.x - s * am.y;   // exp(i th) * amp
+    im += c * am.y + s * am.x;
+  }
+  return make_double2(re, im);
+}
+
 }  // namespace fasst

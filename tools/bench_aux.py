@@ -49,6 +49,11 @@
                     feature stage and per clustering round, the two mask
                     passes' bytes per second, host-inclusive comp_clusters()
                     and refine_clusters(), and the restatement once
+  --workload wf0_chirped  generate_WF0_chirped at the reference's default grid
+                    (39-2000 Hz, stepNotes 16, 44.1 kHz, Nfft = lengthWindow =
+                    2048, perF0 1: 1092 columns): device time of the one
+                    dict_odgd launch, host-inclusive time, and the restatement
+                    on the host (profiles/dict_family_bench.jsonl)
   --workload viterbi  melody tracking (_tracking.pyx:11-93) at config 5:
                     S = 1092 F0 states, N = 20000 frames (runViterbi's
                     transitions, stepNotes 16): tracks/s, device time
@@ -514,6 +519,48 @@ def bench_wf0(steps, warmup):
                              "cores": 1, "kind": "port",
                              "sample": "oracle/dict_ref.py on 8 of the %d F0s, scaled"
                                        % F0Table.size}}
+
+
+def bench_wf0_chirped(steps, warmup):
+    import tempfile
+    from pyfasst_amd import _lib
+    from pyfasst_amd.SeparateLeadStereo import separateLeadFunctions as slf
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dict_family_ref as D
+    os.chdir(tempfile.mkdtemp())
+    kw = dict(minF0=39, maxF0=2000, Fs=44100, Nfft=2048, stepNotes=16, lengthWindow=2048, perF0=1)
+    ms, host = [], []
+    for i in range(warmup + steps):
+        t0 = time.perf_counter()
+        F0Table, WF0 = slf.generate_WF0_chirped(loadWF0=False, **kw)
+        dt = time.perf_counter() - t0
+        m = ctypes.c_double()
+        _lib.lib.dict_last_ms(ctypes.byref(m))
+        if i >= warmup:
+            ms.append(m.value)
+            host.append(dt * 1e3)
+    dm = float(np.median(ms))
+    # CPU: the restatement (the reference's outer-product synthesis) on 8 of the F0s
+    idx = np.linspace(0, F0Table.size - 1, 8).astype(int)
+    t0 = time.perf_counter()
+    for i in idx:
+        D.generate_ODGD_spec(F0Table[i], 44100, lengthOdgd=2048, Nfft=2048,
+                             analysisWindowType='hanning')
+    cpu_s = (time.perf_counter() - t0) / idx.size * F0Table.size
+    partials = sum(int(np.floor(22050.0 / f)) for f in F0Table)
+    return {"metric": "generate_WF0_chirped dictionaries/sec (default grid, device time)",
+            "value": round(1e3 / dm, 3), "unit": "dictionaries/s", "device_ms": round(dm, 3),
+            "host_inclusive_ms": round(float(np.median(host)), 3),
+            "steps": steps, "warmup": warmup, "dtype": "f64",
+            "config": {"workload": "generate_WF0_chirped fs=44100 Nfft=lengthWindow=2048 minF0=39 "
+                                   "maxF0=2000 stepNotes=16 perF0=1: %d combs, %d partials, WF0 "
+                                   "%d x %d" % (F0Table.size, partials, WF0.shape[0],
+                                                WF0.shape[1])},
+            "partial_samples_per_s": round(partials * 2048 / (dm * 1e-3) / 1e9, 2),
+            "cpu_baseline": {"value": round(1.0 / cpu_s, 5), "unit": "dictionaries/s",
+                             "cores": 1, "kind": "port", "seconds": round(cpu_s, 2),
+                             "sample": "tests/dict_family_ref.py generate_ODGD_spec on 8 of the "
+                                       "%d F0s, scaled" % F0Table.size}}
 
 
 def bench_nnls(steps, warmup, frames=1000, seed=0):
@@ -1015,7 +1062,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=("simm", "nmf", "cqt", "viterbi", "wf0", "separate",
                                            "nnls", "spatial", "hmm", "sf", "sfnmf", "sigtools",
-                                           "separate_cqt", "filter", "stereo_nmf", "demix"),
+                                           "separate_cqt", "filter", "stereo_nmf", "demix",
+                                           "wf0_chirped"),
                     required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -1029,7 +1077,8 @@ def main():
           "spatial": bench_spatial, "hmm": bench_hmm, "sf": bench_sf,
           "sfnmf": bench_sfnmf, "sigtools": bench_sigtools,
           "separate_cqt": bench_separate_cqt, "filter": bench_filter,
-          "stereo_nmf": bench_stereo_nmf, "demix": bench_demix}[a.workload]
+          "stereo_nmf": bench_stereo_nmf, "demix": bench_demix,
+          "wf0_chirped": bench_wf0_chirped}[a.workload]
     out = fn(a.steps, a.warmup)
     if NO_CPU:
         out["cpu_baseline"] = None   # not measured (the sample above timed nothing)
