@@ -35,6 +35,11 @@ _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int)
 _vp = ctypes.c_void_p
 _llp = ctypes.POINTER(ctypes.c_longlong)
+_ucp = ctypes.POINTER(ctypes.c_ubyte)
+_lp = ctypes.POINTER(ctypes.c_long)
+_SIG_PCA = [ctypes.c_int] * 4 + [_dp] * 6 + [_ip]
+_SIG_MEDIAN = [ctypes.c_int] * 4 + [_dp, _dp]
+_SIG_INVHERM = [ctypes.c_int, ctypes.c_long, ctypes.c_int] + [_dp] * 6 + [_ip]
 
 # name -> (restype, argtypes); must match include/*.h exactly
 SIGNATURES = {
@@ -180,38 +185,23 @@ SIGNATURES = {
     "nnls_columns": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int,
                                     _dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, _dp,
                                     _ip]),
-}
-
-# include/fasst_nmf.h, the source / filter IS-NMF.  A table of its own:
-# SIGNATURES is compared with the symbols tests/test_abi.py finds in include/*.h
-# by a fixed list of prefixes, which `sfnmf_` is not on.
-SFNMF_SIGNATURES = {
+    # include/fasst_nmf.h, the source / filter IS-NMF
     "sfnmf_create": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(_vp)]),
     "sfnmf_destroy": (ctypes.c_int, [_vp]),
     "sfnmf_set_data": (ctypes.c_int, [_vp, _dp]),
     "sfnmf_set_params": (ctypes.c_int, [_vp] + [_dp] * 6),
     "sfnmf_run": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5),
     "sfnmf_get_params": (ctypes.c_int, [_vp] + [_dp] * 6),
-}
-
-# include/fasst_simm.h, the stereo accompaniment IS-NMF (stereo_NMF); `snmf_`
-# is not on that list of prefixes either
-SNMF_SIGNATURES = {
+    # include/fasst_simm.h, the stereo accompaniment IS-NMF (stereo_NMF)
     "snmf_create": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(_vp)]),
     "snmf_destroy": (ctypes.c_int, [_vp]),
     "snmf_set_data": (ctypes.c_int, [_vp, _dp, _dp]),
     "snmf_set_params": (ctypes.c_int, [_vp, _dp, _dp, _dp]),
     "snmf_run": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, _dp]),
     "snmf_get_params": (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp]),
-}
-
-# include/fasst_sigtools.h, the signal tools (`sig_` is not on that list either).
-# Each call also exists as `<name>_dev` with the same arguments, every array a
-# device pointer (sig_hsum_dev takes the length of bin_idx after it).
-_SIG_PCA = [ctypes.c_int] * 4 + [_dp] * 6 + [_ip]
-_SIG_MEDIAN = [ctypes.c_int] * 4 + [_dp, _dp]
-_SIG_INVHERM = [ctypes.c_int, ctypes.c_long, ctypes.c_int] + [_dp] * 6 + [_ip]
-SIG_SIGNATURES = {
+    # include/fasst_sigtools.h, the signal tools.  Each call also exists as
+    # `<name>_dev` with the same arguments, every array a device pointer
+    # (sig_hsum_dev takes the length of bin_idx after it).
     "sig_pca2d": (ctypes.c_int, _SIG_PCA),
     "sig_pca2d_dev": (ctypes.c_int, _SIG_PCA),
     "sig_median": (ctypes.c_int, _SIG_MEDIAN),
@@ -223,12 +213,7 @@ SIG_SIGNATURES = {
     "sig_invherm_dev": (ctypes.c_int, _SIG_INVHERM),
     "sig_launch_count": (ctypes.c_int, [ctypes.POINTER(ctypes.c_long)]),
     "sig_last_ms": (ctypes.c_int, [_dp]),
-}
-
-# include/fasst_demix.h, DEMIX's device side (`demix_` is not on that list either)
-_ucp = ctypes.POINTER(ctypes.c_ubyte)
-_lp = ctypes.POINTER(ctypes.c_long)
-DEMIX_SIGNATURES = {
+    # include/fasst_demix.h, DEMIX's device side
     "demix_create": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(_vp)]),
     "demix_destroy": (ctypes.c_int, [_vp]),
     "demix_features": (ctypes.c_int, [_vp, _dp, _dp]),
@@ -249,9 +234,7 @@ DEMIX_SIGNATURES = {
     "demix_transfer_count": (ctypes.c_int, [_lp]),
 }
 
-for _name, (_res, _args) in (list(SIGNATURES.items()) + list(SFNMF_SIGNATURES.items()) +
-                             list(SNMF_SIGNATURES.items()) + list(SIG_SIGNATURES.items()) +
-                             list(DEMIX_SIGNATURES.items())):
+for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype = _res
     _fn.argtypes = _args

@@ -49,6 +49,11 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 void set_error(const char *fmt, ...);
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+// blocks of 256 threads for a grid-stride loop over n elements
+inline int egrid(size_t n) {
+  const size_t b = (n + 255) / 256;
+  return (int)(b < 8192 ? b : 8192);
+}
 
 #define FASST_HIP(call)                                                      \
   do {                                                                       \
@@ -81,6 +86,38 @@ struct DeviceGuard {
     if (prev >= 0) (void)hipSetDevice(prev);
   }
 };
+
+// Up to three HIP events owned by a call's scope or by a context and destroyed
+// with it, so no error return after create() can leak them.
+struct Events {
+  hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+  Events() = default;
+  Events(const Events &) = delete;
+  Events &operator=(const Events &) = delete;
+  int create(int n) {
+    for (int i = 0; i < n; ++i) FASST_HIP(hipEventCreate(&e[i]));
+    return FASST_OK;
+  }
+  // the timer of one call: create e[0] and e[1], record e[0] on `stream`
+  int start(hipStream_t stream) {
+    int st = create(2);
+    if (st) return st;
+    FASST_HIP(hipEventRecord(e[0], stream));
+    return FASST_OK;
+  }
+  ~Events() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
+
+// Record `end` on `stream`, wait for it, *ms = the device time since `start`.
+inline int elapsed_ms(hipEvent_t start, hipEvent_t end, hipStream_t stream, float *ms) {
+  FASST_HIP(hipEventRecord(end, stream));
+  FASST_HIP(hipEventSynchronize(end));
+  FASST_HIP(hipEventElapsedTime(ms, start, end));
+  return FASST_OK;
+}
 
 // Device buffer owned by a context; freed in the destructor.
 template <typename T>

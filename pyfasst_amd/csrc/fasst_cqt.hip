@@ -56,6 +56,7 @@
 // of one is the single-signal transform.  A FASST model's two channels, and
 // its 2 nsrc separated images, go through one chain in the model's own
 // planes (fasst_cqt_dev.h).
+#include "fasst_device.h"
 #include "fasst_fft.h"
 #include "fasst_odgd.h"
 #include "fasst_cqt_dev.h"
@@ -261,18 +262,6 @@ __global__ __launch_bounds__(256) void k_cqt_band_cells(const double2 *__restric
   }
 }
 
-// np.abs(complex128): larger * sqrt(fma(r, r, 1)), r = smaller / larger
-// (NumPy's loop for the complex absolute value, as in fasst_sigtools.hip)
-__device__ __forceinline__ double cqt_np_cabs(double re, double im) {
-#pragma clang fp contract(off)
-  const double a = fabs(re), b = fabs(im);
-  if (isinf(a) || isinf(b)) return INFINITY;
-  if (a != a || b != b) return NAN;
-  const double l = a > b ? a : b, s = a > b ? b : a;
-  const double r = l == 0.0 ? 0.0 : s / l;
-  return sqrt(fma(r, r, 1.0)) * l;
-}
-
 struct RasterArgs {
   const double2 *cell;  // [bins*win_nr][nfr] of this octave
   double2 *sp;          // [F][W] row-major (the C ABI's layout)
@@ -320,7 +309,7 @@ __global__ __launch_bounds__(256) void k_cqt_cell_raster(const RasterArgs a) {
     return;
   }
   const double2 lo = raster_at(a, nb, c0), hi = raster_at(a, nb, c1);
-  const double ylo = cqt_np_cabs(lo.x, lo.y), yhi = cqt_np_cabs(hi.x, hi.y);
+  const double ylo = np_cabs(lo.x, lo.y), yhi = np_cabs(hi.x, hi.y);
   const double slope = (yhi - ylo) / (double)(c1 - c0);
   const double t = slope * (double)(c - c0);
   *o = make_double2(t + ylo, 0.0);

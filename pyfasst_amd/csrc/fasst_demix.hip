@@ -21,7 +21,7 @@
 // bytes, but its FP64 sincos / cos / sin / sqrt per point bound it, at 0.07 of
 // that rate (profiles/demix_bench.jsonl).  The expressions
 // follow NumPy's operation order with contraction off.
-#include "fasst_common.h"
+#include "fasst_device.h"
 #include "../../include/fasst_demix.h"
 #include "../../include/fasst_sigtools.h"
 
@@ -40,17 +40,6 @@ constexpr int kDB = 256;           // threads per block, every kernel here
 constexpr int kDmxMaxBlocks = 1024;  // stage-1 blocks of the two-stage reductions
 constexpr double kUBound = 2.33;   // uVarBound == uDistBound (demixTF.py:50-51)
 
-// np.abs(complex128) (see fasst_sigtools.hip)
-__device__ __forceinline__ double dmx_cabs(double re, double im) {
-#pragma clang fp contract(off)
-  const double a = fabs(re), b = fabs(im);
-  if (isinf(a) || isinf(b)) return INFINITY;
-  if (a != a || b != b) return NAN;
-  const double l = a > b ? a : b, s = a > b ? b : a;
-  const double r = l == 0.0 ? 0.0 : s / l;
-  return sqrt(fma(r, r, 1.0)) * l;
-}
-
 // estim_var_theta (:497-512) of one confidence
 __device__ __forceinline__ double dmx_var_theta(double conf, double nm1) {
 #pragma clang fp contract(off)
@@ -65,7 +54,9 @@ __device__ __forceinline__ double dmx_var_theta(double conf, double nm1) {
   return v;
 }
 
-// fixed-order tree over the block's kDB values
+// fixed-order tree over the block's kDB values (the sums do not go through
+// block_sum of fasst_device.h: its blockDim.x loop compiles differently from
+// this constant-bound one, and the other operators need the template anyway)
 template <typename T, typename Op>
 __device__ __forceinline__ T block_reduce(T v, T *sm, Op op) {
   sm[threadIdx.x] = v;
@@ -167,7 +158,7 @@ __global__ __launch_bounds__(kDB) void k_features(const FeatArgs a) {
     qi = (e1.y * rat - e1.x) * scl;
   }
   a.phi[i] = atan2(qi, qr);
-  a.theta[i] = atan(dmx_cabs(e1.x, e1.y) / dmx_cabs(e0.x, e0.y));
+  a.theta[i] = atan(np_cabs(e1.x, e1.y) / np_cabs(e0.x, e0.y));
   a.conf[i] = conf;
   a.var[i] = dmx_var_theta(conf, (double)a.nb - 1.0);
 }
@@ -282,7 +273,7 @@ __global__ __launch_bounds__(kDB) void k_delta_pass(const RoundArgs a) {
       // u0 * v0 + u1 * v1
       const double zr = u0 * a.v0 + (u1r * v1.x - u1i * v1.y);
       const double zi = u1r * v1.y + u1i * v1.x;
-      const double dist = sqrt(2.0 * (1.0 - dmx_cabs(zr, zi)));
+      const double dist = sqrt(2.0 * (1.0 - np_cabs(zr, zi)));
       double bound = (sqrt(a.var[i]) + a.sq_err) * kUBound;
       if (a.conf_c < a.conf[i]) bound = 0.0;
       in = dist < bound;
@@ -387,22 +378,15 @@ __global__ __launch_bounds__(kDB) void k_csums2(const RefArgs a) {
 // ----------------------------------------------------------------- host side
 // HIP events around the kernels of one call (demix_last_ms); the two events
 // belong to the context
-struct DmxTimer {
-  hipEvent_t e0, e1;
-  DmxTimer(hipEvent_t a, hipEvent_t b) : e0(a), e1(b) {}
-  int start() {
-    FASST_HIP(hipEventRecord(e0, 0));
-    return FASST_OK;
-  }
-  int finish(int n_kernels) {
-    FASST_LAUNCH_CHECK();
-    g_dmx_launches += n_kernels;
-    FASST_HIP(hipEventRecord(e1, 0));
-    FASST_HIP(hipEventSynchronize(e1));
-    FASST_HIP(hipEventElapsedTime(&g_dmx_ms, e0, e1));
-    return FASST_OK;
-  }
-};
+static int dmx_start(const Events &tm) {
+  FASST_HIP(hipEventRecord(tm.e[0], 0));
+  return FASST_OK;
+}
+static int dmx_finish(const Events &tm, int n_kernels) {
+  FASST_LAUNCH_CHECK();
+  g_dmx_launches += n_kernels;
+  return elapsed_ms(tm.e[0], tm.e[1], 0, &g_dmx_ms);
+}
 
 static int stage1_blocks(size_t n) {
   const size_t b = (n + kDB - 1) / kDB;
@@ -417,11 +401,7 @@ struct demix_ctx {
   int device = 0, F = 0, N = 0, nb = 0, L = 0, maxc = 0;
   size_t n = 0;
   bool have_features = false;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ~demix_ctx() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
+  Events tm;
   DBuf<double> planes;  // [4][n]
   DBuf<unsigned char> rem, cand, masks;
   DBuf<AMax> apart;
@@ -511,14 +491,9 @@ int demix_create(int device, int F, int N, int neighbors, int max_clusters, demi
   if ((st = c->planes.alloc(4 * n)) || (st = c->rem.alloc(n)) || (st = c->cand.alloc(n)) ||
       (st = c->masks.alloc((size_t)max_clusters * n)) || (st = c->apart.alloc(kDmxMaxBlocks)) ||
       (st = c->aout.alloc(4)) || (st = c->sums.alloc((size_t)3 * F)) || (st = c->v1.alloc(F)) ||
-      (st = c->cnt.alloc(2))) {
+      (st = c->cnt.alloc(2)) || (st = c->tm.create(2))) {
     delete c;
     return st;
-  }
-  if (hipEventCreate(&c->e0) != hipSuccess || hipEventCreate(&c->e1) != hipSuccess) {
-    set_error("demix_create: hipEventCreate failed");
-    delete c;
-    return FASST_ERR_DEVICE;
   }
   *out = c;
   return FASST_OK;
@@ -566,12 +541,11 @@ int demix_features_dev(demix_ctx *c, const double *x0, const double *x1) {
   a.L = c->L;
   a.nb = c->nb;
   a.nblocks = stage1_blocks(n);
-  DmxTimer tm(c->e0, c->e1);
-  if ((st = tm.start())) return st;
+  if ((st = dmx_start(c->tm))) return st;
   k_energy_max1<<<a.nblocks, kDB>>>(a);
   k_energy_max2<<<1, kDB>>>(a);
   k_features<<<(unsigned)((n + kDB - 1) / kDB), kDB>>>(a);
-  if ((st = tm.finish(3))) return st;
+  if ((st = dmx_finish(c->tm, 3))) return st;
   g_dmx_ms += (float)pca_ms;
   c->have_features = true;
   return FASST_OK;
@@ -664,11 +638,10 @@ int demix_argmax(demix_ctx *c, double *out) {
   int st;
   RoundArgs a;
   round_args(c, a);
-  DmxTimer tm(c->e0, c->e1);
-  if ((st = tm.start())) return st;
+  if ((st = dmx_start(c->tm))) return st;
   k_argmax1<<<a.nblocks, kDB>>>(a);
   k_argmax2<<<1, kDB>>>(a);
-  if ((st = tm.finish(2))) return st;
+  if ((st = dmx_finish(c->tm, 2))) return st;
   FASST_HIP(hipMemcpy(out, c->aout.p, 4 * sizeof(double), hipMemcpyDeviceToHost));
   return FASST_OK;
 }
@@ -685,10 +658,9 @@ int demix_theta_pass(demix_ctx *c, double theta_c, double dist_bound, double *su
   round_args(c, a);
   a.theta_c = theta_c;
   a.bound = dist_bound;
-  DmxTimer tm(c->e0, c->e1);
-  if ((st = tm.start())) return st;
+  if ((st = dmx_start(c->tm))) return st;
   k_theta_pass<<<c->F, kDB>>>(a);
-  if ((st = tm.finish(1))) return st;
+  if ((st = dmx_finish(c->tm, 1))) return st;
   FASST_HIP(hipMemcpy(sums, c->sums.p, (size_t)3 * c->F * sizeof(double), hipMemcpyDeviceToHost));
   return FASST_OK;
 }
@@ -716,10 +688,9 @@ int demix_delta_pass(demix_ctx *c, int slot, double theta_c, const double *v1, d
   if (!only_centroid)
     FASST_HIP(hipMemcpy(c->v1.p, v1, (size_t)c->F * sizeof(double2), hipMemcpyHostToDevice));
   FASST_HIP(hipMemset(c->cnt.p, 0, 2 * sizeof(unsigned long long)));
-  DmxTimer tm(c->e0, c->e1);
-  if ((st = tm.start())) return st;
+  if ((st = dmx_start(c->tm))) return st;
   k_delta_pass<<<(unsigned)((c->n + kDB - 1) / kDB), kDB>>>(a);
-  if ((st = tm.finish(1))) return st;
+  if ((st = dmx_finish(c->tm, 1))) return st;
   unsigned long long h[2];
   FASST_HIP(hipMemcpy(h, c->cnt.p, sizeof(h), hipMemcpyDeviceToHost));
   counts[0] = (long)h[0];
@@ -771,10 +742,9 @@ int demix_exclusive(demix_ctx *c, int n, const int *slots, long *sizes) {
   if ((st = ref_args(c, n, slots, "demix_exclusive", a, dslots)) || (st = dsizes.alloc(n)))
     return st;
   a.sizes = dsizes.p;
-  DmxTimer tm(c->e0, c->e1);
-  if ((st = tm.start())) return st;
+  if ((st = dmx_start(c->tm))) return st;
   k_exclusive<<<(unsigned)((c->n + kDB - 1) / kDB), kDB>>>(a);
-  if ((st = tm.finish(1))) return st;
+  if ((st = dmx_finish(c->tm, 1))) return st;
   std::vector<unsigned long long> h(n);
   FASST_HIP(hipMemcpy(h.data(), dsizes.p, (size_t)n * sizeof(unsigned long long),
                       hipMemcpyDeviceToHost));
@@ -802,11 +772,10 @@ int demix_cluster_sums(demix_ctx *c, int n, const int *slots, const double *thre
   a.thr = dthr.p;
   a.part = part.p;
   a.out = out.p;
-  DmxTimer tm(c->e0, c->e1);
-  if ((st = tm.start())) return st;
+  if ((st = dmx_start(c->tm))) return st;
   k_csums1<<<dim3(a.nblocks, n), kDB>>>(a);
   k_csums2<<<n, kDB>>>(a);
-  if ((st = tm.finish(2))) return st;
+  if ((st = dmx_finish(c->tm, 2))) return st;
   FASST_HIP(hipMemcpy(sums, out.p, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost));
   return FASST_OK;
 }

@@ -1,0 +1,104 @@
+// Device helpers shared by every kernel file of the engine (gfx950).  A helper
+// with a numerical contract (np.abs bit for bit, a reciprocal within 1 ulp, a
+// fixed summation order) lives here once, so a fix reaches every caller.
+#pragma once
+#include "fasst_common.h"
+
+namespace fasst {
+
+// Device-side halt: once an iteration raises a flag (singular mixing solve,
+// dead TW) every later kernel of the batch returns at entry, so a batch of
+// iterations is enqueued without host round trips and the state stays the
+// one the flagged iteration left (flags layout in fasst_ctx.h).
+#define HALT_GUARD(h)                                   \
+  do {                                                  \
+    if ((h) && *(volatile const int *)(h)) return;      \
+  } while (0)
+
+// v_mfma_f64_16x16x4f64: D (16 x 16) = A (16 x 4) B (4 x 16) + C
+__device__ __forceinline__ d4 mfma4(double a, double b, d4 c) {
+  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+}
+// v_mfma_f64_4x4x4f64: four independent 4 x 4 blocks
+__device__ __forceinline__ double mfma44(double a, double b, double c) {
+  return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
+}
+
+// 1/x for finite normal x (the E-step's guarded det and max(V, eps), the
+// NMF / SIMM ratios' max(hat, eps)): v_rcp_f64 + two Newton steps (<= 1 ulp)
+// instead of the ~10-instruction IEEE division sequence.
+__device__ __forceinline__ double rcp_nr(double x) {
+  double r = __builtin_amdgcn_rcp(x);
+  r = fma(fma(-x, r, 1.0), r, r);
+  return fma(fma(-x, r, 1.0), r, r);
+}
+
+// np.abs(complex128): larger * sqrt(fma(r, r, 1)), r = smaller / larger
+// (NumPy's SIMD loop for complex absolute)
+__device__ __forceinline__ double np_cabs(double re, double im) {
+#pragma clang fp contract(off)
+  const double a = fabs(re), b = fabs(im);
+  if (isinf(a) || isinf(b)) return INFINITY;
+  if (a != a || b != b) return NAN;
+  const double l = a > b ? a : b, s = a > b ? b : a;
+  const double r = l == 0.0 ? 0.0 : s / l;
+  return sqrt(fma(r, r, 1.0)) * l;
+}
+
+// x ** omega as NumPy gives it (omega == 1: the identity, exact)
+__device__ __forceinline__ double pow_omega(double x, double omega) {
+  return omega == 1.0 ? x : pow(x, omega);
+}
+
+// sum over the wave's 64 lanes in a fixed butterfly: every lane ends with the
+// same value, whatever the grid
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// sum over the block in a fixed tree through s[blockDim.x] (blockDim.x a power
+// of two); every thread returns the total and s is free again on return
+__device__ __forceinline__ double block_sum(double x, double *s) {
+  s[threadIdx.x] = x;
+  __syncthreads();
+  for (int w = blockDim.x >> 1; w > 0; w >>= 1) {
+    if (threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
+    __syncthreads();
+  }
+  const double r = s[0];
+  __syncthreads();
+  return r;
+}
+
+__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
+  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+__device__ __forceinline__ double2 cconj(double2 a) { return make_double2(a.x, -a.y); }
+__device__ __forceinline__ double2 cadd(double2 a, double2 b) {
+  return make_double2(a.x + b.x, a.y + b.y);
+}
+__device__ __forceinline__ double2 csub(double2 a, double2 b) {
+  return make_double2(a.x - b.x, a.y - b.y);
+}
+__device__ __forceinline__ double2 cscale(double2 a, double s) {
+  return make_double2(a.x * s, a.y * s);
+}
+
+// raw-buffer access to streamed operands: a wave-uniform resource (SGPRs,
+// formed on the scalar unit) + a 32-bit per-lane byte offset vo + a uniform
+// byte offset so, so no 64-bit VALU address arithmetic per access and every
+// load is issued unconditionally (AUX 2 = non-temporal).  The resource spans
+// 2 GB from p: the callers keep their offsets inside their allocations.
+typedef unsigned buf_u2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const double *p) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(p), 0, 0x7fffffff, 0x00020000);
+}
+template <int AUX>
+__device__ __forceinline__ double buf_ld(__amdgpu_buffer_rsrc_t r, unsigned vo, unsigned so) {
+  const buf_u2 x = __builtin_amdgcn_raw_buffer_load_b64(r, (int)vo, (int)so, AUX);
+  return __builtin_bit_cast(double, x);
+}
+
+}  // namespace fasst

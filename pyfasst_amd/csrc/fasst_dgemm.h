@@ -23,7 +23,7 @@
 // Requires lda, ldb and the contiguous extent of A (K for NN, M for TA) and
 // N to be even (16-byte alignment); the host falls back otherwise.
 #pragma once
-#include "fasst_common.h"
+#include "fasst_device.h"
 
 namespace fasst {
 
@@ -44,10 +44,6 @@ constexpr int dgemm_sa() { return TA ? kDBK * kDPK : kDBM * kDPM; }
 constexpr int dgemm_sb() { return kDBK * kDPK; }
 template <bool TA>
 constexpr size_t dgemm_smem() { return 2 * (size_t)(dgemm_sa<TA>() + dgemm_sb()) * sizeof(double); }
-
-__device__ __forceinline__ fasst::d4 dmfma(double a, double b, fasst::d4 c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 
 // IG > 0: __builtin_amdgcn_iglp_opt(IG - 1) scheduling hint in the chunk loop
 // (A/B in tools/ubench_dgemm2.hip only)
@@ -147,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void k_dgemm(const DgemmArgs g) {
 #pragma unroll
           for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i][j] = dmfma(a[u][i], b[u][j], acc[i][j]);
+            for (int i = 0; i < 4; ++i) acc[i][j] = mfma4(a[u][i], b[u][j], acc[i][j]);
       } else {   // edge tile: 16-row blocks wholly past M issue no MFMAs
 #pragma unroll
         for (int u = 0; u < 2; ++u)
@@ -155,7 +151,7 @@ __global__ __launch_bounds__(256, 2) void k_dgemm(const DgemmArgs g) {
           for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-              if (i < nib) acc[i][j] = dmfma(a[u][i], b[u][j], acc[i][j]);
+              if (i < nib) acc[i][j] = mfma4(a[u][i], b[u][j], acc[i][j]);
       }
       if (SM == 1 && h == 0 && c + 1 < nch) sstore(odd ? sA0 : sA1, odd ? sB0 : sB1);
     }

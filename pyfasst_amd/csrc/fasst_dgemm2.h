@@ -25,7 +25,7 @@
 // an even leading dimension and a 16-byte aligned base; otherwise the operand
 // is loaded in 4-byte pieces (A4 / B4), which only needs 4-byte alignment.
 #pragma once
-#include "fasst_common.h"
+#include "fasst_device.h"
 
 #include <type_traits>
 
@@ -72,10 +72,6 @@ typedef __attribute__((address_space(1))) void d2_gbl_t;
 
 // 16 zero bytes per lane for the loads that fall outside the operands
 __device__ __attribute__((aligned(16))) double g_d2_zero[2];
-
-__device__ __forceinline__ double d2_mfma(double a, double b, double c) {
-  return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
-}
 
 // (FASST_NO_LDS_PAIRING: keep the operand reads as ds_read_b64, 2 LDS cycles
 // each, not paired into ds_read2_b64 at 8)
@@ -253,7 +249,7 @@ void k_dgemm2(const Dgemm2Args g) {
               if constexpr (M16)
                 acc4[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[sl][i], b[sl][j], acc4[i][j], 0, 0, 0);
               else
-                acc1[i][j] = d2_mfma(a[sl][i], b[sl][j], acc1[i][j]);
+                acc1[i][j] = mfma44(a[sl][i], b[sl][j], acc1[i][j]);
             }
       }
     }

@@ -186,17 +186,11 @@ int dict_wf0_stft(int device, int n_cols, const double *f1, const double *f2,
   a.wlen = wlen;
   a.nfft = nfft;
   a.logn = ilog2(nfft);
-  hipEvent_t e0, e1;
-  FASST_HIP(hipEventCreate(&e0));
-  FASST_HIP(hipEventCreate(&e1));
-  FASST_HIP(hipEventRecord(e0, 0));
+  Events tm;
+  if ((st = tm.start(0))) return st;
   k_wf0_column<<<n_cols, 256, smem>>>(a);
   FASST_LAUNCH_CHECK();
-  FASST_HIP(hipEventRecord(e1, 0));
-  FASST_HIP(hipEventSynchronize(e1));
-  FASST_HIP(hipEventElapsedTime(&g_dict_ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  if ((st = elapsed_ms(tm.e[0], tm.e[1], 0, &g_dict_ms))) return st;
   FASST_HIP(hipMemcpy(wf0, dout.p, (size_t)F * n_cols * sizeof(double), hipMemcpyDeviceToHost));
   return FASST_OK;
 }
@@ -271,17 +265,11 @@ int dict_odgd(int device, int n_cols, const double *f1, const double *f2, const 
   a.length_odgd = length_odgd;
   a.nfft = nfft;
   a.logn = ilog2(nfft);
-  hipEvent_t e0, e1;
-  FASST_HIP(hipEventCreate(&e0));
-  FASST_HIP(hipEventCreate(&e1));
-  FASST_HIP(hipEventRecord(e0, 0));
+  Events tm;
+  if ((st = tm.start(0))) return st;
   k_odgd_column<<<n_cols, 256, smem>>>(a);
   FASST_LAUNCH_CHECK();
-  FASST_HIP(hipEventRecord(e1, 0));
-  FASST_HIP(hipEventSynchronize(e1));
-  FASST_HIP(hipEventElapsedTime(&g_dict_ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  if ((st = elapsed_ms(tm.e[0], tm.e[1], 0, &g_dict_ms))) return st;
   if (odgd) FASST_HIP(hipMemcpy(odgd, dodgd.p, C * L * sizeof(double2), hipMemcpyDeviceToHost));
   if (spectrum)
     FASST_HIP(hipMemcpy(spectrum, dspec.p, C * N * sizeof(double2), hipMemcpyDeviceToHost));

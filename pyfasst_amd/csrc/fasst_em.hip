@@ -24,6 +24,7 @@
 // because the mixing a_r is constant over t.  The t-reductions shrink from
 // R^2 complex products per (f,t) to J(J+1)/2 x 4 + 9J real FMAs.
 #include "fasst_ctx.h"
+#include "fasst_device.h"
 #include "fasst_twc.h"
 
 #include <cmath>
@@ -42,15 +43,6 @@ void set_error(const char *fmt, ...) {
   g_err = buf;
 }
 
-// Device-side halt: once an iteration raises a flag (singular mixing solve,
-// dead TW) every later kernel of the batch returns at entry, so a batch of
-// iterations is enqueued without host round trips and the state stays the
-// one the flagged iteration left (flags layout in fasst_ctx.h).
-#define HALT_GUARD(h)                                   \
-  do {                                                  \
-    if ((h) && *(volatile const int *)(h)) return;      \
-  } while (0)
-
 // XCD-aware logical block: workgroups b, b + 8, ... of a launch share an XCD
 // (dispatch is round-robin over the 8 XCDs, for speed only, never
 // correctness); the bijective remap of cdna_hip_programming.md gives each XCD
@@ -67,10 +59,6 @@ __device__ __forceinline__ dim3 xcd_block() {
   return dim3(L % nx, (L / nx) % ny, L / (nx * ny));
 }
 
-__device__ __forceinline__ d4 mfma4(double a, double b, d4 c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
 // max(x, y) as ONE v_max_f64: fmax() lowers to llvm.maxnum, whose operands
 // the backend first canonicalises (a second v_max_f64 each) unless it can
 // prove them canonical, which it cannot for MFMA results.  For the finite
@@ -79,15 +67,6 @@ __device__ __forceinline__ double vmax_f64(double x, double y) {
   double r;
   asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
   return r;
-}
-
-// 1/x for finite normal x (the E-step's guarded det and max(V, eps)):
-// v_rcp_f64 + two Newton steps (<= 1 ulp) instead of the ~10-instruction
-// IEEE division sequence.
-__device__ __forceinline__ double rcp_nr(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return fma(fma(-x, r, 1.0), r, r);
 }
 
 // ---------------------------------------------------------------- prep
@@ -269,9 +248,6 @@ struct EArgs {
 // streams Cx once, forms V, Sigma_x and its inverse once per point, and keeps
 // two waves per SIMD; the 72 FMAs per point leave the VALU for the matrix
 // pipe (4x4x4_4b runs at 74.7 TF on this chip, profiles/r1_ubench_fp64.txt).
-__device__ __forceinline__ double mfma44(double a, double b, double c) {
-  return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
-}
 
 // Reader-formed pair operands (RP, J >= 4): the slab holds V, P and N only,
 // and the reader forms the pair operands V_j1 V_j2 itself.  With the sources
@@ -357,18 +333,10 @@ static constexpr size_t estep_mx_smem() {
 // raw-buffer forms of the E-step's streaming accesses: wave-uniform
 // resource (SGPRs, formed on the scalar unit) + 32-bit per-lane offset, so
 // no 64-bit VALU address arithmetic per access (aux 2 = non-temporal)
-typedef unsigned es_u2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t es_rsrc(const double *p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(p), 0, 0x7fffffff, 0x00020000);
-}
-template <int AUX>
-__device__ __forceinline__ double es_ld(__amdgpu_buffer_rsrc_t r, unsigned vo, unsigned so) {
-  const es_u2 x = __builtin_amdgcn_raw_buffer_load_b64(r, (int)vo, (int)so, AUX);
-  return __builtin_bit_cast(double, x);
-}
+// (buf_rsrc / buf_ld of fasst_device.h; the store is the E-step's alone)
 template <int AUX>
 __device__ __forceinline__ void es_st(double v, __amdgpu_buffer_rsrc_t r, unsigned vo, unsigned so) {
-  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(es_u2, v), r, (int)vo, (int)so, AUX);
+  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(buf_u2, v), r, (int)vo, (int)so, AUX);
 }
 
 // (J = 4 at K = 128: the 64 KB W tile leaves one block per CU, so one wave
@@ -534,10 +502,10 @@ void k_estep_mx(const EArgs a) {
       if constexpr (SA) {
         const size_t ro = (size_t)t0 * a.Fp;
         const unsigned so = (unsigned)(4 * i * a.Fp) * 8u;
-        c[0][i] = es_ld<2>(es_rsrc(a.cx00 + ro), vo_cx, so);
-        c[1][i] = es_ld<2>(es_rsrc(a.cx11 + ro), vo_cx, so);
-        c[2][i] = es_ld<2>(es_rsrc(a.cxr + ro), vo_cx, so);
-        c[3][i] = es_ld<2>(es_rsrc(a.cxi + ro), vo_cx, so);
+        c[0][i] = buf_ld<2>(buf_rsrc(a.cx00 + ro), vo_cx, so);
+        c[1][i] = buf_ld<2>(buf_rsrc(a.cx11 + ro), vo_cx, so);
+        c[2][i] = buf_ld<2>(buf_rsrc(a.cxr + ro), vo_cx, so);
+        c[3][i] = buf_ld<2>(buf_rsrc(a.cxi + ro), vo_cx, so);
       } else {
         const size_t off = (size_t)(t0 + tq + 4 * i) * a.Fp + f;
         c[0][i] = __builtin_nontemporal_load(a.cx00 + off);
@@ -578,7 +546,7 @@ void k_estep_mx(const EArgs a) {
       const double *tw = a.TW + ((size_t)j * KP + tq) * a.Tp + t0 + fl;
 #pragma unroll
       for (int s = 0; s < NKS; ++s)
-        twv[j][s] = SA ? es_ld<0>(es_rsrc(a.TW + t0), vo_tw, (unsigned)((j * KP + 4 * s) * a.Tp) * 8u)
+        twv[j][s] = SA ? buf_ld<0>(buf_rsrc(a.TW + t0), vo_tw, (unsigned)((j * KP + 4 * s) * a.Tp) * 8u)
                        : tw[(size_t)(4 * s) * a.Tp];
     }
     if constexpr (!CXE) load_cx(tt, cxv);  // this tile's Cx (in flight with the TW operands)
@@ -593,7 +561,7 @@ void k_estep_mx(const EArgs a) {
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
           const int s = s0 + c;
-          ta[sl][c] = es_ld<0>(es_rsrc(a.TW + t0), vo_tw, (unsigned)((j * KP + 4 * s) * a.Tp) * 8u);
+          ta[sl][c] = buf_ld<0>(buf_rsrc(a.TW + t0), vo_tw, (unsigned)((j * KP + 4 * s) * a.Tp) * 8u);
           if constexpr (!WL)
             wa[sl][c] = a.Wkf[lofs + ((size_t)j * KP + tq + 4 * s) * a.Fp + f];
         }
@@ -625,7 +593,7 @@ void k_estep_mx(const EArgs a) {
       auto ld = [&](int j, int s0, int sl) {
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
-          ta[sl][c] = es_ld<0>(es_rsrc(a.TW + t0), vo_tw, (unsigned)((j * KP + 4 * (s0 + c)) * a.Tp) * 8u);
+          ta[sl][c] = buf_ld<0>(buf_rsrc(a.TW + t0), vo_tw, (unsigned)((j * KP + 4 * (s0 + c)) * a.Tp) * 8u);
           wa[sl][c] = a.Wkf[lofs + ((size_t)j * KP + tq + 4 * (s0 + c)) * a.Fp + f];
         }
       };
@@ -663,11 +631,11 @@ void k_estep_mx(const EArgs a) {
 #pragma unroll
         for (int s = 0; s < NKS; ++s)
           tc[s] = PFS || j == 0 ? tn[s]
-                               : es_ld<0>(es_rsrc(a.TW + t0), vo_tw, (unsigned)((j * KP + 4 * s) * a.Tp) * 8u);
+                               : buf_ld<0>(buf_rsrc(a.TW + t0), vo_tw, (unsigned)((j * KP + 4 * s) * a.Tp) * 8u);
         if (PFS && j + 1 < J) {
 #pragma unroll
           for (int s = 0; s < NKS; ++s)
-            tn[s] = es_ld<0>(es_rsrc(a.TW + t0), vo_tw, (unsigned)(((j + 1) * KP + 4 * s) * a.Tp) * 8u);
+            tn[s] = buf_ld<0>(buf_rsrc(a.TW + t0), vo_tw, (unsigned)(((j + 1) * KP + 4 * s) * a.Tp) * 8u);
         }
         __builtin_amdgcn_sched_barrier(0);
         v[j] = d4{0.0, 0.0, 0.0, 0.0};
@@ -782,7 +750,7 @@ void k_estep_mx(const EArgs a) {
         }
         const double val = fabs(fma(Vj, q, 1.0)) * fmin(Vj * (1.0 / kEps), 1.0);
         if constexpr (SA)
-          es_st<2>(val, es_rsrc(a.hatW + ((size_t)j * a.Tp + t0) * a.Fp), vo_cx,
+          es_st<2>(val, buf_rsrc(a.hatW + ((size_t)j * a.Tp + t0) * a.Fp), vo_cx,
                                (unsigned)(4 * i * a.Fp) * 8u);
         else
           __builtin_nontemporal_store(val, a.hatW + ((size_t)j * a.Tp + t) * a.Fp + f);
@@ -1618,19 +1586,6 @@ struct MArgs {
   const int *halt;
 };
 
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ double2 cconj(double2 a) { return make_double2(a.x, -a.y); }
-__device__ __forceinline__ double2 cadd(double2 a, double2 b) {
-  return make_double2(a.x + b.x, a.y + b.y);
-}
-__device__ __forceinline__ double2 csub(double2 a, double2 b) {
-  return make_double2(a.x - b.x, a.y - b.y);
-}
-__device__ __forceinline__ double2 cscale(double2 a, double s) {
-  return make_double2(a.x * s, a.y * s);
-}
 __device__ __forceinline__ double2 cdiv(double2 a, double2 b) {
   // Smith's algorithm (as the C99 / numpy complex division)
   if (fabs(b.x) >= fabs(b.y)) {
@@ -2051,7 +2006,6 @@ struct UArgs {
   double *pmax;
   const int *halt;
 };
-__device__ double block_sum(double x, double *s);
 // FB *= (num / max(den, eps))^omega with den = FW . rowsum(TW) (see
 // k_fb_contract) or, for one of several spectral components, the contracted
 // denominator; then W_new = FB . FW in both layouts.
@@ -2994,18 +2948,6 @@ struct RArgs {
   unsigned tbmask;   // slots with time blobs: their restart test is k_tb_renorm's
   const int *halt;
 };
-
-__device__ double block_sum(double x, double *s) {
-  s[threadIdx.x] = x;
-  __syncthreads();
-  for (int w = blockDim.x >> 1; w > 0; w >>= 1) {
-    if (threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-    __syncthreads();
-  }
-  const double r = s[0];
-  __syncthreads();
-  return r;
-}
 
 // renormalize_parameters (audioModel.py:1991-2037) in two passes over
 // (source, chunk) blocks.  Stage 1: per bin chunk, the column maxima of FB

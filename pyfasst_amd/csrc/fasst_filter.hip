@@ -250,18 +250,6 @@ static int filter_shape(int L, int Min, int Mout, const void *W, int w_tv, int n
 static thread_local bool t_filter_timing = false;
 static thread_local double t_filter_ms = 0.0, t_filter_tr_ms = 0.0;
 
-struct FiltEvents {
-  hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-  int create() {
-    for (auto &x : e) FASST_HIP(hipEventCreate(&x));
-    return FASST_OK;
-  }
-  ~FiltEvents() {
-    for (auto x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-};
-
 // Every pointer a device pointer; returns after the kernels have finished.
 static int filter_run(hipStream_t st, const double *dx, int L, int Min, int Mout, const double2 *dW,
                       int w_tv, int nwf, int w_layout, const double *dawin, const double *dswin,
@@ -279,9 +267,9 @@ static int filter_run(hipStream_t st, const double *dx, int L, int Min, int Mout
   FASST_HIP(hipMemcpyAsync(dtwf.p, twf.data(), twf.size() * sizeof(double2), hipMemcpyHostToDevice, st));
   FASST_HIP(hipMemcpyAsync(dtwi.p, twi.data(), twi.size() * sizeof(double2), hipMemcpyHostToDevice, st));
   const bool timing = t_filter_timing;
-  FiltEvents ev;
+  Events ev;   // start, after the transpose, end
   if (timing) {
-    if ((rc = ev.create())) return rc;
+    if ((rc = ev.create(3))) return rc;
     FASST_HIP(hipEventRecord(ev.e[0], st));
   }
   if (transpose)   // [MM][F][nwf] -> [MM][nwf][F]
@@ -317,12 +305,11 @@ static int filter_run(hipStream_t st, const double *dx, int L, int Min, int Mout
   k_ola_ch<<<dim3((s.len_out + 255) / 256, Mout), 256, 0, st>>>(dframes.p, s.nframes, wlen, hop,
                                                                 dswin, dawin, dy, s.len_out, Mout);
   FASST_LAUNCH_CHECK();
-  if (timing) FASST_HIP(hipEventRecord(ev.e[2], st));
+  float t01 = 0.f, t02 = 0.f;
+  if (timing && (rc = elapsed_ms(ev.e[0], ev.e[2], st, &t02))) return rc;
   FASST_HIP(hipStreamSynchronize(st));   // the scratch above is freed on return
   if (timing) {
-    float t01 = 0.f, t02 = 0.f;
     FASST_HIP(hipEventElapsedTime(&t01, ev.e[0], ev.e[1]));
-    FASST_HIP(hipEventElapsedTime(&t02, ev.e[0], ev.e[2]));
     t_filter_ms = t02;
     t_filter_tr_ms = transpose ? t01 : 0.0;
   }

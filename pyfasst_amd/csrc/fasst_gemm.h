@@ -16,7 +16,7 @@
 // k_gemm_reduce sums in fixed order (deterministic).
 #pragma once
 
-#include "fasst_common.h"
+#include "fasst_device.h"
 
 namespace fasst {
 
@@ -34,10 +34,6 @@ struct GemmArgs {
   int kchunk;       // K range per split (multiple of kGBK)
   size_t slab;      // element offset between split-K partial slabs of one C
 };
-
-__device__ __forceinline__ fasst::d4 gmfma(double a, double b, fasst::d4 c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 
 template <bool TA, bool TB, int NB, int WGM, int WTM, int WTN>
 __global__ __launch_bounds__(256, 2) void k_gemm(const GemmArgs g) {
@@ -154,7 +150,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm(const GemmArgs g) {
         for (int j = 0; j < WTN; ++j) {
           const double bv = sB[b * kGBK * PB + kr * PB + wn * 16 * WTN + j * 16 + fl];
 #pragma unroll
-          for (int i = 0; i < WTM; ++i) acc[b][i][j] = gmfma(a[i], bv, acc[b][i][j]);
+          for (int i = 0; i < WTM; ++i) acc[b][i][j] = mfma4(a[i], bv, acc[b][i][j]);
         }
       }
     }

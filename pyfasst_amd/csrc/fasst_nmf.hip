@@ -75,33 +75,6 @@ __global__ void k_nmf_h(double *__restrict__ H, const double *__restrict__ num,
     H[i] *= num[i] / fmax(den[i], kNmfEps);
 }
 
-// 1/x for finite normal x > 0: v_rcp_f64 + two Newton steps (<= 1 ulp), as
-// the FASST E-step (fasst_em.hip rcp_nr)
-__device__ __forceinline__ double nmf_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return fma(fma(-x, r, 1.0), r, r);
-}
-
-// raw-buffer loads for the fused contractions: wave-uniform resource in
-// SGPRs + a 32-bit lane offset, so every load of a tile is issued
-// unconditionally (a guarded pointer load compiles into an exec branch per
-// load, and the branches made the compiler wait for ALL outstanding loads --
-// the next tile's prefetch included -- before each tile's MFMAs).  An offset
-// of kNmfOOB is outside every resource and reads 0.0; otherwise the accesses
-// stay inside the (padded, zero-filled) allocations, see nmf_create.
-typedef unsigned nmf_u2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t nmf_rsrc(const double *p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(p), 0, 0x7fffffff, 0x00020000);
-}
-__device__ __forceinline__ double nmf_ld(__amdgpu_buffer_rsrc_t r, unsigned vo) {
-  return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, (int)vo, 0, 0));
-}
-
-__device__ __forceinline__ d4 nmfma(double a, double b, d4 c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
 // Fused IS-NMF contractions (K a multiple of 16, <= 64): the model hat = W H
 // is recomputed tile by tile on the MFMA pipe and never stored, the ratios
 // X = SX / max(hat^2, eps), Y = 1 / max(hat, eps) stay in registers, and the
@@ -128,6 +101,13 @@ __device__ __forceinline__ d4 nmfma(double a, double b, d4 c) {
 // in index order: deterministic.
 constexpr int kNmfPW = 2;
 
+// raw-buffer loads (buf_rsrc / buf_ld, and the 16-byte form here): every load
+// of a tile is issued unconditionally (a guarded pointer load compiles into
+// an exec branch per load, and the branches made the compiler wait for ALL
+// outstanding loads -- the next tile's prefetch included -- before each
+// tile's MFMAs).  An offset of kNmfOOB is outside every resource and reads
+// 0.0; otherwise the accesses stay inside the (padded, zero-filled)
+// allocations, see nmf_create.
 typedef unsigned nmf_u4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void nmf_ld2(__amdgpu_buffer_rsrc_t r, unsigned vo, double &a, double &b) {
   const nmf_u4 x = __builtin_amdgcn_raw_buffer_load_b128(r, (int)vo, 0, 0);
@@ -147,7 +127,7 @@ template <int NKC>
 __device__ __forceinline__ void nmf_ld_con(__amdgpu_buffer_rsrc_t r, unsigned vo, int fl, double (&d)[NKC]) {
 #pragma unroll
   for (int m = 0; m < NKC / 2; ++m) nmf_ld2(r, vo + 256u * m, d[2 * m], d[2 * m + 1]);
-  if constexpr (NKC & 1) d[NKC - 1] = nmf_ld(r, vo - 8u * fl + 128u * (NKC - 1));
+  if constexpr (NKC & 1) d[NKC - 1] = buf_ld<0>(r, vo - 8u * fl + 128u * (NKC - 1), 0);
 }
 template <int NKC>
 __device__ __forceinline__ constexpr int nmf_con_k(int kc, int fl) {
@@ -218,7 +198,7 @@ __global__ __launch_bounds__(256, 1) void k_nmf_wnum(const double *__restrict__ 
   const int lane = threadIdx.x & 63, fl = lane & 15, tq = lane >> 4;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g0 = blockIdx.x * 16 * PW, ntt = (N + 15) / 16;
-  const __amdgpu_buffer_rsrc_t rW = nmf_rsrc(W), rH = nmf_rsrc(Ht);
+  const __amdgpu_buffer_rsrc_t rW = buf_rsrc(W), rH = buf_rsrc(Ht);
   double wk[PW][NKS];  // bins past F: W's zero pad rows
 #pragma unroll
   for (int p = 0; p < PW; ++p) nmf_ld_hat(rW, (unsigned)(((g0 + PW * fl + p) * K + 2 * tq) * 8), wk[p]);
@@ -239,7 +219,7 @@ __global__ __launch_bounds__(256, 1) void k_nmf_wnum(const double *__restrict__ 
     const int t0 = tt * 16;
     const unsigned ho = (unsigned)(t0 * K * 8);
     // the SX stream (HBM) first, then the L2-resident Ht tile
-    const __amdgpu_buffer_rsrc_t rS = nmf_rsrc(SXt + (size_t)t0 * F);
+    const __amdgpu_buffer_rsrc_t rS = buf_rsrc(SXt + (size_t)t0 * F);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       nmf_ld2(rS, vo_sx + (unsigned)(4 * i * F * 8), sxv[slot][i][0], sxv[slot][i][1]);
@@ -256,10 +236,10 @@ __global__ __launch_bounds__(256, 1) void k_nmf_wnum(const double *__restrict__ 
       d4 v0 = d4{0.0, 0.0, 0.0, 0.0}, v1 = v0, v2 = v0, v3 = v0;
 #pragma unroll
       for (int s = 0; s < NKS; s += 4) {
-        v0 = nmfma(th[cs][s], wk[p][s], v0);
-        v1 = nmfma(th[cs][s + 1], wk[p][s + 1], v1);
-        v2 = nmfma(th[cs][s + 2], wk[p][s + 2], v2);
-        v3 = nmfma(th[cs][s + 3], wk[p][s + 3], v3);
+        v0 = mfma4(th[cs][s], wk[p][s], v0);
+        v1 = mfma4(th[cs][s + 1], wk[p][s + 1], v1);
+        v2 = mfma4(th[cs][s + 2], wk[p][s + 2], v2);
+        v3 = mfma4(th[cs][s + 3], wk[p][s + 3], v3);
       }
       hv[p] = (v0 + v1) + (v2 + v3);
     }
@@ -272,15 +252,15 @@ __global__ __launch_bounds__(256, 1) void k_nmf_wnum(const double *__restrict__ 
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const double h = v[i];
-        x[i] = sxv[cs][i][p] * nmf_rcp(fmax(h * h, kNmfEps));
-        y[i] = nmf_rcp(fmax(h, kNmfEps));
+        x[i] = sxv[cs][i][p] * rcp_nr(fmax(h * h, kNmfEps));
+        y[i] = rcp_nr(fmax(h, kNmfEps));
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int kc = 0; kc < NKC; ++kc) {
-          num[p][kc] = nmfma(x[i], hb[cs][i][kc], num[p][kc]);
-          den[p][kc] = nmfma(y[i], hb[cs][i][kc], den[p][kc]);
+          num[p][kc] = mfma4(x[i], hb[cs][i][kc], num[p][kc]);
+          den[p][kc] = mfma4(y[i], hb[cs][i][kc], den[p][kc]);
         }
     }
   };
@@ -325,7 +305,7 @@ __global__ __launch_bounds__(256, 1) void k_nmf_hnum(const double *__restrict__ 
   const int lane = threadIdx.x & 63, fl = lane & 15, tq = lane >> 4;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int t0g = blockIdx.x * 16 * PW, nft = (F + 15) / 16;
-  const __amdgpu_buffer_rsrc_t rW = nmf_rsrc(W), rH = nmf_rsrc(Ht);
+  const __amdgpu_buffer_rsrc_t rW = buf_rsrc(W), rH = buf_rsrc(Ht);
   // frames past N read the next Ht rows or its zero pad: finite, and their
   // output columns are never stored
   double bt[PW][NKS], hsv[NKS];
@@ -353,7 +333,7 @@ __global__ __launch_bounds__(256, 1) void k_nmf_hnum(const double *__restrict__ 
   auto load = [&](int ft, int slot) {
     const int f0 = ft * 16;
     const unsigned wo = (unsigned)(f0 * K * 8);
-    const __amdgpu_buffer_rsrc_t rS = nmf_rsrc(SX + (size_t)f0 * N);
+    const __amdgpu_buffer_rsrc_t rS = buf_rsrc(SX + (size_t)f0 * N);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       nmf_ld2(rS, vo_sx + (unsigned)(4 * i * N * 8), sxv[slot][i][0], sxv[slot][i][1]);
@@ -368,10 +348,10 @@ __global__ __launch_bounds__(256, 1) void k_nmf_hnum(const double *__restrict__ 
       d4 v0 = d4{0.0, 0.0, 0.0, 0.0}, v1 = v0, v2 = v0, v3 = v0;
 #pragma unroll
       for (int s = 0; s < NKS; s += 4) {
-        v0 = nmfma(ao[cs][s], bt[p][s], v0);
-        v1 = nmfma(ao[cs][s + 1], bt[p][s + 1], v1);
-        v2 = nmfma(ao[cs][s + 2], bt[p][s + 2], v2);
-        v3 = nmfma(ao[cs][s + 3], bt[p][s + 3], v3);
+        v0 = mfma4(ao[cs][s], bt[p][s], v0);
+        v1 = mfma4(ao[cs][s + 1], bt[p][s + 1], v1);
+        v2 = mfma4(ao[cs][s + 2], bt[p][s + 2], v2);
+        v3 = mfma4(ao[cs][s + 3], bt[p][s + 3], v3);
       }
       hv[p] = (v0 + v1) + (v2 + v3);
     }
@@ -382,15 +362,15 @@ __global__ __launch_bounds__(256, 1) void k_nmf_hnum(const double *__restrict__ 
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const double h = v[i];
-        x[i] = sxv[cs][i][p] * nmf_rcp(fmax(h * h, kNmfEps));
-        y[i] = nmf_rcp(fmax(h, kNmfEps));
+        x[i] = sxv[cs][i][p] * rcp_nr(fmax(h * h, kNmfEps));
+        y[i] = rcp_nr(fmax(h, kNmfEps));
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int kc = 0; kc < NKC; ++kc) {
-          num[p][kc] = nmfma(x[i], bw[cs][i][kc], num[p][kc]);
-          den[p][kc] = nmfma(y[i], bw[cs][i][kc], den[p][kc]);
+          num[p][kc] = mfma4(x[i], bw[cs][i][kc], num[p][kc]);
+          den[p][kc] = mfma4(y[i], bw[cs][i][kc], den[p][kc]);
         }
     }
   };
@@ -689,8 +669,6 @@ struct nmf_ctx {
 
 namespace {
 
-int egrid_n(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 8192); }
-
 int model_xy(nmf_ctx *c) {
   const double *Bs[1] = {c->H.p};
   double *Cs[1] = {c->hat.p};
@@ -698,7 +676,7 @@ int model_xy(nmf_ctx *c) {
                                  c->work.p);
   if (st) return st;
   const size_t FN = (size_t)c->F * c->N;
-  k_nmf_xy<<<egrid_n(FN), 256, 0, c->stream>>>(c->hat.p, c->SX.p, c->X.p, c->Y.p, FN);
+  k_nmf_xy<<<egrid(FN), 256, 0, c->stream>>>(c->hat.p, c->SX.p, c->X.p, c->Y.p, FN);
   FASST_LAUNCH_CHECK();
   return FASST_OK;
 }
@@ -717,7 +695,7 @@ static void nmf_fused(nmf_ctx *c, int update_w, int update_h) {
   // the W update leaves W un-renormalised and H un-rescaled: the H update
   // (or k_nmf_hscale_t) applies both (k_nmf_h_part)
   const double *ws = update_w ? c->wsum.p : nullptr;
-  const int eg = egrid_n((size_t)K * std::max(N, F));
+  const int eg = egrid((size_t)K * std::max(N, F));
   if (update_h) {
     k_nmf_hnum<NKC><<<dim3(gh, c->ng_h), 256, 0, c->stream>>>(c->W.p, c->Ht.p, nullptr, c->SX.p,
                                                               c->part.p, F, N, c->fpc_h);
@@ -748,7 +726,7 @@ int nmf_iteration(nmf_ctx *c, int update_w, int update_h) {
     if ((st = gemm<false, true, 2>(c->stream, c->H.p, N, Bs, N, Cs, F, K, F, N, c->work.p)))
       return st;
     k_nmf_w<<<K, 256, 0, c->stream>>>(c->W.p, c->numT.p, c->denT.p, c->s.p, F, K);
-    k_nmf_hscale<<<egrid_n((size_t)K * N), 256, 0, c->stream>>>(c->H.p, c->s.p, K, N);
+    k_nmf_hscale<<<egrid((size_t)K * N), 256, 0, c->stream>>>(c->H.p, c->s.p, K, N);
     FASST_LAUNCH_CHECK();
   }
   if (update_h) {
@@ -757,7 +735,7 @@ int nmf_iteration(nmf_ctx *c, int update_w, int update_h) {
     double *Cs[2] = {c->num.p, c->den.p};
     if ((st = gemm<true, false, 2>(c->stream, c->W.p, K, Bs, N, Cs, N, K, N, F, c->work.p)))
       return st;
-    k_nmf_h<<<egrid_n((size_t)K * N), 256, 0, c->stream>>>(c->H.p, c->num.p, c->den.p,
+    k_nmf_h<<<egrid((size_t)K * N), 256, 0, c->stream>>>(c->H.p, c->num.p, c->den.p,
                                                            (size_t)K * N);
     FASST_LAUNCH_CHECK();
   }

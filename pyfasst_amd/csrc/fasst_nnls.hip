@@ -22,7 +22,7 @@
 // z = G_PP^-1 c_P, while min z <= 0 step x towards z by the largest feasible
 // alpha and drop the indices that reach zero.  The lanes of the wave share
 // the work of every dot product / axpy; the wave's vectors sit in LDS.
-#include "fasst_common.h"
+#include "fasst_device.h"
 #include "fasst_gemm.h"
 #include "../../include/fasst_nnls.h"
 
@@ -42,12 +42,6 @@ struct NnlsArgs {
   int n, nf, maxiter;
   double tol, add_eps;   // tol: relative to max |c| of the frame
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 // forward solve L[0:p, 0:p] y = b (row-major L, pitch n), y in LDS
 __device__ void nnls_fwd(const double *L, int n, const double *b, double *y, int p, int lane) {

@@ -83,18 +83,6 @@ __global__ void k_sf_hatw(const double *__restrict__ ws, double *__restrict__ ha
   }
 }
 
-__device__ __forceinline__ double sf_block_sum(double x, double *s_red) {
-  s_red[threadIdx.x] = x;
-  __syncthreads();
-  for (int w = blockDim.x / 2; w > 0; w >>= 1) {
-    if (threadIdx.x < w) s_red[threadIdx.x] += s_red[threadIdx.x + w];
-    __syncthreads();
-  }
-  const double r = s_red[0];
-  __syncthreads();
-  return r;
-}
-
 // renormalize_parameters, the spatial half (:1993-1999), one block per source:
 // energy = mean |params|^2 ('inst': the C x r matrix, bin 0 of its constant
 // rows; 'conv': r x C x F), params /= sqrt(energy)
@@ -109,7 +97,7 @@ __global__ __launch_bounds__(256) void k_sf_energy(double2 *__restrict__ mix, in
     const double2 z = mix[(size_t)r0 * 2 * F + (i / nf) * F + i % nf];
     s += z.x * z.x + z.y * z.y;
   }
-  const double e = sf_block_sum(s, s_red) / (double)n;
+  const double e = block_sum(s, s_red) / (double)n;
   const double q = sqrt(e);
   for (size_t i = threadIdx.x; i < (size_t)(r1 - r0) * 2 * F; i += 256) {
     double2 z = mix[(size_t)r0 * 2 * F + i];
@@ -168,7 +156,7 @@ __global__ __launch_bounds__(256) void k_sf_renorm(double *__restrict__ FB, doub
     TW[i] = v;
     s += v;
   }
-  const double tot = sf_block_sum(s, s_red);
+  const double tot = block_sum(s, s_red);
   const int dead = tot < kEps ? 1 : 0;
   const double ge = tot / (double)n;
   if (tid == 0) {

@@ -218,7 +218,6 @@ struct sfnmf_ctx {
 
 namespace {
 
-int egrid(size_t n) { return (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 8192)); }
 dim3 tgrid(int cols, int rows) { return dim3((cols + 31) / 32, std::min((rows + 31) / 32, 65535)); }
 
 int sf_transpose(sfnmf_ctx *c, const double *in, int ldi, double *out, int ldo, int R, int C) {

@@ -17,9 +17,9 @@
 //
 // All four are bandwidth- or latency-bound; none has a matrix product in it.
 // The expressions follow NumPy's operation order with contraction off, and
-// np.abs of a complex number is NumPy's own loop (np_cabs below), which is
-// what makes the median and the 2x2 inverse bit-equal to the reference.
-#include "fasst_common.h"
+// np.abs of a complex number is NumPy's own loop (np_cabs, fasst_device.h),
+// which is what makes the median and the 2x2 inverse bit-equal to the reference.
+#include "fasst_device.h"
 #include "../../include/fasst_sigtools.h"
 
 #include <atomic>
@@ -29,18 +29,6 @@
 namespace fasst {
 
 static std::atomic<long> g_sig_launches{0};
-
-// np.abs(complex128): larger * sqrt(fma(r, r, 1)), r = smaller / larger
-// (NumPy's SIMD loop for complex absolute)
-__device__ __forceinline__ double np_cabs(double re, double im) {
-#pragma clang fp contract(off)
-  const double a = fabs(re), b = fabs(im);
-  if (isinf(a) || isinf(b)) return INFINITY;
-  if (a != a || b != b) return NAN;
-  const double l = a > b ? a : b, s = a > b ? b : a;
-  const double r = l == 0.0 ? 0.0 : s / l;
-  return sqrt(fma(r, r, 1.0)) * l;
-}
 
 // ---------------------------------------------------------------- prinComp2D
 constexpr int kPcaChunk = 256;
@@ -276,27 +264,12 @@ __global__ __launch_bounds__(256) void k_invherm_elem(const InvArgs a) {
 // ----------------------------------------------------------------- host side
 static float g_sig_ms = 0.f;
 
-// HIP events around the kernels of one call (sig_last_ms)
-struct SigTimer {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int start() {
-    FASST_HIP(hipEventCreate(&e0));
-    FASST_HIP(hipEventCreate(&e1));
-    FASST_HIP(hipEventRecord(e0, 0));
-    return FASST_OK;
-  }
-  ~SigTimer() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-};
-
-static int finish_launch(int n_kernels, SigTimer &tm) {
+// tm: the HIP events around the kernels of one call (sig_last_ms)
+static int finish_launch(int n_kernels, Events &tm) {
   FASST_LAUNCH_CHECK();
   g_sig_launches += n_kernels;
-  FASST_HIP(hipEventRecord(tm.e1, 0));
-  FASST_HIP(hipEventSynchronize(tm.e1));
-  FASST_HIP(hipEventElapsedTime(&g_sig_ms, tm.e0, tm.e1));
+  int st = elapsed_ms(tm.e[0], tm.e[1], 0, &g_sig_ms);
+  if (st) return st;
   FASST_HIP(hipDeviceSynchronize());
   return FASST_OK;
 }
@@ -378,8 +351,8 @@ int sig_pca2d_dev(int device, int F, int N, int nb, const double *x0, const doub
   if (smem > 64 * 1024)
     FASST_HIP(hipFuncSetAttribute((const void *)k_pca2d,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  SigTimer tm;
-  if ((st = tm.start())) return st;
+  Events tm;
+  if ((st = tm.start(0))) return st;
   k_pca2d<<<a.nchunks * F, kPcaChunk, smem>>>(a);
   if ((st = finish_launch(1, tm))) return st;
   FASST_HIP(hipMemcpy(flags, dflags.p, 2 * sizeof(int), hipMemcpyDeviceToHost));
@@ -433,8 +406,8 @@ int sig_median_dev(int device, int R, int N, int length, const double *in, doubl
   a.N = N;
   a.length = length < N ? length : N;  // the same windows, and n + length stays an int
   a.nchunks = (N + kMedChunk - 1) / kMedChunk;
-  SigTimer tm;
-  if ((st = tm.start())) return st;
+  Events tm;
+  if ((st = tm.start(0))) return st;
   if ((long)kMedChunk + 2L * a.length <= kMedLdsSpan)
     k_median<true><<<a.nchunks * R, kMedChunk, (kMedChunk + 2 * (size_t)a.length) * sizeof(double)>>>(a);
   else
@@ -492,8 +465,8 @@ int sig_hsum_dev(int device, int F, int T, int n_f0, int n_harm, const double *t
   a.nnz = nnz;
   a.ntiles = (T + kHsTile - 1) / kHsTile;
   a.prod = prod != 0;
-  SigTimer tm;
-  if ((st = tm.start())) return st;
+  Events tm;
+  if ((st = tm.start(0))) return st;
   k_hsum_colsum<<<(T + kHsSumBlock - 1) / kHsSumBlock, kHsSumBlock>>>(a);
   k_hsum<<<a.ntiles * n_f0, kHsTile>>>(a);
   return finish_launch(2, tm);
@@ -570,8 +543,8 @@ int sig_invherm_dev(int device, long n, int off_complex, const double *a00, cons
   a.nzero = dz.p;
   a.n = n;
   a.off_complex = off_complex != 0;
-  SigTimer tm;
-  if ((st = tm.start())) return st;
+  Events tm;
+  if ((st = tm.start(0))) return st;
   k_invherm_elem<<<(int)((n + 255) / 256), 256>>>(a);
   if ((st = finish_launch(1, tm))) return st;
   FASST_HIP(hipMemcpy(n_zero_det, dz.p, sizeof(int), hipMemcpyDeviceToHost));

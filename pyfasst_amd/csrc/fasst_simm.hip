@@ -32,13 +32,6 @@ constexpr double kSimmEps = 1e-20;  // SIMM.py:150, :506
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (size_t)(n); \
        i += (size_t)gridDim.x * blockDim.x)
 
-static inline int egrid(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 8192); }
-
-// ratio^omega with the reference's `** omega` (omega == 1 is exact)
-__device__ __forceinline__ double powo(double x, double omega) {
-  return omega == 1.0 ? x : pow(x, omega);
-}
-
 constexpr int kSimmKmax = 8;  // simm_create: K <= 8 filters
 constexpr int kHgRowChunks = 4;  // frame chunks of k_hgamma_rows (>= 4 waves per SIMD at C5)
 // bins per k_hgamma_rows block: 2 halves its accumulators and doubles the
@@ -134,7 +127,7 @@ __global__ void k_mu_apply_nd(double *__restrict__ X, const double *__restrict__
   GRID_STRIDE(i, (size_t)R * N) {
     const size_t r = i / N, n = i % N;
     const double num = NP[r * 2 * N + n], den = NP[r * 2 * N + N + n];
-    X[i] *= powo(num / fmax(den, kSimmEps), omega);
+    X[i] *= pow_omega(num / fmax(den, kSimmEps), omega);
   }
 }
 
@@ -142,7 +135,7 @@ __global__ void k_mu_apply_nd(double *__restrict__ X, const double *__restrict__
 __global__ void k_mu_apply(double *__restrict__ X, const double *__restrict__ num,
                            const double *__restrict__ den, size_t n, double omega, int floor_eps) {
   GRID_STRIDE(i, n) {
-    double x = X[i] * powo(num[i] / fmax(den[i], kSimmEps), omega);
+    double x = X[i] * pow_omega(num[i] / fmax(den[i], kSimmEps), omega);
     if (floor_eps) x = fmax(x, kSimmEps);
     X[i] = x;
   }
@@ -159,7 +152,7 @@ __global__ void k_hm_apply(double *__restrict__ HM, const double *__restrict__ P
     const double br = bR[r] * bR[r], bl = bL[r] * bL[r];
     const double num = br * PnR[i] + bl * PnL[i];
     const double den = br * PdR[i] + bl * PdL[i];
-    HM[i] *= powo(num / fmax(den, kSimmEps), omega);
+    HM[i] *= pow_omega(num / fmax(den, kSimmEps), omega);
   }
 }
 
@@ -254,18 +247,12 @@ __global__ void k_simm_xy(const double *__restrict__ h, const double *__restrict
 }
 
 // k_simm_xy's operands for one element (both channels' formulas in one
-// place) in the fused skinny products: reciprocals by v_rcp_f64 + two Newton
-// steps (<= 1 ulp) instead of the IEEE division sequences (hv >= eps: it
-// comes from hat_of)
-__device__ __forceinline__ double simm_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return fma(fma(-x, r, 1.0), r, r);
-}
+// place) in the fused skinny products: reciprocals by rcp_nr instead of the
+// IEEE division sequences (hv >= eps: it comes from hat_of)
 template <bool ST>
 __device__ __forceinline__ void xy_of(double hv, double sx, double &x, double &y) {
-  y = simm_rcp(hv);
-  x = ST ? sx * simm_rcp(fmax(hv * hv, kSimmEps)) : (y * sx) * y;
+  y = rcp_nr(hv);
+  x = ST ? sx * rcp_nr(fmax(hv * hv, kSimmEps)) : (y * sx) * y;
 }
 
 // Skinny accompaniment products with k_simm_xy fused into the operand loads
@@ -349,8 +336,8 @@ __global__ __launch_bounds__(256, 2) void k_simm_wmt_xy(const SPl p, const doubl
         xy_of<ST>(hv[c], sv[c][s], x, y);
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-          acc[2 * c][i] = gmfma(a[i], x, acc[2 * c][i]);
-          acc[2 * c + 1][i] = gmfma(a[i], y, acc[2 * c + 1][i]);
+          acc[2 * c][i] = mfma4(a[i], x, acc[2 * c][i]);
+          acc[2 * c + 1][i] = mfma4(a[i], y, acc[2 * c + 1][i]);
         }
       }
     }
@@ -497,8 +484,8 @@ __global__ __launch_bounds__(256, 2) void k_simm_xy_hmt(const SPl p, const doubl
         xy_of<ST>(hv[c], sv[c][j], x, y);
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-          acc[2 * c][i] = gmfma(x, b[i], acc[2 * c][i]);
-          acc[2 * c + 1][i] = gmfma(y, b[i], acc[2 * c + 1][i]);
+          acc[2 * c][i] = mfma4(x, b[i], acc[2 * c][i]);
+          acc[2 * c + 1][i] = mfma4(y, b[i], acc[2 * c + 1][i]);
         }
       }
     }
@@ -579,7 +566,7 @@ __global__ void k_hphi_update(double *__restrict__ HPHI, const double *__restric
       num += part[(((size_t)c * 2 + 0) * K + k) * N + n];
       den += part[(((size_t)c * 2 + 1) * K + k) * N + n];
     }
-    double h = HPHI[(size_t)k * N + n] * powo(num / fmax(den, kSimmEps), omega);
+    double h = HPHI[(size_t)k * N + n] * pow_omega(num / fmax(den, kSimmEps), omega);
     HPHI[(size_t)k * N + n] = h;
     s += h;
   }
@@ -708,7 +695,7 @@ __global__ void k_hgamma_norm(double *__restrict__ HGAMMA, const double *__restr
   double s = 0.0;
   for (int p = 0; p < P; ++p) {
     const double v =
-        HGAMMA[p * K + k] * powo(nd[p * 2 * K + k] / fmax(nd[p * 2 * K + K + k], kSimmEps), omega);
+        HGAMMA[p * K + k] * pow_omega(nd[p * 2 * K + k] / fmax(nd[p * 2 * K + K + k], kSimmEps), omega);
     HGAMMA[p * K + k] = v;
     s += v;
   }
@@ -765,7 +752,7 @@ __global__ __launch_bounds__(256) void k_wm_update(double *__restrict__ WM,
       ratio = (PnR[i] * br + PnL[i] * bl) / (PdR[i] * br + PdL[i] * bl);   // no eps floor (:844)
     else
       ratio = PnR[i] / fmax(PdR[i], kSimmEps);
-    const double w = WM[i] * powo(ratio, omega);
+    const double w = WM[i] * pow_omega(ratio, omega);
     WM[i] = w;
     part += w;
   }

@@ -39,7 +39,7 @@
 // Every wave owns a run of contracted tiles and writes its own partial; the
 // consumers sum the partials in index order, so a run is reproducible bit for
 // bit.
-#include "fasst_common.h"
+#include "fasst_device.h"
 
 #include <algorithm>
 #include <vector>
@@ -51,23 +51,6 @@ namespace fasst {
 constexpr double kSnmfEps = 1e-20;  // SIMM.py:951
 constexpr int kSnmfMaxR = 128;
 constexpr int kSnmfH = 0, kSnmfW = 1, kSnmfB = 2;
-
-__device__ __forceinline__ d4 snmfma(double a, double b, d4 c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
-// 1/x for finite normal x > 0: v_rcp_f64 + two Newton steps (<= 1 ulp), as
-// fasst_nmf.hip nmf_rcp
-__device__ __forceinline__ double snmf_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return fma(fma(-x, r, 1.0), r, r);
-}
-
-// x ** omega as NumPy gives it (omega == 1: the identity)
-__device__ __forceinline__ double snmf_pow(double x, double omega) {
-  return omega == 1.0 ? x : pow(x, omega);
-}
 
 // the loop-invariant kept operand of the hat products: row k0 + fl of keptOp
 // times betaR^2 / betaL^2 (b2: [2][Rp])
@@ -93,10 +76,10 @@ __device__ __forceinline__ void snmf_hat(const double (&a)[4 * NKC], const doubl
   d4 r0 = d4{0.0, 0.0, 0.0, 0.0}, r1 = r0, l0 = r0, l1 = r0;
 #pragma unroll
   for (int s = 0; s < NKS; s += 2) {
-    r0 = snmfma(a[s], bk[0][s], r0);
-    l0 = snmfma(a[s], bk[1][s], l0);
-    r1 = snmfma(a[s + 1], bk[0][s + 1], r1);
-    l1 = snmfma(a[s + 1], bk[1][s + 1], l1);
+    r0 = mfma4(a[s], bk[0][s], r0);
+    l0 = mfma4(a[s], bk[1][s], l0);
+    r1 = mfma4(a[s + 1], bk[0][s + 1], r1);
+    l1 = mfma4(a[s + 1], bk[1][s + 1], l1);
   }
   hR = r0 + r1;
   hL = l0 + l1;
@@ -178,10 +161,10 @@ __global__ __launch_bounds__(256) void k_snmf_con(const double *__restrict__ kep
       // pad bins / frames: x = 0 gives p = 0, q is masked
       const bool ok = kv && c0 + 4 * tq + m < nCon;
       const double r = hR[m], l = hL[m];
-      pR[m] = xr[m] * snmf_rcp(fmax(r * r, kSnmfEps));
-      pL[m] = xl[m] * snmf_rcp(fmax(l * l, kSnmfEps));
-      qR[m] = ok ? snmf_rcp(r) : 0.0;
-      qL[m] = ok ? snmf_rcp(l) : 0.0;
+      pR[m] = xr[m] * rcp_nr(fmax(r * r, kSnmfEps));
+      pL[m] = xl[m] * rcp_nr(fmax(l * l, kSnmfEps));
+      qR[m] = ok ? rcp_nr(r) : 0.0;
+      qL[m] = ok ? rcp_nr(l) : 0.0;
     }
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
@@ -191,16 +174,16 @@ __global__ __launch_bounds__(256) void k_snmf_con(const double *__restrict__ kep
         if (oc0 + kc >= NKC) continue;  // wave-uniform: the last slab's tail
         const double w = cr[16 * (oc0 + kc)];
         if constexpr (MODE == kSnmfB) {
-          acc[0][kc] = snmfma(pR[m], w, acc[0][kc]);
-          acc[1][kc] = snmfma(qR[m], w, acc[1][kc]);
-          acc[2][kc] = snmfma(pL[m], w, acc[2][kc]);
-          acc[3][kc] = snmfma(qL[m], w, acc[3][kc]);
+          acc[0][kc] = mfma4(pR[m], w, acc[0][kc]);
+          acc[1][kc] = mfma4(qR[m], w, acc[1][kc]);
+          acc[2][kc] = mfma4(pL[m], w, acc[2][kc]);
+          acc[3][kc] = mfma4(qL[m], w, acc[3][kc]);
         } else {
           const double wR = w * bo[0][kc], wL = w * bo[1][kc];
-          acc[0][kc] = snmfma(pR[m], wR, acc[0][kc]);
-          acc[1][kc] = snmfma(qR[m], wR, acc[1][kc]);
-          acc[0][kc] = snmfma(pL[m], wL, acc[0][kc]);
-          acc[1][kc] = snmfma(qL[m], wL, acc[1][kc]);
+          acc[0][kc] = mfma4(pR[m], wR, acc[0][kc]);
+          acc[1][kc] = mfma4(qR[m], wR, acc[1][kc]);
+          acc[0][kc] = mfma4(pL[m], wL, acc[0][kc]);
+          acc[1][kc] = mfma4(qL[m], wL, acc[1][kc]);
         }
       }
     }
@@ -340,7 +323,7 @@ __global__ void k_snmf_h_upd(double *__restrict__ Ht, const double *__restrict__
       n += part[(size_t)c * 2 * slab + i];
       d += part[(size_t)c * 2 * slab + slab + i];
     }
-    Ht[i] *= snmf_pow(n / fmax(d, kSnmfEps), omega);
+    Ht[i] *= pow_omega(n / fmax(d, kSnmfEps), omega);
   }
 }
 
@@ -362,7 +345,7 @@ __global__ __launch_bounds__(256) void k_snmf_w_upd(double *__restrict__ W,
       n += part[(size_t)c * 2 * slab + i];
       d += part[(size_t)c * 2 * slab + slab + i];
     }
-    const double w = W[i] * snmf_pow(n / d, omega);
+    const double w = W[i] * pow_omega(n / d, omega);
     W[i] = w;
     acc += w;
   }
@@ -436,8 +419,6 @@ struct snmf_ctx {
 namespace {
 
 constexpr int kSnmfBlocks = 512;  // two workgroups per CU
-
-int snmf_egrid(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 8192); }
 
 // split nct contracted tiles over 4 waves x ng workgroups so that about
 // kSnmfBlocks workgroups run, each wave keeping a few tiles
@@ -596,7 +577,7 @@ int snmf_run(snmf_ctx *c, int n_iter, double omega, double *reco_err) {
     if ((st = c->err.alloc((size_t)3 * n_iter + 1))) return st;
     if ((st = snmf_error(c, slot++))) return st;
   }
-  const int eg = snmf_egrid((size_t)N * Rp);
+  const int eg = egrid((size_t)N * Rp);
   const int nbp = (c->Na / 16) * 4 * c->ng_h;
   for (int it = 0; it < n_iter; ++it) {
     if ((st = snmf_dispatch(c, kSnmfH))) return st;

@@ -16,18 +16,13 @@
 // algebra as the fused E-step (S = Sigma_x^-1, N = S Cx S - S, P = Cx S; the
 // R x R pair loop becomes per-bin t-reductions of V_r1 V_r2 N and V_r P).
 #include "fasst_ctx.h"
+#include "fasst_device.h"
 #include "fasst_sf.h"
 
 #include <cmath>
 #include <vector>
 
 namespace fasst {
-
-__device__ __forceinline__ double2 c_add(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 c_mul(double2 a, double2 b) {
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ double2 c_conj(double2 a) { return make_double2(a.x, -a.y); }
 
 // V[j][f][t] = sum_k W[j][k][f] H[j][k][t] (W = FB.FW in Wkf, H in TW's rows;
 // (m0, m1): the columns of spectral components to include, bit k of word
@@ -220,9 +215,9 @@ __global__ __launch_bounds__(kSsTile) void k_suff_stat(const SSArgs a) {
       const double2 m01 = make_double2(s_out[4 * p + 2], s_out[4 * p + 3]);
       const double2 a0 = s_a[u1][0], a1 = s_a[u1][1], b0 = s_a[u2][0], b1 = s_a[u2][1];
       // conj(a0) (m00 b0 + m01 b1) + conj(a1) (conj(m01) b0 + m11 b1)
-      double2 r0 = c_add(make_double2(m00 * b0.x, m00 * b0.y), c_mul(m01, b1));
-      double2 rr = c_add(c_mul(c_conj(m01), b0), make_double2(m11 * b1.x, m11 * b1.y));
-      double2 v = c_add(c_mul(c_conj(a0), r0), c_mul(c_conj(a1), rr));
+      double2 r0 = cadd(make_double2(m00 * b0.x, m00 * b0.y), cmul(m01, b1));
+      double2 rr = cadd(cmul(cconj(m01), b0), make_double2(m11 * b1.x, m11 * b1.y));
+      double2 v = cadd(cmul(cconj(a0), r0), cmul(cconj(a1), rr));
       v.x *= invT;
       v.y *= invT;
       if (u1 == u2) v.x += s_out[4 * NPAIR + 8 * R + u1] * invT;
@@ -243,7 +238,7 @@ __global__ __launch_bounds__(kSsTile) void k_suff_stat(const SSArgs a) {
     const double *q = s_out + 4 * NPAIR + 8 * r;
     const double2 pc0 = make_double2(q[4 * c + 0], q[4 * c + 1]);   // P[c][0]
     const double2 pc1 = make_double2(q[4 * c + 2], q[4 * c + 3]);   // P[c][1]
-    double2 v = c_add(c_mul(pc0, s_a[r][0]), c_mul(pc1, s_a[r][1]));
+    double2 v = cadd(cmul(pc0, s_a[r][0]), cmul(pc1, s_a[r][1]));
     a.rxs[((size_t)f * 2 + c) * R + r] = make_double2(v.x * invT, v.y * invT);
   }
 }
@@ -293,7 +288,7 @@ __global__ void k_mix_solve_inst(const double2 *__restrict__ rss, const double2 
         double2 x = rxs[((size_t)f * 2 + c) * R + u];
         for (int i = 0; i < no; ++i) {
           const int o = s_o[i];
-          const double2 t = c_mul(mix[((size_t)o * 2 + c) * F + f], rss[((size_t)f * R + o) * R + u]);
+          const double2 t = cmul(mix[((size_t)o * 2 + c) * F + f], rss[((size_t)f * R + o) * R + u]);
           x.x -= t.x;
           x.y -= t.y;
         }
@@ -398,14 +393,14 @@ __global__ void k_mix_solve_conv(const double2 *__restrict__ rss, const double2 
     const double dn = d.x * d.x + d.y * d.y;
     const double2 rinv = make_double2(d.x / dn, -d.y / dn);
     for (int i = k + 1; i < R; ++i) {
-      const double2 m = c_mul(L[i][k], rinv);
+      const double2 m = cmul(L[i][k], rinv);
       for (int c = k + 1; c < R; ++c) {
-        const double2 t = c_mul(m, L[k][c]);
+        const double2 t = cmul(m, L[k][c]);
         L[i][c].x -= t.x;
         L[i][c].y -= t.y;
       }
       for (int c = 0; c < 2; ++c) {
-        const double2 t = c_mul(m, B[k][c]);
+        const double2 t = cmul(m, B[k][c]);
         B[i][c].x -= t.x;
         B[i][c].y -= t.y;
       }
@@ -417,7 +412,7 @@ __global__ void k_mix_solve_conv(const double2 *__restrict__ rss, const double2 
     for (int c = 0; c < 2; ++c) {
       double2 s = B[k][c];
       for (int i = k + 1; i < R; ++i) {
-        const double2 t = c_mul(L[k][i], B[i][c]);
+        const double2 t = cmul(L[k][i], B[i][c]);
         s.x -= t.x;
         s.y -= t.y;
       }
@@ -445,7 +440,7 @@ __global__ void k_sigma_comp(const double *__restrict__ Wkf, const double *__res
     const double2 a0 = A[(size_t)(2 * r) * Fp + f], a1 = A[(size_t)(2 * r + 1) * Fp + f];
     c0 += a0.x * a0.x + a0.y * a0.y;
     c1 += a1.x * a1.x + a1.y * a1.y;
-    co = c_add(co, c_mul(a0, c_conj(a1)));
+    co = cadd(co, cmul(a0, cconj(a1)));
   }
   const size_t i = (size_t)f * T + t;
   diag[i] = c0 * v;
@@ -465,7 +460,7 @@ __global__ void k_inv_sigma_mix(const double *__restrict__ diag, const double2 *
     for (int c = 0; c < n; ++c) {
       d0 += diag[((size_t)c * 2 + 0) * FT + i];
       d1 += diag[((size_t)c * 2 + 1) * FT + i];
-      o = c_add(o, off[(size_t)c * FT + i]);
+      o = cadd(o, off[(size_t)c * FT + i]);
     }
     const double p = psd[i / T];
     d0 += p;
@@ -486,13 +481,13 @@ __global__ void k_wiener_gain(const double *__restrict__ sd, const double2 *__re
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const double s0 = sd[i], s1 = sd[n + i], i0 = isd[i], i1 = isd[n + i];
     const double2 o = so[i], io = iso[i];
-    const double2 w00 = c_mul(o, c_conj(io));
+    const double2 w00 = cmul(o, cconj(io));
     WG[i] = make_double2(w00.x + s0 * i0, w00.y);
     WG[3 * n + i] = make_double2(w00.x + s1 * i1, -w00.y);
-    const double2 w01 = c_add(make_double2(s0 * io.x, s0 * io.y), make_double2(o.x * i1, o.y * i1));
+    const double2 w01 = cadd(make_double2(s0 * io.x, s0 * io.y), make_double2(o.x * i1, o.y * i1));
     WG[n + i] = w01;
-    const double2 ic = c_conj(io);
-    const double2 w10 = c_add(make_double2(o.x * i0, -o.y * i0), make_double2(s1 * ic.x, s1 * ic.y));
+    const double2 ic = cconj(io);
+    const double2 w10 = cadd(make_double2(o.x * i0, -o.y * i0), make_double2(s1 * ic.x, s1 * ic.y));
     WG[2 * n + i] = w10;
   }
 }

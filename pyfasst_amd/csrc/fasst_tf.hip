@@ -9,6 +9,7 @@
 //   k_wiener<J>     Sigma_n = R_n V_n, Sigma_x^-1, WG_n = Sigma_n Sigma_x^-1,
 //                   S_n = WG_n X  (audioModel.py:1327-1467, :1205-1214)
 #include "fasst_ctx.h"
+#include "fasst_device.h"
 #include "fasst_cqt_dev.h"
 #include "fasst_fft.h"
 #include "../../include/fasst_cqt.h"
@@ -16,10 +17,6 @@
 #include <cmath>
 
 namespace fasst {
-
-__device__ __forceinline__ d4 mfma4b(double a, double b, d4 c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 
 // One block per (frame, channel).  x: [nch][L] channel-major; output either
 // [frame][bin] into a pitched device image (ld = row pitch in bins) or, for
@@ -305,7 +302,7 @@ __global__ __launch_bounds__(64) void k_wiener(const WArgs a) {
     if (j >= JR) continue;
     const double *tw = a.TW + ((size_t)j * a.KP + tq) * a.Tp + t0 + fl;
     const double *wk = a.Wkf + ((size_t)j * a.KP + tq) * a.Fp + f;
-    for (int s = 0; s < nks; ++s) v[j] = mfma4b(tw[(size_t)(4 * s) * a.Tp], wk[(size_t)(4 * s) * a.Fp], v[j]);
+    for (int s = 0; s < nks; ++s) v[j] = mfma4(tw[(size_t)(4 * s) * a.Tp], wk[(size_t)(4 * s) * a.Fp], v[j]);
   }
   double cal[J], cbe[J], cgr[J], cgi[J];
 #pragma unroll
@@ -388,7 +385,7 @@ __device__ __forceinline__ d4 ws_term_v(const WSArgs &a, int i, int t0, int f, i
   for (int s = 0; s < (a.KP >> 2); ++s) {
     const int k = tq + 4 * s;
     const double w = ((k < 64 ? m0 >> k : m1 >> (k - 64)) & 1ull) ? wk[(size_t)(4 * s) * a.Fp] : 0.0;
-    v = mfma4b(tw[(size_t)(4 * s) * a.Tp], w, v);
+    v = mfma4(tw[(size_t)(4 * s) * a.Tp], w, v);
   }
   return v;
 }

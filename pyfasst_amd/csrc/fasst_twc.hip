@@ -9,16 +9,12 @@
 //                  :1853-1885), the one-hot TW (:1895-1900) and the prior /
 //                  transition counts (:1902-1924).
 #include "fasst_ctx.h"
+#include "fasst_device.h"
 #include "fasst_twc.h"
 
 #include <cmath>
 
 namespace fasst {
-
-#define TWC_HALT_GUARD(h)                               \
-  do {                                                  \
-    if ((h) && *(volatile const int *)(h)) return;      \
-  } while (0)
 
 constexpr int kTdFrames = 4;     // frames per k_tw_statediv block, one per wave
 constexpr int kTvThreads = 128;  // k_tw_decode: one lane per state (K <= 128)
@@ -35,13 +31,6 @@ struct TDArgs {
   const int *halt;
 };
 
-// sum over the wave's 64 lanes in a fixed butterfly: every lane ends with the
-// same value, whatever the grid
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 // One block per (tile of kTdFrames frames, source), wave w owns frame
 // t0 + w.  hat_W of the tile is recovered once from the E-step's plane,
 // hat_W = rho * max(V_old, eps) with V_old = W_old . TW of the pre-update
@@ -55,7 +44,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 //   TW_all[k, t] *= (num / max(den, eps))^omega
 //   ISdiv[k, t] = sum_f (r - log(max(r, eps)) - 1),  r = hat_W / max(Wb TW_all[k, t], eps)
 __global__ __launch_bounds__(64 * kTdFrames) void k_tw_statediv(const TDArgs a) {
-  TWC_HALT_GUARD(a.halt);
+  HALT_GUARD(a.halt);
   const int j = blockIdx.y;
   if (!a.kind[j]) return;
   extern __shared__ __align__(16) double td_sm[];
@@ -132,7 +121,7 @@ static size_t decode_lds(int K) {
 // in chunks of 2 K frames.  Then TW = one-hot of TW_all and, with a free
 // prior, the state / transition frequencies.
 __global__ __launch_bounds__(kTvThreads) void k_tw_decode(const TVArgs a) {
-  TWC_HALT_GUARD(a.halt);
+  HALT_GUARD(a.halt);
   const int j = blockIdx.x, kind = a.kind[j];
   if (!kind) return;
   extern __shared__ __align__(16) double tv_sm[];

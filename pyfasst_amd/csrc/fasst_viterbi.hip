@@ -555,10 +555,8 @@ int viterbi_tracking(int device, int n_states, int n_frames, const double *log_d
                         (size_t)ld_transition * sizeof(double), (size_t)S * sizeof(double), S,
                         hipMemcpyHostToDevice));
   FASST_HIP(hipMemcpy(dprior.p, log_prior, S * sizeof(double), hipMemcpyHostToDevice));
-  hipEvent_t e0, e1;
-  FASST_HIP(hipEventCreate(&e0));
-  FASST_HIP(hipEventCreate(&e1));
-  FASST_HIP(hipEventRecord(e0, 0));
+  Events tm;
+  if ((st = tm.start(0))) return st;
   // frame-major densities [N][Sp], target-major transitions TT[s][s'] = T[s'][s]
   k_vt_transpose<<<dim3((N + 15) / 16, (S + 15) / 16), 256>>>(dD.p, N, dDT.p, Sp, S, N);
   FASST_LAUNCH_CHECK();
@@ -675,11 +673,7 @@ int viterbi_tracking(int device, int n_states, int n_frames, const double *log_d
   FASST_LAUNCH_CHECK();
   k_vt_fill<<<(nch + 63) / 64, 64>>>(ante.p, Sp, hi_state.p, N, dpath.p);
   FASST_LAUNCH_CHECK();
-  FASST_HIP(hipEventRecord(e1, 0));
-  FASST_HIP(hipEventSynchronize(e1));
-  FASST_HIP(hipEventElapsedTime(&g_vt_ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  if ((st = elapsed_ms(tm.e[0], tm.e[1], 0, &g_vt_ms))) return st;
   FASST_HIP(hipMemcpy(path, dpath.p, (size_t)N * sizeof(long long), hipMemcpyDeviceToHost));
   return FASST_OK;
 }

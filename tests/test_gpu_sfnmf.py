@@ -286,6 +286,7 @@ def test_sfnmf_create_refuses_bad_shapes():
         p = ctypes.c_void_p()
         assert _lib.lib.sfnmf_create(0, *dims, ctypes.byref(p)) == _lib.FASST_ERR_SHAPE, dims
         assert "sfnmf_create" in _lib.last_error() and not p.value
-    assert sorted(_lib.SFNMF_SIGNATURES) == ["sfnmf_create", "sfnmf_destroy", "sfnmf_get_params",
-                                             "sfnmf_run", "sfnmf_set_data", "sfnmf_set_params"]
+    assert sorted(s for s in _lib.SIGNATURES if s.startswith("sfnmf_")) == [
+        "sfnmf_create", "sfnmf_destroy", "sfnmf_get_params", "sfnmf_run", "sfnmf_set_data",
+        "sfnmf_set_params"]
     assert _lib.lib.sfnmf_run(None, 1, 1, 1, 1, 1) == _lib.FASST_ERR_SHAPE
