@@ -112,6 +112,18 @@ struct fasst_ctx {
   // fasst_em.hip) unless FASST_FAST_TAIL=0 was set when this context was
   // created; 2 (default): it also forms the next iteration's FWHt / hsum
   int ftail = 2;
+  // the single-pass E-step's tile-packed operand images (layouts at
+  // k_cx_image / k_tw_image in fasst_em.hip).  eimg: bit 0 the Cx image, bit 1
+  // the TW image (FASST_ESTEP_IMG = 0 | cx | tw | 1, read when the context is
+  // created).  cxp [nft][ntt][512] is built from the planes by the first
+  // iteration after an observation was written (cxp_valid, cleared by every
+  // writer of cx); twp [ntt][J][KP / 8][64] is written by the fused
+  // k_tw_update whenever it forms the next iteration's FWHt (prep_ready), and
+  // packed from TW ahead of the E-step otherwise.  Allocated by the first
+  // iteration of a model that reads them
+  int eimg = 3;
+  bool cxp_valid = false;
+  fasst::DBuf<double2> cxp, twp;
   fasst::DBuf<double2> rss, rxs;
   fasst::DBuf<int> flags;        // [0] singular, [1..nslot] TW restart, [kFlagHalt] halt,
                                  // [kFlagIter] iteration that raised a restart

@@ -212,10 +212,56 @@ __global__ void k_inst_A(const double2 *__restrict__ Pinst, double2 *__restrict_
   }
 }
 
+// ------------------------------------------- E-step operand images (J <= 8)
+// k_estep_mx's lane (fl = lane & 15, tq = lane >> 4) of the wave on the
+// 16 x 16 tile (bin tile bt, frame tile tt) holds point i at (f = 16 bt + fl,
+// t = 16 tt + tq + 4 i).  The images store what each of its load instructions
+// needs as one contiguous KB, 16 bytes per lane.
+//
+// Cx image: record (bt, tt) = 8 pieces of 64 double2 at img + (bt ntt + tt)
+// 512; piece 2 i + h, lane l: (cx00, cx11) (h = 0) or (cxr, cxi) (h = 1) of
+// the lane's point i, padding included.  The records of one bin tile are
+// consecutive in tt.  Built once per observation (cx_image below).
+__global__ __launch_bounds__(256) void k_cx_image(const double *__restrict__ cx,
+                                                  double2 *__restrict__ img, int Fp, int ntt,
+                                                  size_t plane) {
+  const int tt = blockIdx.x, bt = blockIdx.y;
+  double2 *rec = img + ((size_t)bt * ntt + tt) * 512;
+  for (int e = threadIdx.x; e < 512; e += 256) {
+    const int piece = e >> 6, lane = e & 63, i = piece >> 1, fl = lane & 15, tq = lane >> 4;
+    const double *p = cx + (size_t)(16 * tt + tq + 4 * i) * Fp + 16 * bt + fl;
+    rec[e] = piece & 1 ? make_double2(p[2 * plane], p[3 * plane]) : make_double2(p[0], p[plane]);
+  }
+}
+
+// One element of the TW image [ntt][J][KP / 8][64]: piece (tt, j, u), lane l
+// pairs the operands of the k-steps 2 u and 2 u + 1, TW[j][tq + 8 u][16 tt +
+// fl] and TW[j][tq + 8 u + 4][16 tt + fl]; `row(k)` is row k of source j at
+// frame 16 tt + fl
+template <class Row>
+__device__ __forceinline__ void tw_image_store(double2 *__restrict__ img, int tt, int j, int J,
+                                               int KP, int e, Row &&row) {
+  const int u = e >> 6, lane = e & 63, fl = lane & 15, tq = lane >> 4;
+  img[((size_t)tt * J + j) * (KP / 8) * 64 + e] = make_double2(row(tq + 8 * u, fl), row(tq + 8 * u + 4, fl));
+}
+
+// the TW image from the planes: wherever TW was written without it (an
+// upload, the unfused tail, the first iteration of a batch)
+__global__ __launch_bounds__(256) void k_tw_image(const double *__restrict__ TW,
+                                                  double2 *__restrict__ img, int J, int KP, int Tp) {
+  const int tt = blockIdx.x, j = blockIdx.y;
+  const double *tw = TW + (size_t)j * KP * Tp + 16 * tt;
+  for (int e = threadIdx.x; e < (KP / 8) * 64; e += 256)
+    tw_image_store(img, tt, j, J, KP, e, [&](int k, int fl) { return tw[(size_t)k * Tp + fl]; });
+}
+
 // ---------------------------------------------------------------- E-step
 struct EArgs {
   const double *cx00, *cx11, *cxr, *cxi;  // [Tp][Fp]
   const double *TW;                       // [J][KP][Tp]
+  // tile-packed operand images of k_estep_mx (layouts at the pack kernels)
+  const double2 *cxp;                     // [nft][nttp] records of 512: Cx of one 16 x 16 tile
+  const double2 *twp;                     // [nttp][J][KP / 8][64]: the tile's TW operand pairs
   const double *Wkf;                      // [J][KP][Fp]
   const double2 *A;                       // [R][2][Fp]
   const double *psd;                      // [Fp]
@@ -223,6 +269,7 @@ struct EArgs {
   double *part;                           // [slot][Fp][NACC]
   double *llpart;                         // [slot][nft]
   int F, T, Fp, Tp, KP, R, ntt, tpc, nft;
+  int nttp;          // frame tiles of the whole clip (the images' record stride)
   int ybase, tbase;  // this launch's chunks start at partial ybase, frame tile tbase (ntt = end)
   ESched es;         // the partials' layout (k_estep_mx: also its schedule; fasst_esched.h)
   int roff[kMaxJ + 1];
@@ -339,12 +386,34 @@ __device__ __forceinline__ void es_st(double v, __amdgpu_buffer_rsrc_t r, unsign
   __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(buf_u2, v), r, (int)vo, (int)so, AUX);
 }
 
+// 16-byte raw-buffer load of an operand image (as buf_ld: wave-uniform
+// resource, per-lane byte offset vo, uniform byte offset so)
+typedef unsigned buf_u4 __attribute__((ext_vector_type(4)));
+typedef double buf_d2 __attribute__((ext_vector_type(2)));
+template <int AUX>
+__device__ __forceinline__ buf_d2 buf_ld2(__amdgpu_buffer_rsrc_t r, unsigned vo, unsigned so) {
+  const buf_u4 x = __builtin_amdgcn_raw_buffer_load_b128(r, (int)vo, (int)so, AUX);
+  return __builtin_bit_cast(buf_d2, x);
+}
+
+// Does the (J, NKS) instantiation preload every TW operand of a tile in
+// pairs of k-steps (the only form that reads the TW image)
+template <int J, int NKS>
+__host__ __device__ constexpr bool mx_tw_preload() {
+  return J <= 4 && J * NKS <= 32 && NKS % 2 == 0;
+}
+
+// CXI / TWI: Cx / the preloaded TW operands are read from the tile-packed
+// images a.cxp / a.twp (k_cx_image, k_tw_image) instead of the planes: one
+// contiguous KB per wave-instruction, 16 bytes per lane, half the loads.
+// The values and every arithmetic instruction are those of the plane form.
 // (J = 4 at K = 128: the 64 KB W tile leaves one block per CU, so one wave
 // per SIMD and the full register file for the pipelined V tile)
-template <int J, int NKS, int RKU>
+template <int J, int NKS, int RKU, bool CXI = false, bool TWI = false>
 __global__ __launch_bounds__(256, (J > 4 || (J == 4 && NKS == 32)) ? 1 : 2)
 __attribute__((amdgpu_waves_per_eu(1, (J > 4 || (J == 4 && NKS == 32)) ? 1 : 2))) FASST_NO_LDS_PAIRING
 void k_estep_mx(const EArgs a) {
+  static_assert(!TWI || mx_tw_preload<J, NKS>(), "the TW image serves the preload path only");
   HALT_GUARD(a.halt);
   using S = MXShape<J>;
   constexpr bool VR = S::VR, RP = S::RP;
@@ -494,9 +563,26 @@ void k_estep_mx(const EArgs a) {
   if constexpr (SA) wvu = __builtin_amdgcn_readfirstlane(wv);
   const unsigned vo_tw = (unsigned)(tq * a.Tp + fl) * 8u;   // TW[j][k = tq + 4s][t0 + fl]
   const unsigned vo_cx = (unsigned)(tq * a.Fp + f) * 8u;    // plane[t0 + tq + 4i][f]
+  [[maybe_unused]] const unsigned vo_img = (unsigned)lane * 16u;            // image piece[lane]
   // Cx of frame tile tt (raw-buffer form; the flat form without SA)
   auto load_cx = [&](int tt, double (&c)[4][4]) {
     const int t0 = tt * 16;
+    if constexpr (CXI) {
+      // the tile's 8 KB record: piece 2 i + h holds (cx00, cx11) (h = 0) or
+      // (cxr, cxi) (h = 1) of the lane's point i
+      const __amdgpu_buffer_rsrc_t rc =
+          buf_rsrc((const double *)(a.cxp + ((size_t)btile * a.nttp + tt) * 512));
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const buf_d2 d = buf_ld2<2>(rc, vo_img, (unsigned)(2 * i) * 1024u);
+        const buf_d2 o = buf_ld2<2>(rc, vo_img, (unsigned)(2 * i + 1) * 1024u);
+        c[0][i] = d.x;
+        c[1][i] = d.y;
+        c[2][i] = o.x;
+        c[3][i] = o.y;
+      }
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if constexpr (SA) {
@@ -541,8 +627,23 @@ void k_estep_mx(const EArgs a) {
     constexpr bool CP = !VR && J * NKS > 32;
     constexpr int JA = (VR || CP) ? 1 : (J * NKS <= 32) ? J : (32 / NKS > 0 ? 32 / NKS : 1);
     double twv[JA][NKS];
+    if constexpr (TWI) {
+      // the tile's TW image: piece (j, u) holds the operands of the k-steps
+      // s = 2 u (.x) and 2 u + 1 (.y) of source j
+      static_assert(JA == J, "every source preloaded");
+      const __amdgpu_buffer_rsrc_t rt =
+          buf_rsrc((const double *)(a.twp + (size_t)tt * (J * (NKS / 2) * 64)));
 #pragma unroll
-    for (int j = 0; j < (CP ? 0 : JA); ++j) {
+      for (int j = 0; j < J; ++j)
+#pragma unroll
+        for (int u = 0; u < NKS / 2; ++u) {
+          const buf_d2 h = buf_ld2<0>(rt, vo_img, (unsigned)(j * (NKS / 2) + u) * 1024u);
+          twv[j][2 * u] = h.x;
+          twv[j][2 * u + 1] = h.y;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < ((CP || TWI) ? 0 : JA); ++j) {
       const double *tw = a.TW + ((size_t)j * KP + tq) * a.Tp + t0 + fl;
 #pragma unroll
       for (int s = 0; s < NKS; ++s)
@@ -2644,6 +2745,8 @@ struct TUArgs {
   // [J][KP][ntb] (k_tw_rowsum's; reduced in k_renorm_tail)
   const double *FW;
   double *FWHt, *hpart;
+  // and (with FWHt, twp non-null) the next E-step's TW image (k_tw_image)
+  double2 *twp;
   const int *halt;
 };
 // TW *= (sum_chunks num / max(sum_chunks den, eps))^omega   (:1718-1726)
@@ -2725,6 +2828,18 @@ __global__ __launch_bounds__(256) void k_tw_update(const TUArgs a) {
     // transposed into s_r, s_fw[q][k] = FW[k][q], QB rows q at a time (all of
     // them at KP <= 64, the only sizes spectral_update asks this for)
     const int KP = a.KP;
+    // the E-step's TW image of the block's (up to) four frame tiles, from the
+    // same staged rows (k_tw_image's values: s_y holds the planes' zeros in
+    // the padding rows and frames)
+    if (a.twp) {
+      const int per = (KP / 8) * 64;
+      for (int idx = threadIdx.x; idx < 4 * per; idx += blockDim.x) {
+        const int w = idx / per, tt = 4 * blockIdx.x + w;
+        if (16 * tt < a.Tp)
+          tw_image_store(a.twp, tt, j, a.J, KP, idx - w * per,
+                         [&](int k, int fl) { return s_y[k * 64 + 16 * w + fl]; });
+      }
+    }
     double *s_fw = &s_r[0][0];
     const double *gfw = a.FW + (size_t)j * KP * KP;
     const int QB = KP <= 64 ? KP : 32;
@@ -3575,6 +3690,7 @@ static int launch_grid(size_t n, int block = 256) {
 constexpr bool kEsBalancedDefault = true;
 constexpr int kEsMinUnits = 10;
 static int estep_occupancy(const fasst_ctx *c);
+static bool estep_cxi(const fasst_ctx *c);
 static int contract_occupancy(const fasst_ctx *c);
 static int twl_occupancy(const fasst_ctx *c, int *units);
 // bins per block of the FW update's f-contraction (k_fw_reduce holds three
@@ -3812,6 +3928,13 @@ int configure_model(fasst_ctx *c, int J, const int *rank, const int *K, const in
     c->lgen.release();
   }
   c->w_ready = c->prep_ready = 0;
+  // the E-step's operand images follow the model: the TW image its J and KP
+  // (re-allocated by the next iteration), the Cx image whether it is read
+  c->twp.release();
+  if (!estep_cxi(c)) {
+    c->cxp.release();
+    c->cxp_valid = false;
+  }
 #undef ALLOC
   c->configured = 1;
   return FASST_OK;
@@ -3943,6 +4066,9 @@ static EArgs e_args(const fasst_ctx *c, const double *psd_dev) {
   e.cxr = c->cx.p + 2 * plane;
   e.cxi = c->cx.p + 3 * plane;
   e.TW = c->TW.p;
+  e.cxp = c->cxp.p;
+  e.twp = c->twp.p;
+  e.nttp = c->ntt;
   e.Wkf = c->Wkf.p;
   e.A = c->A.p;
   e.psd = psd_dev;
@@ -4330,10 +4456,43 @@ static int launch_tail_side(fasst_ctx *c) {
 
 // E-step instantiation chosen from the model structure; `f` receives an
 // ETag carrying the template parameters (used for launches and occupancy).
-template <int J_, int NKS_, int RKU_>
+template <int J_, int NKS_, int RKU_, bool CXI_, bool TWI_>
 struct ETag {
   static constexpr int J = J_, NKS = NKS_, RKU = RKU_;
+  static constexpr bool CXI = CXI_, TWI = TWI_;
 };
+
+// does the model's single-pass E-step read the Cx / the TW image (the
+// context's FASST_ESTEP_IMG choice; the TW image on the preload path only)
+// (J = 7 at K = 128 keeps the planes: with the 16-byte loads that one
+// instantiation, already at the whole register file, spills 12 bytes per lane)
+static bool estep_cxi(const fasst_ctx *c) {
+  return c->J <= 8 && (c->eimg & 1) && !(c->J == 7 && c->KP == 128);
+}
+static bool estep_twi(const fasst_ctx *c) {
+  return c->J <= 4 && (c->eimg & 2) && c->J * (c->KP / 4) <= 32;
+}
+
+template <int J, int NKS, int RKU, class F>
+static void estep_dispatch_img(const fasst_ctx *c, F &&f) {
+  const bool cxi = estep_cxi(c);
+  if constexpr (J == 7 && NKS == 32) {   // (never with the Cx image: estep_cxi)
+    f(ETag<J, NKS, RKU, false, false>{});
+  } else {
+    if constexpr (mx_tw_preload<J, NKS>())
+      if (estep_twi(c)) {
+        if (cxi)
+          f(ETag<J, NKS, RKU, true, true>{});
+        else
+          f(ETag<J, NKS, RKU, false, true>{});
+        return;
+      }
+    if (cxi)
+      f(ETag<J, NKS, RKU, true, false>{});
+    else
+      f(ETag<J, NKS, RKU, false, false>{});
+  }
+}
 
 template <int J, int NKS, class F>
 static void estep_dispatch_r(const fasst_ctx *c, F &&f) {
@@ -4343,11 +4502,11 @@ static void estep_dispatch_r(const fasst_ctx *c, F &&f) {
     all2 &= c->rank[j] == 2;
   }
   if (all1)
-    f(ETag<J, NKS, 1>{});
+    estep_dispatch_img<J, NKS, 1>(c, f);
   else if (all2)
-    f(ETag<J, NKS, 2>{});
+    estep_dispatch_img<J, NKS, 2>(c, f);
   else
-    f(ETag<J, NKS, 0>{});
+    estep_dispatch_img<J, NKS, 0>(c, f);
 }
 
 template <int J, class F>
@@ -4356,7 +4515,7 @@ static void estep_dispatch_j(const fasst_ctx *c, F &&f) {
     case 16: estep_dispatch_r<J, 4>(c, f); break;
     case 32: estep_dispatch_r<J, 8>(c, f); break;
     case 64: estep_dispatch_r<J, 16>(c, f); break;
-    default: f(ETag<J, 32, 0>{}); break;   // K up to 128: general ranks only
+    default: estep_dispatch_img<J, 32, 0>(c, f); break;   // K up to 128: general ranks only
   }
 }
 
@@ -4374,12 +4533,41 @@ static void estep_dispatch(const fasst_ctx *c, F &&f) {
   }
 }
 
+// The operand images of the coming k_estep_mx launch (fasst_ctx.h): the Cx
+// image rebuilt if an observation was written since it was packed, the TW
+// image packed from TW unless the previous iteration's fused k_tw_update
+// wrote it (tw_fresh: gem_iteration's prep_ready, which every batch start and
+// every path around the fused tail clears)
+static int estep_images(fasst_ctx *c, bool tw_fresh) {
+  if (estep_cxi(c) && !(c->cxp_valid && c->cxp.p)) {
+    const size_t n = (size_t)c->nft * c->ntt * 512;
+    if (c->cxp.n != n)
+      if (int st = c->cxp.alloc_uninit(n)) return st;
+    k_cx_image<<<dim3(c->ntt, c->nft), 256, 0, c->stream>>>(c->cx.p, c->cxp.p, c->Fp, c->ntt,
+                                                            (size_t)c->Tp * c->Fp);
+    FASST_LAUNCH_CHECK();
+    c->cxp_valid = true;
+  }
+  if (estep_twi(c)) {
+    const size_t n = (size_t)c->ntt * c->J * (c->KP / 8) * 64;
+    if (c->twp.n != n) {
+      if (int st = c->twp.alloc_uninit(n)) return st;
+      tw_fresh = false;
+    }
+    if (!tw_fresh) {
+      k_tw_image<<<dim3(c->ntt, c->J), 256, 0, c->stream>>>(c->TW.p, c->twp.p, c->J, c->KP, c->Tp);
+      FASST_LAUNCH_CHECK();
+    }
+  }
+  return FASST_OK;
+}
+
 static void launch_estep(fasst_ctx *c, const EArgs &e, int ny) {
   estep_dispatch(c, [&](auto tag) {
     using T = decltype(tag);
     prof_begin(c, KESTEP);
     const dim3 g = e.es.bal ? dim3(e.es.nb) : dim3(c->nft, ny);
-    k_estep_mx<T::J, T::NKS, T::RKU><<<g, 256, estep_mx_smem<T::J, T::NKS>(), c->stream>>>(e);
+    k_estep_mx<T::J, T::NKS, T::RKU, T::CXI, T::TWI><<<g, 256, estep_mx_smem<T::J, T::NKS>(), c->stream>>>(e);
     prof_end(c, KESTEP);
   });
 }
@@ -4390,10 +4578,10 @@ static int estep_occupancy(const fasst_ctx *c) {
   estep_dispatch(c, [&](auto tag) {
     using T = decltype(tag);
     constexpr size_t smem = estep_mx_smem<T::J, T::NKS>();
-    (void)hipFuncSetAttribute((const void *)k_estep_mx<T::J, T::NKS, T::RKU>,
+    (void)hipFuncSetAttribute((const void *)k_estep_mx<T::J, T::NKS, T::RKU, T::CXI, T::TWI>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_estep_mx<T::J, T::NKS, T::RKU>, 256,
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_estep_mx<T::J, T::NKS, T::RKU, T::CXI, T::TWI>, 256,
                                                      smem) != hipSuccess)
       n = 1;
     occ = std::max(1, n);
@@ -4488,7 +4676,9 @@ static int check_tail_args(const fasst_ctx *c, const UArgs &u, const TUArgs &tu)
   const bool ok_t = !tu.scal || (tu.scal == c->rscal.p && tu.tpart == c->rtpart2.p &&
                                  (!tu.FWHt || (tu.FWHt == c->FWHt.p && tu.hpart == c->hpart.p &&
                                                tu.FW == c->FW.p)));
-  if (ok_u && ok_t) return FASST_OK;
+  const bool ok_i = !tu.twp || (tu.FWHt && tu.twp == c->twp.p &&
+                                c->twp.n == (size_t)c->ntt * c->J * (c->KP / 8) * 64);
+  if (ok_u && ok_t && ok_i) return FASST_OK;
   set_error("internal: fused renormalisation arguments do not point at the context's buffers");
   return FASST_ERR_SHAPE;
 }
@@ -4736,6 +4926,7 @@ static int spectral_update(fasst_ctx *c, double omega, bool tail = false) {
   const bool prep = tail && c->ftail >= 2 && c->KP <= 64;
   tu.FWHt = prep ? c->FWHt.p : nullptr;
   tu.hpart = c->hpart.p;
+  tu.twp = prep && estep_twi(c) ? c->twp.p : nullptr;   // (allocated by the iteration's E-step)
   launch_fb_contract(c, b, false, true);
   FASST_LAUNCH_CHECK();
   if (int st = launch_fb_update(c, u, tu, true)) return st;
@@ -4824,7 +5015,8 @@ static int gem_iteration(fasst_ctx *c, const double *psd_dev, double *ll_dev, do
     k_egen_stats<<<dim3(c->nft, c->nchunk_e), kEgsThreads, lds, c->stream>>>(e, gg);
     prof_end(c, KESTEP);
   } else {
-    launch_estep(c, e, c->nchunk_e);
+    if ((st = estep_images(c, prep_ready))) return st;
+    launch_estep(c, e_args(c, psd_dev), c->nchunk_e);
   }
   FASST_LAUNCH_CHECK();
   if (!prep_ready) FASST_HIP(hipStreamWaitEvent(c->stream, c->ev_join, 0));  // hsum, FWHt below
@@ -4914,6 +5106,8 @@ int fasst_create(int device, int F, int T, fasst_ctx **out) {
   c->nft = c->Fp / kTile;
   c->ntt = c->Tp / kTile;
   if (const char *v = getenv("FASST_FAST_TAIL")) c->ftail = atoi(v);
+  if (const char *v = getenv("FASST_ESTEP_IMG"))
+    c->eimg = !strcmp(v, "cx") ? 1 : (!strcmp(v, "tw") ? 2 : (!strcmp(v, "0") ? 0 : 3));
   int st = FASST_OK;
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
       hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking) != hipSuccess ||
@@ -4963,6 +5157,8 @@ int fasst_destroy(fasst_ctx *c) {
     if (c->h_flags) (void)hipHostFree(c->h_flags);
     if (c->h_ll) (void)hipHostFree(c->h_ll);
     c->cx.release();
+    c->cxp.release();
+    c->twp.release();
     c->X.release();
     c->FB.release();
     c->FW.release();

@@ -881,6 +881,7 @@ int fasst_set_audio(fasst_ctx *c, const double *data, int L, const double *windo
   FASST_HIP(hipStreamSynchronize(c->stream));
   c->have_X = true;
   c->cx_ready = true;
+  c->cxp_valid = false;   // (the E-step rebuilds its Cx image from the new planes)
   return FASST_OK;
 }
 
@@ -912,6 +913,7 @@ int fasst_set_cx(fasst_ctx *c, const double *cx) {
   FASST_LAUNCH_CHECK();
   FASST_HIP(hipStreamSynchronize(c->stream));
   c->cx_ready = true;
+  c->cxp_valid = false;   // (the E-step rebuilds its Cx image from the new planes)
   return FASST_OK;
 }
 
@@ -956,6 +958,7 @@ int fasst_set_stft(fasst_ctx *c, const double *X) {
   FASST_LAUNCH_CHECK();
   FASST_HIP(hipStreamSynchronize(c->stream));
   c->cx_ready = true;
+  c->cxp_valid = false;   // (the E-step rebuilds its Cx image from the new planes)
   return FASST_OK;
 }
 
@@ -1301,6 +1304,7 @@ int fasst_set_audio_cqt(fasst_ctx *c, cqt_ctx *q, const double *data, long L) {
   FASST_HIP(hipStreamSynchronize(c->stream));
   c->have_X = true;
   c->cx_ready = true;
+  c->cxp_valid = false;   // (the E-step rebuilds its Cx image from the new planes)
   return FASST_OK;
 }
 
