@@ -49,8 +49,10 @@ typedef struct fasst_ctx fasst_ctx;
  * (source / filter) spectral components (fasst_sf_* and fasst_set_factors /
  * fasst_get_factors).  Revision 6 adds fasst_estep_partition.  Revision 7 adds
  * the source / filter IS-NMF (sfnmf_*, fasst_nmf.h).  Revision 8 adds the
- * stereo accompaniment IS-NMF (snmf_*, fasst_simm.h). */
-#define FASST_ABI_VERSION 8
+ * stereo accompaniment IS-NMF (snmf_*, fasst_simm.h).  Revision 9 adds the
+ * GEMM layer's test entry points (fasst_gemm_plan, fasst_gemm_probe,
+ * fasst_dgemm2_probe). */
+#define FASST_ABI_VERSION 9
 int fasst_abi_version(void);
 
 /* The E-step's balanced schedule, host arithmetic only (no device call;
@@ -62,6 +64,44 @@ int fasst_abi_version(void);
  * Needs 1 <= nb <= nbt Q < 2^30. */
 int fasst_estep_partition(int nbt, int Q, int nb, long long *lo, int *first, int *nseg,
                           int *max_slots);
+
+/* The FP64 MFMA GEMM layer (pyfasst_amd/csrc/fasst_gemm.h, fasst_dgemm2.h),
+ * exported so that tests can pin it directly.
+ *
+ * fasst_gemm_plan: host arithmetic only (no device call).  What gemm<.., NB>
+ * does with an M x N x K product: the split-K count *nz it runs when given a
+ * workspace, the K range *kchunk of one split, the k_gemm tile shape
+ * (*wgm, *wtm, *wtn: a wgm x 4/wgm wave grid of wtm x wtn MFMA tiles) and the
+ * workspace *work_doubles it needs (0: no split).  A null pointer is skipped.
+ * Needs M, N, K >= 1 and NB in {1, 2, 4}. */
+int fasst_gemm_plan(int M, int N, int K, int NB, int *nz, int *kchunk, int *wgm, int *wtm,
+                    int *wtn, long long *work_doubles);
+/* One gemm<ta, tb, nb> call, C_b = opA opB_b for b < nb, on host operands.
+ * A is [M][lda] (ta: [K][lda]); B holds the nb operands back to back, each
+ * [K][ldb] (tb: [N][ldb]); C holds the nb outputs back to back, each [M][ldc].
+ * Every array is uploaded whole with the given leading dimensions (C too:
+ * elements the product does not own come back as they went in) and the call
+ * runs on a stream of its own.  use_work bit 0: pass a workspace of
+ * fasst_gemm_plan's work_doubles followed by a guard tail (otherwise none is
+ * passed and the product runs unsplit); bit 1 (tb == 0 only): B is one
+ * [K][ldb] array and operand b is its column block b N .. b N + N - 1.
+ * *nz_ran: the split count that ran.  *guard_ok: the guard tails behind the
+ * operands, outputs and workspace are bit-intact.  (ta, tb, nb) outside the
+ * instantiated forms (0,0,1) (1,0,1) (1,0,2) (1,0,4) (0,1,1) (0,1,2) returns
+ * FASST_ERR_UNSUPPORTED; a split product with ldc != N FASST_ERR_SHAPE. */
+int fasst_gemm_probe(int device, int ta, int tb, int nb, int M, int N, int K, const double *A,
+                     int lda, const double *B, int ldb, double *C, int ldc, int use_work,
+                     int *nz_ran, int *guard_ok);
+/* One dgemm2 call, C [M][ldc] = A^T B with A [K][lda] and B [K][ldb], in the
+ * same way.  a_skew / b_skew in {0, 1} put the device operand one double past
+ * a 16-byte boundary (the 4-byte-piece arms with an even leading dimension);
+ * A == B with equal lda / ldb and skews runs on one device buffer.  flat = 1
+ * keeps the 16-byte form on flat-address pieces.  *arm: 0 D2Prod raw-buffer
+ * pieces, 1 D2Prod flat pieces, 2 D2Odd with B in 4-byte pieces, 3 D2Odd with
+ * A, 4 D2Odd with both.  A damaged guard tail returns FASST_ERR_DEVICE. */
+int fasst_dgemm2_probe(int device, int M, int N, int K, const double *A, int lda, int a_skew,
+                       const double *B, int ldb, int b_skew, double *C, int ldc, int flat,
+                       int *arm);
 
 const char *fasst_last_error(void);
 int fasst_device_count(int *n);

@@ -47,6 +47,14 @@ SIGNATURES = {
     "fasst_last_error": (ctypes.c_char_p, []),
     "fasst_device_count": (ctypes.c_int, [_ip]),
     "fasst_estep_partition": (ctypes.c_int, [ctypes.c_int] * 3 + [_llp, _ip, _ip, _ip]),
+    "fasst_gemm_plan": (ctypes.c_int, [ctypes.c_int] * 4 + [_ip] * 5 + [_llp]),
+    "fasst_gemm_probe": (ctypes.c_int, [ctypes.c_int] * 7 + [_dp, ctypes.c_int, _dp, ctypes.c_int,
+                                                             _dp, ctypes.c_int, ctypes.c_int, _ip,
+                                                             _ip]),
+    "fasst_dgemm2_probe": (ctypes.c_int, [ctypes.c_int] * 4 + [_dp, ctypes.c_int, ctypes.c_int,
+                                                               _dp, ctypes.c_int, ctypes.c_int,
+                                                               _dp, ctypes.c_int, ctypes.c_int,
+                                                               _ip]),
     "fasst_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
     "fasst_configure": (ctypes.c_int, [_vp, ctypes.c_int, _ip, _ip, ctypes.c_int]),
     "fasst_configure_types": (ctypes.c_int, [_vp, ctypes.c_int, _ip, _ip, _ip]),
@@ -244,8 +252,9 @@ for _name, (_res, _args) in SIGNATURES.items():
 # revision 3: fasst_spatial_filter_* and fasst_gcc_phat; revision 4:
 # fasst_set_tw_constr / fasst_get_tw_constr; revision 5: the two-factor model,
 # fasst_sf_* and fasst_set_factors / fasst_get_factors; revision 6:
-# fasst_estep_partition; revision 7: sfnmf_*; revision 8: snmf_*)
-ABI_VERSION = 8
+# fasst_estep_partition; revision 7: sfnmf_*; revision 8: snmf_*; revision 9:
+# fasst_gemm_plan / fasst_gemm_probe / fasst_dgemm2_probe)
+ABI_VERSION = 9
 if lib.fasst_abi_version() != ABI_VERSION:
     raise ImportError("pyfasst_amd: %s has ABI revision %d, this binding expects %d; rebuild it "
                       "(make -C pyfasst_amd/csrc)" % (LIB_PATH, lib.fasst_abi_version(), ABI_VERSION))

@@ -359,23 +359,34 @@ __global__ void k_gemm_reduce(const double *__restrict__ part, int nz, size_t sl
                               double *__restrict__ out, size_t n);
 
 // Host helper: C_b = opA * opB_b with an automatic split-K when the output
-// tile grid would leave the chip idle.  `work` must hold nz*M*ldc doubles per
-// output when split (query with gemm_workspace).
+// tile grid would leave the chip idle.  `work` must hold NB*nz*M*N doubles
+// when split (query with gemm_workspace); a split product needs ldc == N and
+// is refused (FASST_ERR_SHAPE, nothing launched) otherwise.  Without `work`
+// the product runs unsplit.  *nz_ran, if given, receives the split count run.
 struct GemmPlan {
   int nz = 1, kchunk = 0;
 };
 GemmPlan gemm_plan(int M, int N, int K, int NB);
 template <bool TA, bool TB, int NB>
 int gemm(hipStream_t s, const double *A, int lda, const double *const *B, int ldb, double *const *C,
-         int ldc, int M, int N, int K, double *work);
+         int ldc, int M, int N, int K, double *work, int *nz_ran = nullptr);
 // doubles of `work` gemm() needs for these sizes (0: no split)
 size_t gemm_workspace(int M, int N, int K, int NB);
 
 // Large plain products (the Stereo_SIMM NF0-sized ones): row-major
 // C (M x N) = A^T B with A given k-major [K][lda] and B [K][ldb], on k_dgemm2
 // (fasst_dgemm2.h: global_load_lds stages, 4x4x4_4b MFMA).  Rows that are not
-// 16-byte aligned (odd lda / ldb) are loaded in 4-byte pieces.
+// 16-byte aligned (odd lda / ldb) are loaded in 4-byte pieces.  allow_buf =
+// false keeps the 16-byte form off the raw-buffer pieces (the flat-address arm
+// that operands past 2 GB take); *arm, if given, receives the arm launched.
+enum Dgemm2Arm {
+  kD2ArmProdBuf = 0,   // D2Prod, raw-buffer LDS-DMA pieces
+  kD2ArmProdFlat = 1,  // D2Prod, flat global_load_lds pieces
+  kD2ArmOddB4 = 2,     // D2Odd, B in 4-byte pieces
+  kD2ArmOddA4 = 3,     // D2Odd, A in 4-byte pieces
+  kD2ArmOddA4B4 = 4    // D2Odd, both in 4-byte pieces
+};
 int dgemm2(hipStream_t s, int M, int N, int K, const double *A, int lda, const double *B, int ldb,
-           double *C, int ldc);
+           double *C, int ldc, bool allow_buf = true, int *arm = nullptr);
 
 }  // namespace fasst

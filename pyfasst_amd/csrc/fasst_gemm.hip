@@ -95,8 +95,14 @@ static int launch_shape(hipStream_t s, const GemmArgs &g, int nz) {
 
 template <bool TA, bool TB, int NB>
 int gemm(hipStream_t s, const double *A, int lda, const double *const *B, int ldb, double *const *C,
-         int ldc, int M, int N, int K, double *work) {
+         int ldc, int M, int N, int K, double *work, int *nz_ran) {
   GemmPlan p = gemm_plan(M, N, K, NB);
+  const bool split = p.nz > 1 && work;
+  if (split && ldc != N) {  // split-K outputs must be dense: refuse before any launch
+    set_error("gemm: split-K (nz %d) needs ldc == N (ldc %d, N %d)", p.nz, ldc, N);
+    return FASST_ERR_SHAPE;
+  }
+  if (nz_ran) *nz_ran = split ? p.nz : 1;
   GemmArgs g;
   g.A = A;
   g.lda = lda;
@@ -105,7 +111,7 @@ int gemm(hipStream_t s, const double *A, int lda, const double *const *B, int ld
   g.N = N;
   g.K = K;
   g.kchunk = p.kchunk;
-  if (p.nz == 1 || !work) {
+  if (!split) {
     g.kchunk = K;
     g.ldc = ldc;
     g.slab = 0;
@@ -126,12 +132,8 @@ int gemm(hipStream_t s, const double *A, int lda, const double *const *B, int ld
   int st = launch_shape<TA, TB, NB>(s, g, p.nz);
   if (st) return st;
   for (int b = 0; b < NB; ++b) {
-    if (ldc == N) {
-      k_gemm_reduce<<<(int)std::min<size_t>((slab + 255) / 256, 4096), 256, 0, s>>>(
-          work + (size_t)b * p.nz * slab, p.nz, slab, C[b], slab);
-    } else {
-      return FASST_ERR_SHAPE;  // split-K outputs must be dense
-    }
+    k_gemm_reduce<<<(int)std::min<size_t>((slab + 255) / 256, 4096), 256, 0, s>>>(
+        work + (size_t)b * p.nz * slab, p.nz, slab, C[b], slab);
     FASST_LAUNCH_CHECK();
   }
   return FASST_OK;
@@ -151,12 +153,18 @@ static int launch_dgemm2(hipStream_t s, Dgemm2Args g) {
   return FASST_OK;
 }
 
-int dgemm2(hipStream_t s, int M, int N, int K, const double *A, int lda, const double *B, int ldb,
-           double *C, int ldc) {
+// dgemm2's argument check (also what fasst_dgemm2_probe sizes its buffers by)
+static int dgemm2_check(int M, int N, int K, int lda, int ldb, int ldc) {
   if (M <= 0 || N <= 0 || K <= 0 || lda < M || ldb < N || ldc < N) {
     set_error("dgemm2: bad shape M %d N %d K %d (lda %d ldb %d ldc %d)", M, N, K, lda, ldb, ldc);
     return FASST_ERR_SHAPE;
   }
+  return FASST_OK;
+}
+
+int dgemm2(hipStream_t s, int M, int N, int K, const double *A, int lda, const double *B, int ldb,
+           double *C, int ldc, bool allow_buf, int *arm) {
+  if (int st = dgemm2_check(M, N, K, lda, ldb, ldc)) return st;
   Dgemm2Args g{};
   g.A = A;
   g.B = B;
@@ -173,11 +181,16 @@ int dgemm2(hipStream_t s, int M, int N, int K, const double *A, int lda, const d
   // the stereo SIMM iteration 9.19 -> 8.80 ms against the flat-address form
   const bool fits = (size_t)K * lda * sizeof(double) < (1ull << 31) &&
                     (size_t)K * ldb * sizeof(double) < (1ull << 31);
-  if (a16 && b16 && fits) return launch_dgemm2<D2Prod, false, false, true>(s, g);
-  if (a16 && b16) return launch_dgemm2<D2Prod, false, false>(s, g);
-  if (a16) return launch_dgemm2<D2Odd, false, true>(s, g);
-  if (b16) return launch_dgemm2<D2Odd, true, false>(s, g);
-  return launch_dgemm2<D2Odd, true, true>(s, g);
+  const int which = a16 && b16 ? (fits && allow_buf ? kD2ArmProdBuf : kD2ArmProdFlat)
+                               : (a16 ? kD2ArmOddB4 : (b16 ? kD2ArmOddA4 : kD2ArmOddA4B4));
+  if (arm) *arm = which;
+  switch (which) {
+    case kD2ArmProdBuf: return launch_dgemm2<D2Prod, false, false, true>(s, g);
+    case kD2ArmProdFlat: return launch_dgemm2<D2Prod, false, false>(s, g);
+    case kD2ArmOddB4: return launch_dgemm2<D2Odd, false, true>(s, g);
+    case kD2ArmOddA4: return launch_dgemm2<D2Odd, true, false>(s, g);
+    default: return launch_dgemm2<D2Odd, true, true>(s, g);
+  }
 }
 
 size_t gemm_workspace(int M, int N, int K, int NB) {
@@ -186,16 +199,192 @@ size_t gemm_workspace(int M, int N, int K, int NB) {
 }
 
 template int gemm<false, false, 1>(hipStream_t, const double *, int, const double *const *, int,
-                                   double *const *, int, int, int, int, double *);
+                                   double *const *, int, int, int, int, double *, int *);
 template int gemm<true, false, 1>(hipStream_t, const double *, int, const double *const *, int,
-                                  double *const *, int, int, int, int, double *);
+                                  double *const *, int, int, int, int, double *, int *);
 template int gemm<true, false, 2>(hipStream_t, const double *, int, const double *const *, int,
-                                  double *const *, int, int, int, int, double *);
+                                  double *const *, int, int, int, int, double *, int *);
 template int gemm<true, false, 4>(hipStream_t, const double *, int, const double *const *, int,
-                                  double *const *, int, int, int, int, double *);
+                                  double *const *, int, int, int, int, double *, int *);
 template int gemm<false, true, 1>(hipStream_t, const double *, int, const double *const *, int,
-                                  double *const *, int, int, int, int, double *);
+                                  double *const *, int, int, int, int, double *, int *);
 template int gemm<false, true, 2>(hipStream_t, const double *, int, const double *const *, int,
-                                  double *const *, int, int, int, int, double *);
+                                  double *const *, int, int, int, int, double *, int *);
+
+// ---------------------------------------------------------------------------
+// Test entry points (include/fasst_hip.h): the plan as the host computes it,
+// and one gemm<> / dgemm2 call on caller-given operands with guarded buffers.
+namespace {
+
+// bit pattern of the guard tails: a finite double no product here computes
+constexpr unsigned long long kGuardBits = 0x4757415244454421ull;
+
+// a device buffer of n payload doubles, `skew` doubles past the allocation's
+// (16-byte aligned) base, followed by `tail` guard doubles
+struct GuardBuf {
+  DBuf<double> d;
+  size_t n = 0, skew = 0, tail = 0;
+  double *p() const { return d.p + skew; }
+  int alloc(size_t count, size_t guard, size_t sk = 0) {
+    n = count;
+    skew = sk;
+    tail = guard;
+    int st = d.alloc_uninit(sk + count + guard);
+    if (st) return st;
+    std::vector<unsigned long long> g(sk + guard, kGuardBits);
+    if (sk) FASST_HIP(hipMemcpy(d.p, g.data(), sk * sizeof(double), hipMemcpyHostToDevice));
+    FASST_HIP(hipMemcpy(d.p + sk + count, g.data(), guard * sizeof(double), hipMemcpyHostToDevice));
+    return FASST_OK;
+  }
+  int upload(const double *h) {
+    FASST_HIP(hipMemcpy(p(), h, n * sizeof(double), hipMemcpyHostToDevice));
+    return FASST_OK;
+  }
+  int download(double *h) const {
+    FASST_HIP(hipMemcpy(h, p(), n * sizeof(double), hipMemcpyDeviceToHost));
+    return FASST_OK;
+  }
+  // *ok &= every guard double still holds kGuardBits
+  int intact(int *ok) const {
+    std::vector<unsigned long long> g(skew + tail);
+    if (skew) FASST_HIP(hipMemcpy(g.data(), d.p, skew * sizeof(double), hipMemcpyDeviceToHost));
+    FASST_HIP(hipMemcpy(g.data() + skew, d.p + skew + n, tail * sizeof(double), hipMemcpyDeviceToHost));
+    for (unsigned long long v : g)
+      if (v != kGuardBits) *ok = 0;
+    return FASST_OK;
+  }
+};
+
+struct ProbeStream {
+  hipStream_t s = nullptr;
+  int create() {
+    FASST_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    return FASST_OK;
+  }
+  ~ProbeStream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+};
+
+constexpr size_t kProbeTail = 512;  // guard doubles behind operands and outputs
+
+}  // namespace
 
 }  // namespace fasst
+
+using namespace fasst;
+
+extern "C" {
+
+int fasst_gemm_plan(int M, int N, int K, int NB, int *nz, int *kchunk, int *wgm, int *wtm, int *wtn,
+                    long long *work_doubles) {
+  if (M < 1 || N < 1 || K < 1 || (NB != 1 && NB != 2 && NB != 4)) {
+    set_error("fasst_gemm_plan: need M, N, K >= 1 and NB in {1, 2, 4} (M %d N %d K %d NB %d)", M, N,
+              K, NB);
+    return FASST_ERR_SHAPE;
+  }
+  const GemmPlan p = gemm_plan(M, N, K, NB);
+  const TileShape t = tile_shape(M, N, NB);
+  if (nz) *nz = p.nz;
+  if (kchunk) *kchunk = p.kchunk;
+  if (wgm) *wgm = t.wgm;
+  if (wtm) *wtm = t.wtm;
+  if (wtn) *wtn = t.wtn;
+  if (work_doubles) *work_doubles = (long long)gemm_workspace(M, N, K, NB);
+  return FASST_OK;
+}
+
+int fasst_gemm_probe(int device, int ta, int tb, int nb, int M, int N, int K, const double *A,
+                     int lda, const double *B, int ldb, double *C, int ldc, int use_work,
+                     int *nz_ran, int *guard_ok) {
+  const bool with_work = use_work & 1, bcols = use_work & 2;
+  if (M < 1 || N < 1 || K < 1 || !A || !B || !C || lda < (ta ? M : K) ||
+      ldb < (tb ? K : (bcols ? nb * N : N)) || ldc < N || (use_work & ~3) || (bcols && tb) ||
+      nb < 1 || nb > 4) {
+    set_error("fasst_gemm_probe: bad arguments (ta %d tb %d nb %d M %d N %d K %d lda %d ldb %d "
+              "ldc %d use_work %d)", ta, tb, nb, M, N, K, lda, ldb, ldc, use_work);
+    return FASST_ERR_SHAPE;
+  }
+  typedef int (*gemm_fn)(hipStream_t, const double *, int, const double *const *, int,
+                         double *const *, int, int, int, int, double *, int *);
+  gemm_fn fn = nullptr;
+  if (!ta && !tb && nb == 1) fn = gemm<false, false, 1>;
+  if (ta && !tb && nb == 1) fn = gemm<true, false, 1>;
+  if (ta && !tb && nb == 2) fn = gemm<true, false, 2>;
+  if (ta && !tb && nb == 4) fn = gemm<true, false, 4>;
+  if (!ta && tb && nb == 1) fn = gemm<false, true, 1>;
+  if (!ta && tb && nb == 2) fn = gemm<false, true, 2>;
+  if (!fn) {
+    set_error("fasst_gemm_probe: gemm<%d, %d, %d> is not instantiated", ta != 0, tb != 0, nb);
+    return FASST_ERR_UNSUPPORTED;
+  }
+  DeviceGuard dg(device);
+  const size_t na = (size_t)(ta ? K : M) * lda;
+  const size_t nb1 = (size_t)(tb ? N : K) * ldb;      // one B operand (all of them with bcols)
+  const size_t nbs = bcols ? nb1 : nb * nb1;
+  const size_t nc1 = (size_t)M * ldc;
+  const size_t nw = gemm_workspace(M, N, K, nb);
+  GuardBuf dA, dB, dC, dW;
+  ProbeStream ps;
+  int st;
+  if ((st = dA.alloc(na, kProbeTail)) || (st = dB.alloc(nbs, kProbeTail)) ||
+      (st = dC.alloc(nb * nc1, kProbeTail)) || (st = dA.upload(A)) || (st = dB.upload(B)) ||
+      (st = dC.upload(C)) || (st = ps.create()))
+    return st;
+  // the workspace, then a guard tail of one slab (M N doubles) at least
+  if (with_work && (st = dW.alloc(nw, std::max((size_t)M * N, kProbeTail)))) return st;
+  FASST_HIP(hipDeviceSynchronize());
+  const double *Bs[4] = {nullptr, nullptr, nullptr, nullptr};
+  double *Cs[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int b = 0; b < nb; ++b) {
+    Bs[b] = dB.p() + (bcols ? (size_t)b * N : b * nb1);
+    Cs[b] = dC.p() + b * nc1;
+  }
+  int ran = 0;
+  st = fn(ps.s, dA.p(), lda, Bs, ldb, Cs, ldc, M, N, K, with_work ? dW.p() : nullptr, &ran);
+  if (st) return st;
+  FASST_HIP(hipStreamSynchronize(ps.s));
+  if ((st = dC.download(C))) return st;
+  int ok = 1;
+  if ((st = dA.intact(&ok)) || (st = dB.intact(&ok)) || (st = dC.intact(&ok)) ||
+      (with_work && (st = dW.intact(&ok))))
+    return st;
+  if (nz_ran) *nz_ran = ran;
+  if (guard_ok) *guard_ok = ok;
+  return FASST_OK;
+}
+
+int fasst_dgemm2_probe(int device, int M, int N, int K, const double *A, int lda, int a_skew,
+                       const double *B, int ldb, int b_skew, double *C, int ldc, int flat, int *arm) {
+  int st;
+  if ((st = dgemm2_check(M, N, K, lda, ldb, ldc))) return st;
+  if (!A || !B || !C || (a_skew & ~1) || (b_skew & ~1)) {
+    set_error("fasst_dgemm2_probe: bad arguments (a_skew %d b_skew %d)", a_skew, b_skew);
+    return FASST_ERR_SHAPE;
+  }
+  DeviceGuard dg(device);
+  const bool same = A == B && lda == ldb && a_skew == b_skew;   // one buffer as both operands
+  GuardBuf dA, dB, dC;
+  ProbeStream ps;
+  // an odd skew + payload keeps the tail 16-byte aligned or not: either is a guard
+  if ((st = dA.alloc((size_t)K * lda, kProbeTail, a_skew)) || (st = dA.upload(A)) ||
+      (!same && ((st = dB.alloc((size_t)K * ldb, kProbeTail, b_skew)) || (st = dB.upload(B)))) ||
+      (st = dC.alloc((size_t)M * ldc, kProbeTail)) || (st = dC.upload(C)) || (st = ps.create()))
+    return st;
+  FASST_HIP(hipDeviceSynchronize());
+  int which = -1;
+  st = dgemm2(ps.s, M, N, K, dA.p(), lda, same ? dA.p() : dB.p(), ldb, dC.p(), ldc, !flat, &which);
+  if (st) return st;
+  FASST_HIP(hipStreamSynchronize(ps.s));
+  if ((st = dC.download(C))) return st;
+  int ok = 1;
+  if ((st = dA.intact(&ok)) || (!same && (st = dB.intact(&ok))) || (st = dC.intact(&ok))) return st;
+  if (!ok) {
+    set_error("fasst_dgemm2_probe: a guard tail was overwritten");
+    return FASST_ERR_DEVICE;
+  }
+  if (arm) *arm = which;
+  return FASST_OK;
+}
+
+}  // extern "C"
