@@ -52,7 +52,7 @@ typedef struct fasst_ctx fasst_ctx;
  * stereo accompaniment IS-NMF (snmf_*, fasst_simm.h).  Revision 9 adds the
  * GEMM layer's test entry points (fasst_gemm_plan, fasst_gemm_probe,
  * fasst_dgemm2_probe). */
-#define FASST_ABI_VERSION 9
+#define FASST_ABI_VERSION 10
 int fasst_abi_version(void);
 
 /* The E-step's balanced schedule, host arithmetic only (no device call;
@@ -318,7 +318,22 @@ int fasst_gcc_phat(fasst_ctx *ctx, int nfft, double *out);
  * fasst_sf_wiener_images / fasst_sf_separate_waveforms: as fasst_wiener_images
  * (resident STFT only) / fasst_separate_waveforms with the sources given here:
  * source n sums the spatial components j with src_of[j] == n (-1: in none);
- * S out complex128 [nsrc][2][F][T], y out float64 [nsrc][2][len].            */
+ * S out complex128 [nsrc][2][F][T], y out float64 [nsrc][2][len].
+ *
+ * Sparsity reweighting (reweigh_sparsity_constraint, audioModel.py:2981-3014).
+ * fasst_sf_set_sparsity: length[J], the median filter length of component j's
+ * barycentre track (0: the component is not reweighed); cleared by
+ * fasst_sf_configure.  fasst_sf_reweigh(sigma > 0): for j = 0 .. J-1 in order,
+ * where length[j] > 0 and factor 0 has Kw > 2, TW of factor 0 (the buffer in
+ * use: one shared by two components is multiplied twice) is multiplied in
+ * place by the Gaussian mask of width sigma around the median-filtered
+ * barycentre of its columns (k_sf_bary, then k_sf_sparsify).
+ * fasst_sf_run_sparse: fasst_sf_run with fasst_sf_reweigh(sigma[it]) after
+ * every iteration it whose flags are clean.  An iteration that flags a dead TW
+ * returns FASST_TW_RESTART with *iters_done = it + 1 WITHOUT that iteration's
+ * reweigh: the reference redraws TW inside GEM_iteration (:2023-2028), before
+ * the reweigh of the same loop pass (:2966-2977), so the caller redraws,
+ * uploads, calls fasst_sf_reweigh(sigma[it]) and resumes at it + 1.          */
 int fasst_sf_configure(fasst_ctx *ctx, int J, const int *rank, const int *mix_conv, const int *nfac,
                        const int *Kb, const int *Kw, const int *priors, const int *alias);
 int fasst_sf_set_spatial(fasst_ctx *ctx, int j, const double *params, int free_);
@@ -329,6 +344,10 @@ int fasst_get_factors(fasst_ctx *ctx, int j, int i, double *FB, double *FW, doub
 int fasst_sf_renormalize(fasst_ctx *ctx, int *restart_mask);
 int fasst_sf_run(fasst_ctx *ctx, int n_iter, const double *psd, double omega, double *logliks,
                  int *restart_mask, int *iters_done);
+int fasst_sf_set_sparsity(fasst_ctx *ctx, const int *length);
+int fasst_sf_reweigh(fasst_ctx *ctx, double sigma);
+int fasst_sf_run_sparse(fasst_ctx *ctx, int n_iter, const double *psd, double omega,
+                        const double *sigma, double *logliks, int *restart_mask, int *iters_done);
 int fasst_sf_wiener_images(fasst_ctx *ctx, const double *psd, int nsrc, const int *src_of, double *S);
 int fasst_sf_separate_waveforms(fasst_ctx *ctx, const double *psd, int nsrc, const int *src_of,
                                 const double *window, const double *analysis_window, int wlen,

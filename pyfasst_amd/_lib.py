@@ -128,6 +128,10 @@ SIGNATURES = {
     "fasst_get_factors": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp]),
     "fasst_sf_renormalize": (ctypes.c_int, [_vp, _ip]),
     "fasst_sf_run": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_double, _dp, _ip, _ip]),
+    "fasst_sf_set_sparsity": (ctypes.c_int, [_vp, _ip]),
+    "fasst_sf_reweigh": (ctypes.c_int, [_vp, ctypes.c_double]),
+    "fasst_sf_run_sparse": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_double, _dp, _dp, _ip,
+                                           _ip]),
     "fasst_sf_wiener_images": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _ip, _dp]),
     "fasst_sf_separate_waveforms": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _ip, _dp, _dp,
                                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp]),
@@ -253,8 +257,9 @@ for _name, (_res, _args) in SIGNATURES.items():
 # fasst_set_tw_constr / fasst_get_tw_constr; revision 5: the two-factor model,
 # fasst_sf_* and fasst_set_factors / fasst_get_factors; revision 6:
 # fasst_estep_partition; revision 7: sfnmf_*; revision 8: snmf_*; revision 9:
-# fasst_gemm_plan / fasst_gemm_probe / fasst_dgemm2_probe)
-ABI_VERSION = 9
+# fasst_gemm_plan / fasst_gemm_probe / fasst_dgemm2_probe; revision 10:
+# fasst_sf_set_sparsity / fasst_sf_reweigh / fasst_sf_run_sparse)
+ABI_VERSION = 10
 if lib.fasst_abi_version() != ABI_VERSION:
     raise ImportError("pyfasst_amd: %s has ABI revision %d, this binding expects %d; rebuild it "
                       "(make -C pyfasst_amd/csrc)" % (LIB_PATH, lib.fasst_abi_version(), ABI_VERSION))

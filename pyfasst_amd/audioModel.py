@@ -1249,10 +1249,12 @@ class multiChanSourceF0Filter(FASST):
     constructed (its initial renormalisation runs on the host), but
     estim_param_a_post_model() and the separation refuse it by name; choose
     minF0 / maxF0 / stepnoteF0 so that the dictionary has at most 128
-    columns.  A model with `sparsity` set raises
-    NotImplementedError from estim_param_a_post_model(): the reference's
-    schedule needs a host step between iterations and a median filter the
-    package does not have.  initializeFreeMats() starts the source
+    columns.  With `sparsity` set (the median filter length of each
+    component's F0 track) the reference's schedule runs on the device as its
+    own loop body, GEM_iteration() then reweigh_sparsity_constraint(sigma)
+    (k_sf_bary / k_sf_sparsify), or resident through Engine.sf_run_sparse;
+    the fused estim_param_a_post_model() raises NotImplementedError for such
+    a model and names both.  initializeFreeMats() starts the source
     activations from an IS-NMF of the mono power on the source dictionary, at
     any dictionary width.  initSpecCompsWithLabelAndFiles and the
     multichanLead subclass are outside the scope."""
@@ -1412,19 +1414,56 @@ class multiChanSourceF0Filter(FASST):
 
     def estim_param_a_post_model(self, ):
         """audioModel.py:2933-2979 for sparsity=None (reweigh_sparsity_constraint
-        then does nothing): the base class's iterations on the GPU."""
+        then does nothing): the base class's iterations on the GPU, fused in
+        one device call.  With a sparsity constraint the fused call is refused
+        (NotImplementedError): the schedule runs as the reference's own loop
+        body (:2966-2977),
+
+            for i in range(iter_num):
+                logliks[i] = model.GEM_iteration()
+                model.reweigh_sparsity_constraint(sigma_i)
+
+        with sigma_i = exp(log K^2 + (log 9 - log K^2) i / max(iter_num - 1, 1)),
+        K the largest factor-0 TW.shape[0] of the spectral components, both
+        steps on the device; Engine.sf_run_sparse runs the whole schedule
+        without the parameters leaving the GPU."""
         if any(sc.get('sparsity') for sc in self.spec_comps.values()):
             raise NotImplementedError(
-                "multiChanSourceF0Filter with a sparsity constraint: the schedule "
-                "(reweigh_sparsity_constraint, audioModel.py:2981-3014) needs a host step "
-                "between the device iterations and a median filter this package does not have")
+                "multiChanSourceF0Filter with a sparsity constraint: the fused "
+                "estim_param_a_post_model() does not run the sparsity schedule "
+                "(audioModel.py:2939-2977); loop over GEM_iteration() and "
+                "reweigh_sparsity_constraint(sigma), or use Engine.sf_run_sparse")
         return super(multiChanSourceF0Filter, self).estim_param_a_post_model()
 
     def reweigh_sparsity_constraint(self, sigma):
-        """audioModel.py:2981-3014: nothing to do for components without a
-        sparsity constraint (the only ones this class estimates); with one,
-        NotImplementedError (the reference's median filter is not in this
-        package)."""
-        if any(sc.get('sparsity') for sc in self.spec_comps.values()):
-            raise NotImplementedError("reweigh_sparsity_constraint: the sparsity schedule is "
-                                      "outside this package (DESIGN.md 7)")
+        """audioModel.py:2981-3014 on the device (fasst_sf_reweigh): for j in
+        range(nbComps), where spec_comps[j]['sparsity'] is set and factor 0's
+        TW has more than two rows, TW is multiplied in place by the Gaussian
+        mask of width sigma centred on the barycentre of its columns over the
+        F0 axis, median-filtered over spec_comps[j]['sparsity'] frames (the
+        mask's last row, the unvoiced one, holds the column maximum; columns
+        are divided by that maximum where it is > 0).  Uploads the model, runs
+        k_sf_bary and k_sf_sparsify per component, and writes the reweighed TW
+        back into the model's arrays; nothing happens when no component
+        qualifies."""
+        lengths = {}
+        for j in range(self.nbComps):
+            comp = self.spec_comps[j]
+            L = comp['sparsity']
+            if L and comp['factor'][0]['TW'].shape[0] > 2:
+                if int(L) != L or L < 0:
+                    raise ValueError("spec_comps[%d]['sparsity'] = %r is not a median filter "
+                                     "length (an integer > 0)" % (j, L))
+                lengths[comp['spat_comp_ind']] = (j, int(min(L, 2 ** 31 - 1)))
+        if not lengths:
+            return
+        if self.audioObject.channels != 2:
+            raise AttributeError("Nb channels " + str(self.audioObject.channels) +
+                                 " not implemented yet")
+        order, ranks, _, conv = self._structure_sf()
+        self._upload_sf(order, ranks, conv)
+        eng = self._engine
+        eng.sf_set_sparsity([lengths.get(j, (0, 0))[1] for j in range(len(order))])
+        eng.sf_reweigh(sigma)
+        for j, (k, _) in sorted(lengths.items()):
+            self.spec_comps[k]['factor'][0]['TW'][...] = eng.get_factors(j, 0, tw_only=True)

@@ -72,6 +72,41 @@ __device__ __forceinline__ double block_sum(double x, double *s) {
   return r;
 }
 
+// medianFilter's output sample n of a row of N samples (tools/signalTools.py
+// :13-24): the median of the window [max(n - length, 0), min(n + length, N - 1)),
+// an even count averaging the two middle values; an empty window, one that
+// holds a NaN, or a NaN mean (+inf and -inf in the middle) gives `self`, the
+// sample itself.  Selection by rank counting, ties broken by index, so any
+// window length works.  src is indexed by the sample's own index (the row, or
+// an LDS stage of it offset by the stage's first sample); length <= N.
+// A span of more than kMedLdsSpan doubles (48 KiB) is not staged by the callers
+constexpr int kMedLdsSpan = 6144;
+__device__ __forceinline__ double median_at(const double *src, double self, int n, int length, int N) {
+#pragma clang fp contract(off)
+  const int lo = max(n - length, 0);
+  const int hi = (int)min((long)n + length, (long)N - 1);
+  const int cnt = hi - lo;
+  if (cnt <= 0) return self;
+  bool has_nan = false;
+  for (int i = lo; i < hi; ++i) has_nan |= src[i] != src[i];
+  if (has_nan) return self;
+  const int k1 = (cnt - 1) >> 1, k2 = cnt >> 1;
+  double v1 = 0.0, v2 = 0.0;
+  int found = 0;
+  for (int i = lo; i < hi && found < 2; ++i) {
+    const double xi = src[i];
+    int rank = 0;
+    for (int j = lo; j < hi; ++j) {
+      const double xj = src[j];
+      rank += (xj < xi) || (xj == xi && j < i);
+    }
+    if (rank == k1) { v1 = xi; ++found; }
+    if (rank == k2) { v2 = xi; ++found; }
+  }
+  const double res = k1 == k2 ? v1 : (v1 + v2) / 2.0;
+  return res != res ? self : res;
+}
+
 __device__ __forceinline__ double2 cmul(double2 a, double2 b) {
   return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }

@@ -38,6 +38,10 @@ struct fasst_sf_model {
   // contraction outputs and the split-K workspace of the MFMA GEMM
   fasst::DBuf<double> cn, cd, xn, xd, fwh, work;
   int psd_cap = 0;
+  // sparsity reweighting (fasst_sf_set_sparsity): the median length of
+  // component j's barycentre track (0: none) and the track itself, mu [T]
+  int sparsity[fasst::kMaxJ] = {0};
+  fasst::DBuf<double> mu;
 };
 
 namespace fasst {

@@ -17,6 +17,10 @@
 //   renorm    k_sf_energy per source, k_sf_renorm per factor (the energy handed
 //             from factor to factor as the reference does)
 // Every reduction has a fixed order: two runs are bit-equal.
+//
+// Between iterations, for a model with sparsity lengths (fasst_sf_run_sparse,
+// fasst_sf_reweigh): reweigh_sparsity_constraint (:2981-3014) on factor 0's
+// TW, k_sf_bary then k_sf_sparsify per component.
 #include "fasst_sf.h"
 #include "fasst_cqt_dev.h"
 #include "fasst_fft.h"
@@ -29,7 +33,7 @@
 namespace fasst {
 
 enum { KSF_GEMM = fasst_ctx::kSfSlot0, KSF_PROD, KSF_RATIO, KSF_UPDATE, KSF_RENORM, KSF_WIENER, KSF_OTHER,
-       KSF_HATW, KSF_ENERGY };
+       KSF_HATW, KSF_ENERGY, KSF_BARY, KSF_SPARSIFY };
 static inline void sf_count(fasst_ctx *c, int id) {
   if (c->prof) c->prof_cnt[id] += 1;
 }
@@ -165,6 +169,86 @@ __global__ __launch_bounds__(256) void k_sf_renorm(double *__restrict__ FB, doub
   }
   if (dead || last) return;
   for (size_t i = tid; i < n; i += 256) TW[i] /= ge;
+}
+
+// reweigh_sparsity_constraint (audioModel.py:2981-3014) on one TW [K][T], K > 2,
+// in two launches: a frame's median window holds the barycentres of up to 2 L
+// neighbouring frames, and in one in-place launch another block could have
+// multiplied those columns of TW before they were read.
+//
+// mu[t] = sum_{k<K-1} k (K-1-k)^2 TW[k,t] / sum_{k<K-1} (K-1-k)^2 max(TW[k,t], eps):
+// one thread per frame, the rows in ascending order (loads coalesce over t)
+constexpr int kBaryBlock = 64;
+__global__ __launch_bounds__(kBaryBlock) void k_sf_bary(const double *__restrict__ TW, int K, int T,
+                                                        double *__restrict__ mu) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * kBaryBlock + threadIdx.x;
+  if (t >= T) return;
+  const double *p = TW + t;
+  double num = 0.0, den = 0.0;
+#pragma unroll 8
+  for (int k = 0; k < K - 1; ++k) {
+    const double v = p[(size_t)k * T];
+    const double d = (double)(K - 1 - k), w = d * d;
+    num += (double)k * w * v;
+    den += w * fmax(v, kEps);
+  }
+  mu[t] = num / den;
+}
+
+// TW[k,t] *= m[k] / max_k m[k], m[k] = exp(-0.5 (k - med(mu)[t])^2 / sigma), the
+// last row's m replaced by the maximum (no division where the maximum is not
+// > 0).  Block (x, y): frames [256 x, 256 x + 256), rows [rows y, rows y + rows);
+// every block takes the median of its frames itself (medianFilter's windows,
+// median_at; mu staged in LDS over the chunk and its halo when that fits).
+// The maximum over k = 0 .. K-1 needs no pass over the rows: subtraction,
+// square, division and exp are monotone in |k - med| in floating point too, so
+// it is m at the row nearest to med, the larger of its two integer neighbours
+constexpr int kSpChunk = 256;
+
+struct SfSpArgs {
+  double *TW;
+  const double *mu;
+  int K, T, L, rows;
+  double sigma;
+};
+
+__device__ __forceinline__ double sp_mask(double k, double med, double sigma) {
+#pragma clang fp contract(off)
+  const double d = k - med;
+  return exp(-0.5 * (d * d) / sigma);
+}
+
+template <bool kStaged>
+__global__ __launch_bounds__(kSpChunk) void k_sf_sparsify(const SfSpArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) double sm[];  // [kSpChunk + 2 L] if staged
+  const int c0 = blockIdx.x * kSpChunk;
+  // the samples any window of this chunk can hold: [s_lo, s_hi), s_hi <= T - 1
+  const int s_lo = max(c0 - a.L, 0);
+  const int s_hi = (int)min((long)c0 + kSpChunk - 1 + a.L, (long)a.T - 1);
+  if (kStaged) {
+    for (int i = s_lo + (int)threadIdx.x; i < s_hi; i += kSpChunk) sm[i - s_lo] = a.mu[i];
+    __syncthreads();
+  }
+  const double *src = kStaged ? sm - s_lo : a.mu;
+  const int t = c0 + threadIdx.x;
+  if (t >= a.T) return;
+  const double med = median_at(src, a.mu[t], t, a.L, a.T);
+  const double last = (double)(a.K - 1);
+  double top = med;   // a NaN track: a NaN mask, as np.max gives
+  if (med == med) {
+    const double kf = fmin(fmax(floor(med), 0.0), last);
+    top = fmax(sp_mask(kf, med, a.sigma), sp_mask(fmin(kf + 1.0, last), med, a.sigma));
+  }
+  const bool norm = top > 0.0;
+  const int k0 = blockIdx.y * a.rows, k1 = min(k0 + a.rows, a.K);
+  double *p = a.TW + t;
+  for (int k = k0; k < k1; ++k) {
+    double w = k == a.K - 1 ? top : sp_mask((double)k, med, a.sigma);
+    if (norm) w /= top;
+    p[(size_t)k * a.T] *= w;
+  }
 }
 
 // Per-bin Wiener images from the V_j planes (compute_sigma_comp_2d :1327-1372,
@@ -434,6 +518,70 @@ static int sf_flags_mask(fasst_ctx *c, int *mask) {
   return FASST_OK;
 }
 
+// the two reweighting kernels carry device time as well as a launch count
+// while profiling is on: an event pair and a host wait per launch
+static int sf_tick(fasst_ctx *c, int id) {
+  if (c->prof) FASST_HIP(hipEventRecord(c->ev0[id][0], c->stream));
+  return FASST_OK;
+}
+static int sf_tock(fasst_ctx *c, int id) {
+  if (!c->prof) return FASST_OK;
+  float ms = 0.f;
+  int st = elapsed_ms(c->ev0[id][0], c->ev1[id][0], c->stream, &ms);
+  if (st) return st;
+  c->prof_ms[id] += ms;
+  c->prof_cnt[id] += 1;
+  return FASST_OK;
+}
+
+// reweigh_sparsity_constraint (audioModel.py:2987-3014): the components in
+// order, each on the TW its factor 0 uses, so a TW shared by two components is
+// multiplied twice, as the reference's in-place loop does
+static int sf_reweigh(fasst_ctx *c, double sigma) {
+  fasst_sf_model *m = c->sf;
+  const int T = c->T;
+  int st;
+  for (int j = 0; j < m->J; ++j) {
+    const int K = m->fac[j][0].Kw;
+    if (!m->sparsity[j] || K <= 2) continue;
+    if ((st = sf_tick(c, KSF_BARY))) return st;
+    k_sf_bary<<<(T + kBaryBlock - 1) / kBaryBlock, kBaryBlock, 0, c->stream>>>(m->fac[j][0].tw, K, T, m->mu.p);
+    FASST_LAUNCH_CHECK();
+    if ((st = sf_tock(c, KSF_BARY))) return st;
+    SfSpArgs a;
+    a.TW = m->fac[j][0].tw;
+    a.mu = m->mu.p;
+    a.K = K;
+    a.T = T;
+    a.L = std::min(m->sparsity[j], T);   // the same windows, and t + L stays an int
+    a.sigma = sigma;
+    // row slabs: about 1024 blocks in all, no slab under 8 rows
+    const int nchunks = (T + kSpChunk - 1) / kSpChunk;
+    const int want = std::max(1, 1024 / nchunks);
+    a.rows = std::max(8, (K + want - 1) / want);
+    const dim3 grid(nchunks, (K + a.rows - 1) / a.rows);
+    if ((st = sf_tick(c, KSF_SPARSIFY))) return st;
+    if ((long)kSpChunk + 2L * a.L <= kMedLdsSpan)
+      k_sf_sparsify<true><<<grid, kSpChunk, (kSpChunk + 2 * (size_t)a.L) * sizeof(double), c->stream>>>(a);
+    else
+      k_sf_sparsify<false><<<grid, kSpChunk, 0, c->stream>>>(a);
+    FASST_LAUNCH_CHECK();
+    if ((st = sf_tock(c, KSF_SPARSIFY))) return st;
+  }
+  return FASST_OK;
+}
+
+// the mask's width: the maximum over the rows is taken where it must lie for
+// sigma > 0 (k_sf_sparsify)
+static int sf_check_sigma(const double *sigma, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!(sigma[i] > 0.0)) {
+      set_error("reweigh_sparsity_constraint: sigma[%d] = %g is not > 0", i, sigma[i]);
+      return FASST_ERR_SHAPE;
+    }
+  return FASST_OK;
+}
+
 static int sf_launch_wiener(fasst_ctx *c, const double *dpsd, int nsrc, const int *src_of, double2 *dS,
                             size_t splane, size_t sf, size_t st_) {
   fasst_sf_model *m = c->sf;
@@ -673,8 +821,9 @@ int fasst_sf_renormalize(fasst_ctx *c, int *restart_mask) {
   return FASST_OK;
 }
 
-int fasst_sf_run(fasst_ctx *c, int n_iter, const double *psd, double omega, double *logliks,
-                 int *restart_mask, int *iters_done) {
+// fasst_sf_run (sigma == nullptr) and fasst_sf_run_sparse
+static int sf_run(fasst_ctx *c, int n_iter, const double *psd, double omega, const double *sigma,
+                  double *logliks, int *restart_mask, int *iters_done) {
   int st = need_sf(c, 0);
   if (st) return st;
   if (n_iter < 0 || (n_iter > 0 && (!psd || !logliks))) return FASST_ERR_SHAPE;
@@ -682,6 +831,7 @@ int fasst_sf_run(fasst_ctx *c, int n_iter, const double *psd, double omega, doub
     set_error("fasst_sf_run: no observation resident (upload Cx first)");
     return FASST_ERR_SHAPE;
   }
+  if (sigma && (st = sf_check_sigma(sigma, n_iter))) return st;
   fasst_sf_model *m = c->sf;
   DeviceGuard g(c->device);
   if (iters_done) *iters_done = 0;
@@ -708,6 +858,9 @@ int fasst_sf_run(fasst_ctx *c, int n_iter, const double *psd, double omega, doub
     if ((st = sf_flags_mask(c, &mask))) return st;
     done = it + 1;
     if (mask) break;
+    // (a dead TW is redrawn inside the reference's GEM_iteration, before its
+    // reweigh: that iteration's reweigh is the caller's, after the redraw)
+    if (sigma && (st = sf_reweigh(c, sigma[it]))) return st;
   }
   if (iters_done) *iters_done = done;
   FASST_HIP(hipMemcpy(logliks, m->ll.p, (size_t)done * sizeof(double), hipMemcpyDeviceToHost));
@@ -716,6 +869,47 @@ int fasst_sf_run(fasst_ctx *c, int n_iter, const double *psd, double omega, doub
     return FASST_TW_RESTART;
   }
   return FASST_OK;
+}
+
+int fasst_sf_run(fasst_ctx *c, int n_iter, const double *psd, double omega, double *logliks,
+                 int *restart_mask, int *iters_done) {
+  return sf_run(c, n_iter, psd, omega, nullptr, logliks, restart_mask, iters_done);
+}
+
+int fasst_sf_run_sparse(fasst_ctx *c, int n_iter, const double *psd, double omega, const double *sigma,
+                        double *logliks, int *restart_mask, int *iters_done) {
+  if (n_iter > 0 && !sigma) return FASST_ERR_SHAPE;
+  return sf_run(c, n_iter, psd, omega, n_iter > 0 ? sigma : nullptr, logliks, restart_mask, iters_done);
+}
+
+int fasst_sf_set_sparsity(fasst_ctx *c, const int *length) {
+  int st = need_sf(c, 0);
+  if (st) return st;
+  if (!length) return FASST_ERR_SHAPE;
+  fasst_sf_model *m = c->sf;
+  bool any = false;
+  for (int j = 0; j < m->J; ++j) {
+    if (length[j] < 0) {
+      set_error("fasst_sf_set_sparsity: component %d has length %d < 0", j, length[j]);
+      return FASST_ERR_SHAPE;
+    }
+    any |= length[j] > 0;
+  }
+  DeviceGuard g(c->device);
+  if (any && !m->mu.p) {
+    FASST_HIP(hipStreamSynchronize(c->stream));
+    if ((st = m->mu.alloc(c->T))) return st;
+  }
+  for (int j = 0; j < m->J; ++j) m->sparsity[j] = length[j];
+  return FASST_OK;
+}
+
+int fasst_sf_reweigh(fasst_ctx *c, double sigma) {
+  int st = need_sf(c, 0);
+  if (st) return st;
+  if ((st = sf_check_sigma(&sigma, 1))) return st;
+  DeviceGuard g(c->device);
+  return sf_reweigh(c, sigma);
 }
 
 int fasst_sf_wiener_images(fasst_ctx *c, const double *psd, int nsrc, const int *src_of, double *S) {

@@ -111,8 +111,7 @@ __global__ __launch_bounds__(kPcaChunk) void k_pca2d(const PcaArgs a) {
 }
 
 // -------------------------------------------------------------- medianFilter
-constexpr int kMedChunk = 128;
-constexpr int kMedLdsSpan = 6144;  // doubles (48 KiB): a wider span stays in global memory
+constexpr int kMedChunk = 128;  // (kMedLdsSpan, fasst_device.h: a wider span stays in global memory)
 
 struct MedArgs {
   const double *in;  // [R][N]
@@ -137,33 +136,7 @@ __global__ __launch_bounds__(kMedChunk) void k_median(const MedArgs a) {
   const double *src = kStaged ? sm - s_lo : row;
   const int n = c0 + threadIdx.x;
   if (n >= a.N) return;
-  const double self = row[n];
-  const int lo = max(n - a.length, 0);
-  const int hi = (int)min((long)n + a.length, (long)a.N - 1);
-  const int cnt = hi - lo;
-  double res = self;
-  if (cnt > 0) {
-    bool has_nan = false;
-    for (int i = lo; i < hi; ++i) has_nan |= src[i] != src[i];
-    if (!has_nan) {
-      const int k1 = (cnt - 1) >> 1, k2 = cnt >> 1;
-      double v1 = 0.0, v2 = 0.0;
-      int found = 0;
-      for (int i = lo; i < hi && found < 2; ++i) {
-        const double xi = src[i];
-        int rank = 0;
-        for (int j = lo; j < hi; ++j) {
-          const double xj = src[j];
-          rank += (xj < xi) || (xj == xi && j < i);
-        }
-        if (rank == k1) { v1 = xi; ++found; }
-        if (rank == k2) { v2 = xi; ++found; }
-      }
-      res = k1 == k2 ? v1 : (v1 + v2) / 2.0;
-      if (res != res) res = self;  // +inf and -inf in the middle
-    }
-  }
-  a.out[(size_t)r * a.N + n] = res;
+  a.out[(size_t)r * a.N + n] = median_at(src, row[n], n, a.length, a.N);
 }
 
 // ------------------------------------------------------- f0detectionFunction

@@ -249,8 +249,13 @@ class Engine(object):
         check(lib.fasst_set_factors(self._h, int(j), int(i), dptr(FB), dptr(FW), dptr(TW)),
               "fasst_set_factors")
 
-    def get_factors(self, j, i):
+    def get_factors(self, j, i, tw_only=False):
         kb, kw = self.sf_factors[j][i]
+        if tw_only:
+            TW = np.empty((kw, self.T))
+            check(lib.fasst_get_factors(self._h, int(j), int(i), None, None, dptr(TW)),
+                  "fasst_get_factors")
+            return TW
         FB = np.empty((self.F, kb))
         FW = np.empty((kb, kw))
         TW = np.empty((kw, self.T))
@@ -303,6 +308,41 @@ class Engine(object):
         if st == _lib.FASST_TW_RESTART:
             return ll[:done.value], done.value, mask.value
         check(st, "fasst_run")
+        return ll[:n], n, 0
+
+    # ------------------------------------------------------------ sparsity reweighting
+    def sf_set_sparsity(self, lengths):
+        """Median filter length of each component's barycentre track, 0 for a
+        component that is not reweighed (fasst_sf_set_sparsity)."""
+        n = np.ascontiguousarray(lengths, dtype=np.int32)
+        if n.shape != (len(self.structure[0]),):
+            raise ValueError("one sparsity length per spatial component, got %s" % (n.shape,))
+        check(lib.fasst_sf_set_sparsity(self._h, iptr(n)), "fasst_sf_set_sparsity")
+
+    def sf_reweigh(self, sigma):
+        """reweigh_sparsity_constraint(sigma) on the resident TW (fasst_sf_reweigh)."""
+        check(lib.fasst_sf_reweigh(self._h, float(sigma)), "fasst_sf_reweigh")
+
+    def sf_run_sparse(self, psd_rows, omega, sigmas):
+        """run() with sf_reweigh(sigmas[i]) after every iteration whose flags
+        are clean (fasst_sf_run_sparse): (logliks, done, restart_mask).  After
+        a restart the last iteration done has not been reweighed."""
+        psd_rows = np.ascontiguousarray(psd_rows, dtype=np.float64)
+        sigmas = np.ascontiguousarray(sigmas, dtype=np.float64)
+        n = psd_rows.shape[0]
+        if n and psd_rows.shape[1] != self.F:
+            raise ValueError("psd rows must have F=%d columns" % self.F)
+        if sigmas.shape != (n,):
+            raise ValueError("one sigma per iteration: %s for %d" % (sigmas.shape, n))
+        ll = np.zeros(max(n, 1))
+        mask = ctypes.c_int(0)
+        done = ctypes.c_int(0)
+        st = lib.fasst_sf_run_sparse(self._h, n, dptr(psd_rows) if n else None, float(omega),
+                                     dptr(sigmas) if n else None, dptr(ll), ctypes.byref(mask),
+                                     ctypes.byref(done))
+        if st == _lib.FASST_TW_RESTART:
+            return ll[:done.value], done.value, mask.value
+        check(st, "fasst_sf_run_sparse")
         return ll[:n], n, 0
 
     def set_profiling(self, on=True):

@@ -28,7 +28,10 @@
                     the F0 dictionary of minF0=39 .. maxF0=2000 at
                     stepnoteF0=16 plus one column, 20 filter basis functions
                     with 4 weights) at C3's signal size, on the engine (the
-                    class surface takes Kb <= 128)
+                    class surface takes Kb <= 128); with
+                    --sparsity L also ms per iteration through sf_run_sparse
+                    (both source / filter components reweighed over L frames,
+                    sigma from K^2 to 9) and the device time of its two kernels
   --workload sfnmf  SFNMF_decomp_init (tools/nmf.py:161-360) at F = 2049,
                     N = 10000 on the default F0 dictionary's width K = 1093,
                     Kf = 10, Kr = 2: ms per iteration (sfnmf_run), and the
@@ -648,10 +651,16 @@ def bench_viterbi(steps, warmup, S=1092, N=20000, seed=0):
                              "scaled to N=%d" % (n_cpu, N)}}
 
 
-def bench_sf(steps, warmup, F=2049, T=10000, seed=0):
+COPY_GBS = 6290.0   # the device copy rate profiles/sigtools_bench.jsonl measured
+
+
+def bench_sf(steps, warmup, F=2049, T=10000, seed=0, sparsity=0):
     """The two-factor path (csrc/fasst_sf.hip) at the reference class's default
     shape: ms per GEM iteration (a host sync per iteration: the restart flags),
-    then the launch counts of a profiled iteration."""
+    then the launch counts of a profiled iteration.  sparsity = L > 0: the
+    same through sf_run_sparse with both source / filter components reweighed,
+    in the same session, and the two kernels' device time against TW read
+    twice and written once at the measured copy rate."""
     from pyfasst_amd import synthetic
     from pyfasst_amd.engine import Engine
     nf0 = int(np.ceil(12.0 * 16 * np.log2(2000.0 / 39.0)) + 1) + 1     # + the column of ones
@@ -683,6 +692,30 @@ def bench_sf(steps, warmup, F=2049, T=10000, seed=0):
     kt = eng.kernel_times()
     eng.set_profiling(False)
     gflop = 2.0 * 2 * F * nf0 * T * (3 + 2) / 1e9   # P0 three times, W0^T [rn | rd]: per SF component
+    sparse = None
+    if sparsity > 0:
+        n = max(steps, warmup, 2)
+        sig = np.exp(np.log(float(nf0) ** 2) + (np.log(9.0) - np.log(float(nf0) ** 2)) *
+                     np.arange(n) / (n - 1.0))
+        eng.sf_set_sparsity([sparsity, sparsity, 0])
+        eng.sf_run_sparse(psd[:max(warmup, 1)], 1.0, sig[:max(warmup, 1)])
+        t0 = time.perf_counter()
+        _, done, mask = eng.sf_run_sparse(psd[:steps], 1.0, sig[:steps])
+        dts = (time.perf_counter() - t0) / max(done, 1)
+        eng.set_profiling(True)
+        eng.sf_run_sparse(psd[:1], 1.0, sig[-1:])
+        ks = eng.kernel_times()
+        eng.set_profiling(False)
+        copy_ms = 3.0 * nf0 * T * 8 / (COPY_GBS * 1e9) * 1e3   # per sparse component
+        dev = {k: round(float(ks[k][0]), 4) for k in ("k_sf_bary", "k_sf_sparsify")}
+        sparse = {"length": sparsity, "sparse_components": 2, "iterations": int(done),
+                  "restart_mask": int(mask), "ms_per_iteration": round(dts * 1e3, 3),
+                  "ms_per_iteration_without": round(dt * 1e3, 3),
+                  "kernel_device_ms_per_launch": dev,
+                  "launches_per_iteration": {k: int(ks[k][1]) for k in dev},
+                  "reweigh_device_ms_per_iteration": round(2 * sum(dev.values()), 4),
+                  "copy_rate_ms_per_component": round(copy_ms, 4),
+                  "frac_of_measured_copy_%d" % COPY_GBS: round(copy_ms / sum(dev.values()), 4)}
     return {"metric": "GEM iteration, source / filter model (two-factor path)",
             "value": round(dt * 1e3, 3), "unit": "ms", "higher_is_better": False,
             "steps": steps, "warmup": warmup, "dtype": "f64",
@@ -692,7 +725,8 @@ def bench_sf(steps, warmup, F=2049, T=10000, seed=0):
                                    % (F, T, F, nf0, nf0, F, kf, kf, kw, kw, kres)},
             "source_factor_gflop": round(gflop, 1),
             "source_factor_tflops": round(gflop / 1e3 / dt, 2),
-            "launches_per_iteration": {k: int(v[1]) for k, v in sorted(kt.items())}}
+            "launches_per_iteration": {k: int(v[1]) for k, v in sorted(kt.items())},
+            "sparsity": sparse}
 
 
 def bench_sfnmf(steps, warmup, F=2049, N=10000, K=1093, Kf=10, Kr=2, seed=0):
@@ -1069,6 +1103,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-cpu-baseline", action="store_true",
                     help="skip the CPU baseline (profiling passes)")
+    ap.add_argument("--sparsity", type=int, default=0,
+                    help="sf: median length L of the sparsity reweighting (0: off)")
     a = ap.parse_args()
     global NO_CPU
     NO_CPU = a.no_cpu_baseline
@@ -1079,7 +1115,8 @@ def main():
           "separate_cqt": bench_separate_cqt, "filter": bench_filter,
           "stereo_nmf": bench_stereo_nmf, "demix": bench_demix,
           "wf0_chirped": bench_wf0_chirped}[a.workload]
-    out = fn(a.steps, a.warmup)
+    out = fn(a.steps, a.warmup, sparsity=a.sparsity) if a.workload == "sf" else \
+        fn(a.steps, a.warmup)
     if NO_CPU:
         out["cpu_baseline"] = None   # not measured (the sample above timed nothing)
     print(json.dumps(out), flush=True)
