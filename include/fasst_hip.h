@@ -51,8 +51,10 @@ typedef struct fasst_ctx fasst_ctx;
  * the source / filter IS-NMF (sfnmf_*, fasst_nmf.h).  Revision 8 adds the
  * stereo accompaniment IS-NMF (snmf_*, fasst_simm.h).  Revision 9 adds the
  * GEMM layer's test entry points (fasst_gemm_plan, fasst_gemm_probe,
- * fasst_dgemm2_probe). */
-#define FASST_ABI_VERSION 10
+ * fasst_dgemm2_probe).  Revision 10 adds the sparsity reweighting
+ * (fasst_sf_set_sparsity / fasst_sf_reweigh / fasst_sf_run_sparse).  Revision
+ * 11 adds the spatial package (fasst_spatial.h). */
+#define FASST_ABI_VERSION 11
 int fasst_abi_version(void);
 
 /* The E-step's balanced schedule, host arithmetic only (no device call;

@@ -1,7 +1,7 @@
 """ctypes binding of libfasst_hip.so (declared in include/fasst_hip.h,
 include/fasst_simm.h, include/fasst_nmf.h, include/fasst_cqt.h,
 include/fasst_viterbi.h, include/fasst_dict.h, include/fasst_sigtools.h,
-include/fasst_filter.h and include/fasst_demix.h).
+include/fasst_filter.h, include/fasst_demix.h and include/fasst_spatial.h).
 
 The product path has no CPU fallback: if the HIP library is missing this
 module raises at import time, and every compute call raises if the device
@@ -244,6 +244,17 @@ SIGNATURES = {
     "demix_last_ms": (ctypes.c_int, [_dp]),
     "demix_launch_count": (ctypes.c_int, [_lp]),
     "demix_transfer_count": (ctypes.c_int, [_lp]),
+    # include/fasst_spatial.h, the spatial package
+    "fasst_steer_ula": (ctypes.c_int, [ctypes.c_int] * 4 + [_dp, _dp, ctypes.c_double, _dp]),
+    "fasst_steer_acous": (ctypes.c_int, [ctypes.c_int] * 3 + [_dp, _dp, ctypes.c_double, _dp]),
+    "fasst_cx_tmean": (ctypes.c_int, [_vp, _dp]),
+    "fasst_dir_diag": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_double, _dp, _dp, _dp]),
+    "fasst_ula_response": (ctypes.c_int, [ctypes.c_int] * 4 + [_dp, _dp, _dp, ctypes.c_double,
+                                                               _dp]),
+    "fasst_mvdr_target": (ctypes.c_int, [ctypes.c_int] * 3 + [_dp, _dp, _dp]),
+    "fasst_spatial_launch_count": (ctypes.c_int, [_lp]),
+    "fasst_spatial_last_ms": (ctypes.c_int, [_dp]),
+    "fasst_spatial_transfer_bytes": (ctypes.c_int, [_lp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
@@ -258,8 +269,9 @@ for _name, (_res, _args) in SIGNATURES.items():
 # fasst_sf_* and fasst_set_factors / fasst_get_factors; revision 6:
 # fasst_estep_partition; revision 7: sfnmf_*; revision 8: snmf_*; revision 9:
 # fasst_gemm_plan / fasst_gemm_probe / fasst_dgemm2_probe; revision 10:
-# fasst_sf_set_sparsity / fasst_sf_reweigh / fasst_sf_run_sparse)
-ABI_VERSION = 10
+# fasst_sf_set_sparsity / fasst_sf_reweigh / fasst_sf_run_sparse; revision 11:
+# include/fasst_spatial.h)
+ABI_VERSION = 11
 if lib.fasst_abi_version() != ABI_VERSION:
     raise ImportError("pyfasst_amd: %s has ABI revision %d, this binding expects %d; rebuild it "
                       "(make -C pyfasst_amd/csrc)" % (LIB_PATH, lib.fasst_abi_version(), ABI_VERSION))

@@ -1037,6 +1037,16 @@ class FASST(object):
             return np.fft.irfft(self.Cx[1] / np.abs(self.Cx[1]),
                                 n=self.sig_repr_params['fsize'], axis=0)
 
+    def dir_diag_stereo(self, ntheta=512, distanceInterMic=0.3):
+        """Capon directivity diagram of the model's own observation: what
+        spatial.steering_vectors.dir_diag_stereo(self.Cx, nft=fsize,
+        samplerate=...) returns, from the resident planes (no F x T array
+        crosses to the host).  Not a method of the reference's class."""
+        if self._engine is None:
+            raise AttributeError("no observation: call comp_transf_Cx() first")
+        return self._engine.dir_diag(ntheta, distanceInterMic, self.sig_repr_params['fsize'],
+                                     self._samplerate_or_default())
+
     def mvdr_2d(self, theta, distanceInterMic=.3):
         """The reference's method (audioModel.py:1238-1314) cannot run, so there
         is nothing to reproduce: its steering-vector module uses `np` and

@@ -148,4 +148,7 @@ int configure_model(fasst_ctx *c, int J, const int *rank, const int *K, const in
 int build_inst_A(fasst_ctx *c);
 int launch_w_old(fasst_ctx *c);  // Wkf = FB.FW
 void sf_release(fasst_ctx *c);   // drop the two-factor model (fasst_sf.hip)
+// inv_herm_mat_2d on device arrays (k_inv_herm, fasst_tf.hip)
+int launch_inv_herm(int n, const double *d, const double2 *off, double *id, double2 *ioff,
+                    double *det, hipStream_t stream);
 }  // namespace fasst

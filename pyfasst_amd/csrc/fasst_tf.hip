@@ -475,6 +475,15 @@ __global__ void k_inv_herm(int n, const double *__restrict__ d, const double2 *_
   }
 }
 
+// k_inv_herm on device arrays, enqueued on `stream` (fasst_ctx.h): d and id
+// [2][n], off and ioff [n] complex, det [n]
+int launch_inv_herm(int n, const double *d, const double2 *off, double *id, double2 *ioff,
+                    double *det, hipStream_t stream) {
+  k_inv_herm<<<std::min((n + 255) / 256, 4096), 256, 0, stream>>>(n, d, off, id, ioff, det);
+  FASST_LAUNCH_CHECK();
+  return FASST_OK;
+}
+
 // ---- time-invariant spatial filter (separate_spatial_filter_comp,
 // audioModel.py:891-1061) ---------------------------------------------------
 // R_n of spatial component n at bin f (audioModel.py:974-981): the sums over

@@ -452,6 +452,43 @@ class Engine(object):
         check(lib.fasst_gcc_phat(self._h, int(nfft), dptr(out)), "fasst_gcc_phat")
         return out
 
+    # ------------------------------------------------------------ spatial package
+    def cx_tmean(self):
+        """Time means of Cx[0], Re Cx[1], Im Cx[1] and Cx[2] of the resident
+        observation, [4, F] (fasst_cx_tmean); no plane leaves the device."""
+        out = np.empty((4, self.F))
+        check(lib.fasst_cx_tmean(self._h, dptr(out)), "fasst_cx_tmean")
+        return out
+
+    def dir_diag(self, ntheta, distanceInterMic, nft, samplerate):
+        """Capon directivity diagram of the resident observation
+        (fasst_dir_diag; spatial/steering_vectors.py:120-160): the time mean,
+        its clamped 2 x 2 inverse and the diagram on the device; returns the
+        (ntheta, F) diagram and theta.  A zero determinant raises the
+        reference's ValueError (:132-135)."""
+        from .spatial.steering_vectors import soundCelerity
+        ntheta = int(ntheta)
+        nfreqs = int(nft) // 2 + 1
+        if nfreqs != self.F:
+            raise ValueError("operands could not be broadcast together with shapes (%d,) (%d,)"
+                             % (nfreqs, self.F))
+        if ntheta < 1:
+            raise ValueError("dir_diag: ntheta %d < 1" % ntheta)
+        freqs = np.arange(nfreqs) * 1. / nft * samplerate
+        theta = np.arange(1, ntheta + 1) * np.pi / (ntheta + 1.) - np.pi / 2.
+        # one np.sin per angle, as the reference's loop takes them
+        sin_theta = np.array([np.sin(t) for t in theta], dtype=np.float64)
+        diagram = np.empty((ntheta, self.F))
+        det = np.empty(self.F)
+        check(lib.fasst_dir_diag(self._h, ntheta, dptr(np.ascontiguousarray(freqs)),
+                                 dptr(sin_theta), float(distanceInterMic / soundCelerity),
+                                 dptr(diagram), dptr(det), None), "fasst_dir_diag")
+        if not np.all(det):
+            raise ValueError(
+                "Not possible to compute directivity, singular covariance. " +
+                "\nThe channels are probably either identical or colinear.")
+        return diagram, theta
+
     # ------------------------------------------------------------ step methods
     def source_powers(self, j0, nj, colmasks=None):
         """V [nj, F, T] of spatial components j0 .. j0+nj-1 (fasst_source_powers)."""

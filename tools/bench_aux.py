@@ -57,6 +57,10 @@
                     2048, perF0 1: 1092 columns): device time of the one
                     dict_odgd launch, host-inclusive time, and the restatement
                     on the host (profiles/dict_family_bench.jsonl)
+  --workload dirdiag  dir_diag_stereo (spatial/steering_vectors.py:76-160) at
+                    F = 2049, T = 10000, ntheta = 512: device time per kernel,
+                    the resident and the host-array route
+                    (profiles/dirdiag_bench.jsonl)
   --workload viterbi  melody tracking (_tracking.pyx:11-93) at config 5:
                     S = 1092 F0 states, N = 20000 frames (runViterbi's
                     transitions, stepNotes 16): tracks/s, device time
@@ -1092,12 +1096,71 @@ def bench_filter(steps, warmup, M=2, L=5120000, wlen=4096, hop=512, seed=0):
                                        "istft() per channel on the GPU, best of two"}}
 
 
+def bench_dirdiag(steps, warmup, F=2049, T=10000, ntheta=512, seed=0):
+    """dir_diag_stereo at the headline size: the resident route (the model's
+    planes, nothing but the diagram crosses) against the host-array route
+    (Cx uploaded as an observation first), device time per kernel."""
+    from pyfasst_amd.engine import Engine
+    from pyfasst_amd.spatial import steering_vectors as sv
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import spatial_pkg_ref as S
+    rs = np.random.RandomState(seed)
+    X = rs.randn(2, F, T) + 1j * rs.randn(2, F, T)
+    X[1] += 0.5 * X[0]
+    Cx = np.array([X[0] * np.conjugate(X[0]), X[0] * np.conjugate(X[1]), X[1] * np.conjugate(X[1])])
+    del X
+    kw = dict(nft=2 * (F - 1), ntheta=ntheta, samplerate=44100, distanceInterMic=0.3)
+    eng = Engine(F, T)
+    eng.set_cx(Cx)
+
+    def timed(fn):
+        for _ in range(warmup):
+            fn()
+        wall, ms = [], []
+        for _ in range(steps):
+            t0 = time.perf_counter()
+            fn()
+            wall.append(time.perf_counter() - t0)
+            ms.append(sv.last_ms())
+        return float(np.median(wall)) * 1e3, {k: float(np.median([m[k] for m in ms])) for k in ms[0]}
+
+    res_ms, kern = timed(lambda: eng.dir_diag(ntheta, 0.3, kw['nft'], 44100))
+    host_ms, _ = timed(lambda: sv.dir_diag_stereo(Cx, **kw))
+    d = eng.dir_diag(ntheta, 0.3, kw['nft'], 44100)[0]
+    cpu_s = err = None
+    if not NO_CPU:
+        t1 = time.perf_counter()
+        ref = S.dir_diag_stereo(Cx, **kw)[0]
+        cpu_s = time.perf_counter() - t1
+        err = S.rel_max(d, ref)
+    nbytes = 4 * 8 * F * T
+    gbs = nbytes / (kern['k_cx_tmean'] * 1e-3) / 1e9
+    return {"metric": "dir_diag_stereo resident route, host-inclusive ms", "value": round(res_ms, 3),
+            "unit": "ms", "ms_per_step": round(res_ms, 3), "steps": steps, "warmup": warmup,
+            "dtype": "f64", "data": "synthetic, RandomState(0)",
+            "config": {"workload": "dir_diag_stereo F=%d T=%d ntheta=%d" % (F, T, ntheta)},
+            "device_ms": {"k_cx_tmean": round(kern['k_cx_tmean'], 4),
+                          "k_capon_diagram": round(kern['k_capon_diagram'], 4)},
+            "resident_route_host_inclusive_ms": round(res_ms, 3),
+            "host_array_route_host_inclusive_ms": round(host_ms, 2),
+            "rel_err_vs_restatement": err,
+            "roofline": {"bound": "hbm", "achieved": round(gbs, 1), "peak": COPY_GBS, "unit": "GB/s",
+                         "frac": round(gbs / COPY_GBS, 4), "traffic": int(nbytes),
+                         "scope": "k_cx_tmean (partial and combine launch), device events; the "
+                                  "four planes read once, against the device copy rate of "
+                                  "profiles/sigtools_bench.jsonl"},
+            "cpu_baseline": {"value": round(cpu_s * 1e3, 1) if cpu_s else None, "unit": "ms",
+                             "cores": _blas_threads(), "kind": "port",
+                             "sample": "tests/spatial_pkg_ref.py dir_diag_stereo at the full size, "
+                                       "once"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=("simm", "nmf", "cqt", "viterbi", "wf0", "separate",
                                            "nnls", "spatial", "hmm", "sf", "sfnmf", "sigtools",
                                            "separate_cqt", "filter", "stereo_nmf", "demix",
-                                           "wf0_chirped"),
+                                           "wf0_chirped", "dirdiag"),
                     required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -1114,7 +1177,7 @@ def main():
           "sfnmf": bench_sfnmf, "sigtools": bench_sigtools,
           "separate_cqt": bench_separate_cqt, "filter": bench_filter,
           "stereo_nmf": bench_stereo_nmf, "demix": bench_demix,
-          "wf0_chirped": bench_wf0_chirped}[a.workload]
+          "wf0_chirped": bench_wf0_chirped, "dirdiag": bench_dirdiag}[a.workload]
     out = fn(a.steps, a.warmup, sparsity=a.sparsity) if a.workload == "sf" else \
         fn(a.steps, a.warmup)
     if NO_CPU:
