@@ -18,6 +18,7 @@
 #pragma once
 #include "fasst_common.h"
 #include "fasst_esched.h"
+#include "fasst_twsched.h"
 
 struct fasst_sf_model;   // two-factor spectral components (fasst_sf.h)
 
@@ -91,6 +92,9 @@ struct fasst_ctx {
   int nchunk_e = 1, tpc_e = 1, nchunk_b = 1, tpc_b = 1, nacc = 0;
   fasst::ESched esched = {};   // the E-step's schedule and the layout of epart / llpart
   int nsplit_t = 1, fpc_t = 1;  // TW contraction bin chunks
+  // k_tw_contract_lds's schedule and the layout of its tnum / tden (bal == 0:
+  // the nsplit_t bin chunks, which the multi-block path always uses)
+  fasst::TwSched twsched = {};
   fasst::DBuf<double> epart, llpart, bnum, tnum, tden, psd, ll, hsum, rscal, rpmax, rpe, rtpart;
   fasst::DBuf<double> gden, TWt, pnum, pden;  // FW update (free FW)
   int nchunk_r = 1;

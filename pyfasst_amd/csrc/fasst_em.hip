@@ -2359,6 +2359,7 @@ __global__ __launch_bounds__(256) void k_fw_final(const FWArgs a) {
 struct TArgs {
   const double *TW, *Wkf_old, *Wkf_new, *Wfk_new, *hatW;
   double *tnum, *tden;  // [nsplit][J][Tp][KP]
+  TwSched ts;           // k_tw_contract_lds<BAL>: its schedule and the partials' slots
   int F, T, Fp, Tp, KP, J, nft, ntt, fpc;
   int tw_free[kMaxJ];
   int kb0[kMaxJ], kb1[kMaxJ];  // BLK: the V tiles sum the columns [kb0, kb1) only
@@ -2546,191 +2547,224 @@ typedef __attribute__((address_space(3))) void lds_void_t;
 
 // (the body is a device function: the host pass of a kernel template
 // analyses its body, and the AMDGPU buffer-resource builtins do not exist there)
-template <class CF>
+//
+// BAL (the balanced schedule, fasst_twsched.h): a.ts.nb persistent blocks, each
+// walking its contiguous range of the (source, frame group, bin step) list one
+// segment at a time -- operands, pipeline, stores to the segment's slot -- so
+// every block does the same number of bin steps (+-1) and a unit that one
+// block finishes alone leaves one partial, not one per bin chunk.
+template <class CF, bool BAL>
 __device__ __forceinline__ void tw_contract_lds_body(const TArgs &a);
-template <class CF>
+template <class CF, bool BAL = false>
 __global__ __launch_bounds__(CF::NT) FASST_NO_LDS_PAIRING
 void k_tw_contract_lds(const TArgs a) {
-  tw_contract_lds_body<CF>(a);
+  tw_contract_lds_body<CF, BAL>(a);
 }
-template <class CF>
+template <class CF, bool BAL>
 __device__ __forceinline__ void tw_contract_lds_body(const TArgs &a) {
   HALT_GUARD(a.halt);
-  constexpr int NKC = CF::NKC_, NW = CF::NW_, TPW = CF::TPW_, NS = CF::NS_;
-  constexpr int KP = CF::KP, NKS = 4 * NKC, SS = CF::SS, WPI = CF::WPI, NWO = CF::NWO;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  // (wv through readfirstlane: the compiler then knows it is wave-uniform, so
-  // the piece / tile branches below are scalar, not exec-masked waterfalls)
-  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int fl = lane & 15, tq = lane >> 4;
-  const dim3 bi = xcd_block();   // x: frame-tile group, y: source, z: bin chunk
-  const int j = bi.y;
-  if (!a.tw_free[j]) return;
-  const int tt0 = (bi.x * NW + wv) * TPW;   // this wave's first frame tile
-  const int fb = bi.z * a.fpc, fe = min(fb + a.fpc, a.nft), nst = fe - fb;
-  // TW operands of the V tiles (resident for the whole bin loop)
-  double bt[TPW][NKS];
+  // one segment: source j, frame group grp, the nst bin steps from bin tile
+  // fb, partials to `slot`
+  auto segment = [&](int j, int grp, int fb, int nst, int slot) {
+    constexpr int NKC = CF::NKC_, NW = CF::NW_, TPW = CF::TPW_, NS = CF::NS_;
+    constexpr int KP = CF::KP, NKS = 4 * NKC, SS = CF::SS, WPI = CF::WPI, NWO = CF::NWO;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    // (wv through readfirstlane: the compiler then knows it is wave-uniform, so
+    // the piece / tile branches below are scalar, not exec-masked waterfalls)
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fl = lane & 15, tq = lane >> 4;
+    const int tt0 = (grp * NW + wv) * TPW;   // this wave's first frame tile
+    // TW operands of the V tiles (resident for the whole bin loop)
+    double bt[TPW][NKS];
 #pragma unroll
-  for (int p = 0; p < TPW; ++p) {
-    const bool tin = tt0 + p < a.ntt;
-    const double *tw = a.TW + ((size_t)j * a.KP + tq) * a.Tp + (tt0 + p) * 16 + fl;
+    for (int p = 0; p < TPW; ++p) {
+      const bool tin = tt0 + p < a.ntt;
+      const double *tw = a.TW + ((size_t)j * a.KP + tq) * a.Tp + (tt0 + p) * 16 + fl;
 #pragma unroll
-    for (int s = 0; s < NKS; ++s) bt[p][s] = tin ? tw[(size_t)(4 * s) * a.Tp] : 0.0;
-  }
-  // (retire them before the first DMA: a use of an ordinary load while LDS-DMA
-  // is in flight would drain the DMA ring)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  // buffer resources: W rows of source j, its rho plane
-  const unsigned wbytes = (unsigned)((size_t)KP * a.Fp * sizeof(double));
-  const unsigned pbytes = (unsigned)((size_t)a.Tp * a.Fp * sizeof(double));
-  const __amdgpu_buffer_rsrc_t rWo = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<double *>(a.Wkf_old + (size_t)j * KP * a.Fp), 0, wbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rWn = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<double *>(a.Wkf_new + (size_t)j * KP * a.Fp), 0, wbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rWf = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<double *>(a.Wfk_new + (size_t)j * a.Fp * KP), 0, wbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<double *>(a.hatW + (size_t)j * a.Tp * a.Fp), 0, pbytes, 0x00020000);
-  // per-lane byte offsets of this wave's pieces (loop-invariant; the bin
-  // step's offset rides in the SGPR soffset)
-  constexpr int WPW = CF::WPW;
-  static_assert(WPW <= 8, "W pieces per wave");
-  unsigned wvo[8];
-#pragma unroll
-  for (int r = 0; r < WPW; ++r) {
-    const int p = wv + NW * r;
-    unsigned o = 0;
-    if (p < NWO + KP / 8) {          // Wo / Wn: row 8 p' + lane / 8, granule lane % 8
-      const int pp = p < NWO ? p : p - NWO, k = 8 * pp + (lane >> 3);
-      o = (unsigned)(((size_t)k * a.Fp + 2 * (lane & 7)) * sizeof(double));
-    } else if (p < WPI) {            // Wf: LDS position P -> element P ^ swz
-      const int P = (p - NWO - KP / 8) * 128 + 2 * lane;
-      const int e = P ^ ((((P / KP) >> 2) & 1) << 4);
-      o = (unsigned)(e * sizeof(double));
+      for (int s = 0; s < NKS; ++s) bt[p][s] = tin ? tw[(size_t)(4 * s) * a.Tp] : 0.0;
     }
-    wvo[r] = o;
-  }
-  unsigned rvo[TPW][2];
-#pragma unroll
-  for (int p = 0; p < TPW; ++p) {
-    // frame tiles past the last one re-read the last (never used)
-    const int tt = min(tt0 + p, a.ntt - 1);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int g = 4 * q + (lane >> 4);
-      rvo[p][q] = (unsigned)(((size_t)(tt * 16 + fl) * a.Fp + 2 * g) * sizeof(double));
-    }
-  }
-  auto issue = [&](int c) {   // stage c (bin tile fb + c) into buffer c % NS
-    double *st = smem + (c % NS) * SS;
-    const int f0 = (fb + c) * 16;
+    // (retire them before the first DMA: a use of an ordinary load while LDS-DMA
+    // is in flight would drain the DMA ring)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // buffer resources: W rows of source j, its rho plane
+    const unsigned wbytes = (unsigned)((size_t)KP * a.Fp * sizeof(double));
+    const unsigned pbytes = (unsigned)((size_t)a.Tp * a.Fp * sizeof(double));
+    const __amdgpu_buffer_rsrc_t rWo = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<double *>(a.Wkf_old + (size_t)j * KP * a.Fp), 0, wbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rWn = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<double *>(a.Wkf_new + (size_t)j * KP * a.Fp), 0, wbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rWf = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<double *>(a.Wfk_new + (size_t)j * a.Fp * KP), 0, wbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<double *>(a.hatW + (size_t)j * a.Tp * a.Fp), 0, pbytes, 0x00020000);
+    // per-lane byte offsets of this wave's pieces (loop-invariant; the bin
+    // step's offset rides in the SGPR soffset)
+    constexpr int WPW = CF::WPW;
+    static_assert(WPW <= 8, "W pieces per wave");
+    unsigned wvo[8];
 #pragma unroll
     for (int r = 0; r < WPW; ++r) {
       const int p = wv + NW * r;
-      // (wave-uniform branches: one resource per call, never a runtime
-      // select of a 128-bit resource)
-      lds_void_t *d = (lds_void_t *)(st + 128 * p);
-      if (p < NWO)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rWo, d, 16, wvo[r], f0 * 8, 0, 0);
-      else if (p < NWO + KP / 8)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rWn, d, 16, wvo[r], f0 * 8, 0, 0);
-      else if (p < WPI)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rWf, d, 16, wvo[r], f0 * KP * 8, 0, 0);
+      unsigned o = 0;
+      if (p < NWO + KP / 8) {          // Wo / Wn: row 8 p' + lane / 8, granule lane % 8
+        const int pp = p < NWO ? p : p - NWO, k = 8 * pp + (lane >> 3);
+        o = (unsigned)(((size_t)k * a.Fp + 2 * (lane & 7)) * sizeof(double));
+      } else if (p < WPI) {            // Wf: LDS position P -> element P ^ swz
+        const int P = (p - NWO - KP / 8) * 128 + 2 * lane;
+        const int e = P ^ ((((P / KP) >> 2) & 1) << 4);
+        o = (unsigned)(e * sizeof(double));
+      }
+      wvo[r] = o;
     }
-    double *sr = st + CF::WD + wv * TPW * CF::RD;
+    unsigned rvo[TPW][2];
+#pragma unroll
+    for (int p = 0; p < TPW; ++p) {
+      // frame tiles past the last one re-read the last (never used)
+      const int tt = min(tt0 + p, a.ntt - 1);
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int g = 4 * q + (lane >> 4);
+        rvo[p][q] = (unsigned)(((size_t)(tt * 16 + fl) * a.Fp + 2 * g) * sizeof(double));
+      }
+    }
+    auto issue = [&](int c) {   // stage c (bin tile fb + c) into buffer c % NS
+      double *st = smem + (c % NS) * SS;
+      const int f0 = (fb + c) * 16;
+#pragma unroll
+      for (int r = 0; r < WPW; ++r) {
+        const int p = wv + NW * r;
+        // (wave-uniform branches: one resource per call, never a runtime
+        // select of a 128-bit resource)
+        lds_void_t *d = (lds_void_t *)(st + 128 * p);
+        if (p < NWO)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rWo, d, 16, wvo[r], f0 * 8, 0, 0);
+        else if (p < NWO + KP / 8)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rWn, d, 16, wvo[r], f0 * 8, 0, 0);
+        else if (p < WPI)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rWf, d, 16, wvo[r], f0 * KP * 8, 0, 0);
+      }
+      double *sr = st + CF::WD + wv * TPW * CF::RD;
+#pragma unroll
+      for (int p = 0; p < TPW; ++p)
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rR, (lds_void_t *)(sr + p * CF::RD + 128 * q), 16,
+                                                   rvo[p][q], f0 * 8, 0, 0);
+    };
+    d4 num[TPW][NKC], den[TPW][NKC];
 #pragma unroll
     for (int p = 0; p < TPW; ++p)
 #pragma unroll
-      for (int q = 0; q < 2; ++q)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rR, (lds_void_t *)(sr + p * CF::RD + 128 * q), 16,
-                                                 rvo[p][q], f0 * 8, 0, 0);
-  };
-  d4 num[TPW][NKC], den[TPW][NKC];
+      for (int kc = 0; kc < NKC; ++kc) num[p][kc] = den[p][kc] = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-  for (int p = 0; p < TPW; ++p)
+    for (int c = 0; c < NS - 1; ++c)
+      if (c < nst) issue(c);
+    // lane's LDS read offsets (doubles) inside a stage
+    const int fpl = 4 * (fl & 3) + (fl >> 2);   // V-tile bin row permutation (k_tw_contract)
+    const int ow = tq * 16 + fpl;   // Wo / Wn: row tq + 4 s at + 64 s
+    // Wf element (4 tq + i, 16 kc + fl) sits at (4 tq + i) KP + 16 kc + fl
+    // with bit 4 flipped for odd tq: + 16 where the flipped bit was 0 (even kc,
+    // or even i at KP = 16, where bit 4 is the row's low bit), - 16 otherwise
+    const int s1 = (tq & 1) << 4;
+    const int ofp = CF::WF0 + 4 * tq * KP + fl + s1, ofm = ofp - 2 * s1;
+    const int orr = CF::WD + wv * TPW * CF::RD + (2 * tq * 16 + fl) * 2;   // granules 2 tq, 2 tq + 1
+    for (int c = 0; c < nst; ++c) {
+      // this wave's stage c pieces have landed (younger stages may still fly)
+      const int ahead = min(NS - 2, nst - 1 - c);
+      if (NS >= 3 && ahead >= 1)
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CF::LPC < 63 ? CF::LPC : 63) : "memory");
+      else
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();   // every wave's stage c is in; stage c - 1 is read
+      if (c + NS - 1 < nst) issue(c + NS - 1);
+      const double *st = smem + (c % NS) * SS;
 #pragma unroll
-    for (int kc = 0; kc < NKC; ++kc) num[p][kc] = den[p][kc] = d4{0.0, 0.0, 0.0, 0.0};
+      for (int p = 0; p < TPW; ++p) {
+        if (tt0 + p >= a.ntt) break;  // wave-uniform: no frame tile left
+        typedef double dv2 __attribute__((ext_vector_type(2)));
+        const dv2 h01 = *(const dv2 *)(st + orr + p * CF::RD);
+        const dv2 h23 = *(const dv2 *)(st + orr + p * CF::RD + 32);
+        const double h[4] = {h01.x, h01.y, h23.x, h23.y};
+        // (this kernel is bound by MFMA + VALU issue, which do not overlap on
+        // gfx950: one accumulation chain per V tile, one Newton step on
+        // v_rcp_f64, no padding masks -- a bin past F meets W_new's zero rows
+        // in the contraction, a frame past T lands in num / den columns
+        // k_tw_update never reads, and every padded operand is finite)
+        d4 vo = d4{0.0, 0.0, 0.0, 0.0}, vn = vo;
 #pragma unroll
-  for (int c = 0; c < NS - 1; ++c)
-    if (c < nst) issue(c);
-  // lane's LDS read offsets (doubles) inside a stage
-  const int fpl = 4 * (fl & 3) + (fl >> 2);   // V-tile bin row permutation (k_tw_contract)
-  const int ow = tq * 16 + fpl;   // Wo / Wn: row tq + 4 s at + 64 s
-  // Wf element (4 tq + i, 16 kc + fl) sits at (4 tq + i) KP + 16 kc + fl
-  // with bit 4 flipped for odd tq: + 16 where the flipped bit was 0 (even kc,
-  // or even i at KP = 16, where bit 4 is the row's low bit), - 16 otherwise
-  const int s1 = (tq & 1) << 4;
-  const int ofp = CF::WF0 + 4 * tq * KP + fl + s1, ofm = ofp - 2 * s1;
-  const int orr = CF::WD + wv * TPW * CF::RD + (2 * tq * 16 + fl) * 2;   // granules 2 tq, 2 tq + 1
-  for (int c = 0; c < nst; ++c) {
-    // this wave's stage c pieces have landed (younger stages may still fly)
-    const int ahead = min(NS - 2, nst - 1 - c);
-    if (NS >= 3 && ahead >= 1)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CF::LPC < 63 ? CF::LPC : 63) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();   // every wave's stage c is in; stage c - 1 is read
-    if (c + NS - 1 < nst) issue(c + NS - 1);
-    const double *st = smem + (c % NS) * SS;
+        for (int s = 0; s < NKS; ++s) {
+          vo = mfma4(st[ow + 64 * s], bt[p][s], vo);
+          vn = mfma4(st[CF::WN0 + ow + 64 * s], bt[p][s], vn);
+        }
+        double r3[4], r4[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const double vm = vmax_f64(vn[i], kEps);
+          double rv = __builtin_amdgcn_rcp(vm);
+          rv = fma(fma(-vm, rv, 1.0), rv, rv);
+          const double other = vmax_f64(vo[i], kEps);
+          r4[i] = other * rv;                // other / V_new
+          r3[i] = (h[i] * r4[i]) * r4[i];    // other hat_W / V_new^2, hat_W = rho other
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int kc = 0; kc < NKC; ++kc) {
+            const bool ev = ((KP == 16 ? i : kc) & 1) == 0;
+            const double bw = st[(ev ? ofp : ofm) + i * KP + kc * 16];
+            num[p][kc] = mfma4(r3[i], bw, num[p][kc]);
+            den[p][kc] = mfma4(r4[i], bw, den[p][kc]);
+          }
+      }
+    }
+    const size_t base = ((size_t)slot * a.J + j) * a.Tp;
 #pragma unroll
     for (int p = 0; p < TPW; ++p) {
-      if (tt0 + p >= a.ntt) break;  // wave-uniform: no frame tile left
-      typedef double dv2 __attribute__((ext_vector_type(2)));
-      const dv2 h01 = *(const dv2 *)(st + orr + p * CF::RD);
-      const dv2 h23 = *(const dv2 *)(st + orr + p * CF::RD + 32);
-      const double h[4] = {h01.x, h01.y, h23.x, h23.y};
-      // (this kernel is bound by MFMA + VALU issue, which do not overlap on
-      // gfx950: one accumulation chain per V tile, one Newton step on
-      // v_rcp_f64, no padding masks -- a bin past F meets W_new's zero rows
-      // in the contraction, a frame past T lands in num / den columns
-      // k_tw_update never reads, and every padded operand is finite)
-      d4 vo = d4{0.0, 0.0, 0.0, 0.0}, vn = vo;
+      if (tt0 + p >= a.ntt) break;
 #pragma unroll
-      for (int s = 0; s < NKS; ++s) {
-        vo = mfma4(st[ow + 64 * s], bt[p][s], vo);
-        vn = mfma4(st[CF::WN0 + ow + 64 * s], bt[p][s], vn);
-      }
-      double r3[4], r4[4];
+      for (int kc = 0; kc < NKC; ++kc)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const double vm = vmax_f64(vn[i], kEps);
-        double rv = __builtin_amdgcn_rcp(vm);
-        rv = fma(fma(-vm, rv, 1.0), rv, rv);
-        const double other = vmax_f64(vo[i], kEps);
-        r4[i] = other * rv;                // other / V_new
-        r3[i] = (h[i] * r4[i]) * r4[i];    // other hat_W / V_new^2, hat_W = rho other
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int kc = 0; kc < NKC; ++kc) {
-          const bool ev = ((KP == 16 ? i : kc) & 1) == 0;
-          const double bw = st[(ev ? ofp : ofm) + i * KP + kc * 16];
-          num[p][kc] = mfma4(r3[i], bw, num[p][kc]);
-          den[p][kc] = mfma4(r4[i], bw, den[p][kc]);
+        for (int m = 0; m < 4; ++m) {
+          const size_t o = (base + (tt0 + p) * 16 + tq + 4 * m) * a.KP + kc * 16 + fl;
+          a.tnum[o] = num[p][kc][m];
+          a.tden[o] = den[p][kc][m];
         }
     }
-  }
-  const size_t base = ((size_t)bi.z * a.J + j) * a.Tp;
-#pragma unroll
-  for (int p = 0; p < TPW; ++p) {
-    if (tt0 + p >= a.ntt) break;
-#pragma unroll
-    for (int kc = 0; kc < NKC; ++kc)
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const size_t o = (base + (tt0 + p) * 16 + tq + 4 * m) * a.KP + kc * 16 + fl;
-        a.tnum[o] = num[p][kc][m];
-        a.tden[o] = den[p][kc][m];
-      }
+  };
+  if constexpr (!BAL) {
+    const dim3 bi = xcd_block();   // x: frame-tile group, y: source, z: bin chunk
+    const int j = bi.y;
+    if (!a.tw_free[j]) return;
+    const int fb = bi.z * a.fpc, fe = min(fb + a.fpc, a.nft);
+    segment(j, bi.x, fb, fe - fb, bi.z);
+  } else {
+    // (plain block order: xcd_block()'s placement, consecutive ranges on one
+    // XCD, measured the same)
+    const int b = blockIdx.x;
+    const long long U = tws_steps(a.ts), end = es_lo(b + 1, U, a.ts.nb);
+    for (long long s = es_lo(b, U, a.ts.nb); s < end;) {
+      const TwSeg g = tws_segment(a.ts, b, s, end);
+      s += g.nf;
+      const int j = g.u / a.ts.G;
+      if (!a.tw_free[j]) continue;   // (the whole block: no barrier is skipped by a part of it)
+      segment(j, g.u - j * a.ts.G, g.f0, g.nf, g.slot);
+      // The segment's DMA ring is drained (its last bin step waited on
+      // vmcnt(0) and issued nothing), and its stores and the next segment's
+      // TW loads retire together at that segment's vmcnt(0), before its first
+      // DMA.  What is left: every wave has read the last stage before a DMA
+      // of the next segment lands in the same buffers.
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+    }
   }
 }
 
 struct TUArgs {
   double *TW;
   const double *tnum, *tden;
-  int T, Tp, KP, J, nsplit;
+  TwSched ts;   // layout of tnum / tden (fasst_twsched.h; bal == 0: nslot bin chunks)
+  int T, Tp, KP, J;
   double omega;
   int kb0[kMaxJ], kb1[kMaxJ], tw_free[kMaxJ];  // rows [kb0, kb1) are updated
   // fused tail (scal non-null): the renormalisation's TW column scale w2
@@ -2756,6 +2790,9 @@ __global__ __launch_bounds__(256) void k_tw_update(const TUArgs a) {
   // (prep: the block's final TW rows [KP][64], padding rows / frames 0)
   extern __shared__ __attribute__((aligned(16))) double s_y[];
   const int j = blockIdx.y, t0 = blockIdx.x * 64;
+  // the partials of the block's 64 frames: their unit's own slots, summed in
+  // slot order (a frame group is a whole number of 64-frame blocks)
+  const int nseg = tws_segments(a.ts, j, t0);
   if (a.scal) {
     // y = fl(fl(TW r) w2): the two roundings of k_tw_update then k_renorm_apply
     const bool fr = a.tw_free[j];
@@ -2794,7 +2831,7 @@ __global__ __launch_bounds__(256) void k_tw_update(const TUArgs a) {
           double r = 1.0;
           if (t < a.T) {
             double num = 0.0, den = 0.0;
-            for (int c = 0; c < a.nsplit; ++c) {
+            for (int c = 0; c < nseg; ++c) {
               const size_t o = (((size_t)c * a.J + j) * a.Tp + t) * a.KP + kb + kl;
               num += a.tnum[o];
               den += a.tden[o];
@@ -2899,7 +2936,7 @@ __global__ __launch_bounds__(256) void k_tw_update(const TUArgs a) {
       double r = 1.0;
       if (t < a.T) {
         double num = 0.0, den = 0.0;
-        for (int c = 0; c < a.nsplit; ++c) {
+        for (int c = 0; c < nseg; ++c) {
           const size_t o = (((size_t)c * a.J + j) * a.Tp + t) * a.KP + kb + kl;
           num += a.tnum[o];
           den += a.tden[o];
@@ -3689,10 +3726,12 @@ static int launch_grid(size_t n, int block = 256) {
 // takes by default (fasst_configure)
 constexpr bool kEsBalancedDefault = true;
 constexpr int kEsMinUnits = 10;
+// k_tw_contract_lds's schedule when FASST_TWC_SCHED is unset
+constexpr bool kTwcBalancedDefault = true;
 static int estep_occupancy(const fasst_ctx *c);
 static bool estep_cxi(const fasst_ctx *c);
 static int contract_occupancy(const fasst_ctx *c);
-static int twl_occupancy(const fasst_ctx *c, int *units);
+static int twl_occupancy(const fasst_ctx *c, bool bal, int *units, int *group_tiles);
 // bins per block of the FW update's f-contraction (k_fw_reduce holds three
 // [fpc][KP] tiles in LDS: 96 KB at KP = 128 with 32 bins)
 static int fw_fpc(const fasst_ctx *c) { return c->KP > 64 ? 32 : kFwFpc; }
@@ -3863,19 +3902,40 @@ int configure_model(fasst_ctx *c, int J, const int *rank, const int *K, const in
   // (the bin split also multiplies k_tw_update's reduction: a fixed, small
   // split measured best at C3)
   c->nsplit_t = std::max(1, std::min(4, c->nft / 32));
-  int tw_units = 0;
-  const long cap_t = (long)twl_occupancy(c, &tw_units) * ncu;
+  int tw_units = 0, tw_tiles = 0;
+  const long cap_t = (long)twl_occupancy(c, false, &tw_units, &tw_tiles) * ncu;
   if ((long)tw_units * J * c->nsplit_t < cap_t)
     c->nsplit_t = best_split((long)tw_units * J, cap_t, c->nft / 16);
   if (const char *v = getenv("FASST_NSPLIT_T")) c->nsplit_t = std::max(1, std::min(atoi(v), c->nft));
   c->fpc_t = (c->nft + c->nsplit_t - 1) / c->nsplit_t;
   c->nsplit_t = (c->nft + c->fpc_t - 1) / c->fpc_t;
+  // k_tw_contract_lds's schedule (the single-component path; fasst_twsched.h).
+  // FASST_TWC_SCHED=grid | balanced picks it (read here, once per
+  // configuration), FASST_TWC_NB sets the balanced schedule's block count:
+  // by default one round of resident blocks.
+  c->twsched = TwSched{};
+  c->twsched.nslot = c->nsplit_t;
+  long cap_tb = 0;
+  {
+    // (an explicit FASST_NSPLIT_T asks for the grid)
+    bool bal = kTwcBalancedDefault && !getenv("FASST_NSPLIT_T");
+    if (const char *v = getenv("FASST_TWC_SCHED")) bal = !strcmp(v, "balanced");
+    // (k_tw_update's 64-frame blocks each lie inside one frame group)
+    if (bal && tw_tiles % 4 == 0 && (long long)J * tw_units * c->nft < (1ll << 30)) {
+      cap_tb = (long)twl_occupancy(c, true, &tw_units, &tw_tiles) * ncu;
+      long long nb = cap_tb;
+      if (const char *v = getenv("FASST_TWC_NB")) nb = atoll(v);
+      c->twsched = tws_make(J, tw_units, 16 * tw_tiles, c->nft, nb);
+    }
+  }
   if (getenv("FASST_VERBOSE"))
     fprintf(stderr,
             "fasst: %d CUs; estep %d %s, %d slots (cap %ld blocks); fb %d chunks (cap %ld); tw %d "
-            "splits (cap %ld)\n",
+            "%s, %d slots (cap %ld)\n",
             ncu, c->esched.bal ? c->esched.nb : c->nchunk_e,
-            c->esched.bal ? "balanced blocks" : "chunks", c->esched.nslot, cap_e, c->nchunk_b, cap_b, c->nsplit_t, cap_t);
+            c->esched.bal ? "balanced blocks" : "chunks", c->esched.nslot, cap_e, c->nchunk_b, cap_b,
+            c->twsched.bal ? c->twsched.nb : c->nsplit_t, c->twsched.bal ? "persistent blocks" : "splits",
+            c->twsched.nslot, c->twsched.bal ? cap_tb : cap_t);
   const int NP = J * (J + 1) / 2;
   c->nacc = 4 * NP + 8 * J;
   int st;
@@ -3900,8 +3960,10 @@ int configure_model(fasst_ctx *c, int J, const int *rank, const int *K, const in
   ALLOC(TWt, (size_t)J * Tp * KP);
   ALLOC(pnum, (size_t)((c->F + fw_fpc(c) - 1) / fw_fpc(c)) * J * KP * KP);
   ALLOC(pden, (size_t)((c->F + fw_fpc(c) - 1) / fw_fpc(c)) * J * KP * KP);
-  ALLOC(tnum, (size_t)c->nsplit_t * J * Tp * KP);
-  ALLOC(tden, (size_t)c->nsplit_t * J * Tp * KP);
+  // (the multi-block path keeps the static split whatever the schedule)
+  const int tslots = std::max(c->nsplit_t, c->twsched.nslot);
+  ALLOC(tnum, (size_t)tslots * J * Tp * KP);
+  ALLOC(tden, (size_t)tslots * J * Tp * KP);
   ALLOC(rss, conv ? 0 : (size_t)Fp * R * R);
   ALLOC(rxs, conv ? 0 : (size_t)Fp * 2 * R);
   ALLOC(flags, kNFlags);
@@ -4194,6 +4256,16 @@ static FWArgs fw_args(const fasst_ctx *c, const Step &s, double omega) {
   return a;
 }
 
+// The layout of tnum / tden in the update at hand: k_tw_contract_lds's
+// schedule on the single-component path, the static bin split of
+// k_tw_contract<BLK> on the multi-block one
+static TwSched tw_layout(const fasst_ctx *c) {
+  if (!c->multi) return c->twsched;
+  TwSched s{};
+  s.nslot = c->nsplit_t;
+  return s;
+}
+
 // the caller adds the ratio plane hatW and, for LAM / TBQ, the planes cp / pw / oth
 static TArgs t_args(const fasst_ctx *c, const Step &s, double omega) {
   TArgs a{};
@@ -4213,6 +4285,7 @@ static TArgs t_args(const fasst_ctx *c, const Step &s, double omega) {
   a.nft = c->nft;
   a.ntt = c->ntt;
   a.fpc = c->fpc_t;
+  a.ts = tw_layout(c);
   a.omega = omega;
   for (int j = 0; j < kMaxJ; ++j) {
     a.tw_free[j] = s.tw[j];
@@ -4236,7 +4309,7 @@ static TUArgs tu_args(const fasst_ctx *c, const Step &s, double omega, const TBA
   a.Tp = c->Tp;
   a.KP = c->KP;
   a.J = c->J;
-  a.nsplit = c->nsplit_t;
+  a.ts = tw_layout(c);
   a.omega = omega;
   for (int j = 0; j < kMaxJ; ++j) {
     a.kb0[j] = s.kb0[j];
@@ -4646,7 +4719,10 @@ static void launch_tw_contract_lds(fasst_ctx *c, const TArgs &t) {
   nkc_dispatch(c, [&](auto n) {
     using CF = TwlShape<decltype(n)::value>;
     const int g = (c->ntt + CF::NW_ * CF::TPW_ - 1) / (CF::NW_ * CF::TPW_);
-    k_tw_contract_lds<CF><<<dim3(g, c->J, c->nsplit_t), CF::NT, CF::smem, c->stream>>>(t);
+    if (t.ts.bal)
+      k_tw_contract_lds<CF, true><<<t.ts.nb, CF::NT, CF::smem, c->stream>>>(t);
+    else
+      k_tw_contract_lds<CF><<<dim3(g, c->J, c->nsplit_t), CF::NT, CF::smem, c->stream>>>(t);
   });
   prof_end(c, KTWC);
 }
@@ -4731,17 +4807,17 @@ static int launch_fw_update(fasst_ctx *c, const FWArgs &w, bool blk, bool timed)
   return FASST_OK;
 }
 
-// resident k_tw_contract_lds blocks per CU, and its frame-tile groups (units)
-static int twl_occupancy(const fasst_ctx *c, int *units) {
+// resident k_tw_contract_lds blocks per CU (bal: of its balanced form), its
+// frame-tile groups (units) and the frame tiles of one
+static int twl_occupancy(const fasst_ctx *c, bool bal, int *units, int *group_tiles) {
   int n = 0;
   nkc_dispatch(c, [&](auto k) {
     using CF = TwlShape<decltype(k)::value>;
-    (void)hipFuncSetAttribute((const void *)k_tw_contract_lds<CF>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF::smem);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_tw_contract_lds<CF>, CF::NT,
-                                                     CF::smem) != hipSuccess)
-      n = 1;
-    *units = (c->ntt + CF::NW_ * CF::TPW_ - 1) / (CF::NW_ * CF::TPW_);
+    const void *fn = bal ? (const void *)k_tw_contract_lds<CF, true> : (const void *)k_tw_contract_lds<CF>;
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF::smem);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, CF::NT, CF::smem) != hipSuccess) n = 1;
+    *group_tiles = CF::NW_ * CF::TPW_;
+    *units = (c->ntt + *group_tiles - 1) / *group_tiles;
   });
   return std::max(1, n);
 }
