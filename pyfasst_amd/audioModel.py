@@ -308,7 +308,10 @@ class FASST(object):
                     raise ValueError("spectral component %d factor %d: FB %s, FW %s, TW %s for "
                                      "F=%d, T=%d" % ((k, fi) + tuple(shp) + (
                                          self.nbFreqsSigRepr, self.nbFramesSigRepr)))
-                if min(shp[1]) < 1 or max(shp[1]) > self.SF_MAX_K:
+                if min(shp[1]) >= 1 and shp[1][0] > self.SF_MAX_K and \
+                        getattr(self, 'wideDictionary', False):
+                    self._admit_wide(k, fi, fac, shp[1])
+                elif min(shp[1]) < 1 or max(shp[1]) > self.SF_MAX_K:
                     raise NotImplementedError("spectral component %d factor %d: Kb=%d, Kw=%d "
                                               "outside 1..%d %s" % ((k, fi) + shp[1] + (
                                                   self.SF_MAX_K, what)))
@@ -343,6 +346,38 @@ class FASST(object):
             raise NotImplementedError("total spatial rank %d above %d (the explicit-V E-step) %s"
                                       % (sum(ranks), self.SF_MAX_RANK, what))
         return [owner[j] for j in range(J)], ranks, None, conv
+
+    SF_WIDE_MAX_K = 2048   # Kb of a wide factor (wideDictionary=True)
+
+    def _admit_wide(self, k, fi, fac, shape):
+        """The wide arm of the two-factor path ("Wide fixed
+        dictionaries"): with self.wideDictionary set, a factor with 128 < Kb <=
+        2048 whose FB and FW are fixed, FW square and diagonal, TW free.  FW
+        is the identity where multiChanSourceF0Filter creates it; the
+        renormalisation (the constructor's included) leaves a diagonal matrix
+        in its place (FW *= max(FB), FW /= mean(FW), :2010-2018), so diagonal
+        is what is compared here, on the host.  Anything else raises
+        NotImplementedError, naming the factor and the property."""
+        Kb, Kw = shape
+        where = "spectral component %d factor %d (Kb=%d, Kw=%d)" % (k, fi, Kb, Kw)
+
+        def refuse(prop):
+            raise NotImplementedError("%s: %s; a wide dictionary (Kb > %d) is a fixed FB with a "
+                                      "fixed, square, diagonal FW and a free NMF TW, Kb <= %d"
+                                      % (where, prop, self.SF_MAX_K, self.SF_WIDE_MAX_K))
+        if Kb > self.SF_WIDE_MAX_K:
+            refuse("Kb above %d" % self.SF_WIDE_MAX_K)
+        if fac.get('FB_frdm_prior', 'free') != 'fixed':
+            refuse("FB_frdm_prior=%r" % fac.get('FB_frdm_prior', 'free'))
+        if fac.get('FW_frdm_prior', 'fixed') != 'fixed':
+            refuse("FW_frdm_prior=%r" % fac.get('FW_frdm_prior'))
+        if Kw != Kb:
+            refuse("FW is not square")
+        FW = np.asarray(fac['FW'])
+        if not np.all(np.isfinite(FW)) or np.count_nonzero(FW - np.diag(np.diag(FW))):
+            refuse("FW is not diagonal")
+        if fac.get('TW_frdm_prior', 'free') != 'free':
+            refuse("TW_frdm_prior=%r" % fac.get('TW_frdm_prior'))
 
     def _refuse_sf(self, name):
         if self._is_sf():
@@ -1253,13 +1288,16 @@ class multiChanSourceF0Filter(FASST):
     free), and one residual NMF component.  Runs on the two-factor path
     (fasst_sf.hip); the dictionaries are built on the GPU.
 
-    On the device every factor has Kb, Kw <= 128 (FASST._structure_sf).  The
-    reference's default F0 range and step (minF0=39, maxF0=2000,
-    stepnoteF0=16) give a source dictionary of 1093 columns: the model can be
-    constructed (its initial renormalisation runs on the host), but
-    estim_param_a_post_model() and the separation refuse it by name; choose
-    minF0 / maxF0 / stepnoteF0 so that the dictionary has at most 128
-    columns.  With `sparsity` set (the median filter length of each
+    On the device every factor has Kb, Kw <= 128 (FASST._structure_sf) unless
+    the model is created with wideDictionary=True.  The reference's default
+    F0 range and step (minF0=39, maxF0=2000, stepnoteF0=16) give a source
+    dictionary of 1093 columns: the model can be constructed (its initial
+    renormalisation runs on the host), but by default (wideDictionary=False)
+    estim_param_a_post_model() and the separation still refuse it by name.
+    wideDictionary=True admits the source factor at up to 2048 columns (fixed
+    FB, fixed diagonal FW, free TW: FASST._admit_wide) and runs it on the wide
+    arm of fasst_sf.hip; the sparsity reweighting takes such a
+    model as it is.  With `sparsity` set (the median filter length of each
     component's F0 track) the reference's schedule runs on the device as its
     own loop body, GEM_iteration() then reweigh_sparsity_constraint(sigma)
     (k_sf_bary / k_sf_sparsify), or resident through Engine.sf_run_sparse;
@@ -1271,9 +1309,10 @@ class multiChanSourceF0Filter(FASST):
 
     def __init__(self, audio, nbComps=3, nbNMFResComps=1, nbFilterComps=20, nbFilterWeigs=[4, ],
                  minF0=39, maxF0=2000, minF0search=80, maxF0search=800, stepnoteF0=16,
-                 chirpPerF0=1, spatial_rank=1, sparsity=None, **kwargs):
+                 chirpPerF0=1, spatial_rank=1, sparsity=None, wideDictionary=False, **kwargs):
         from .SeparateLeadStereo import separateLeadFunctions as slf
         super(multiChanSourceF0Filter, self).__init__(audio=audio, **kwargs)
+        self.wideDictionary = bool(wideDictionary)
         self.comp_transf_Cx()
         self.sourceParams = {'minF0': minF0, 'maxF0': maxF0, 'stepnoteF0': stepnoteF0,
                              'chirpPerF0': chirpPerF0, 'minF0search': minF0search,

@@ -139,7 +139,7 @@ struct fasst_ctx {
   // (events on the stream each kernel runs on, the side-stream fork kept, a
   // ring of kProfRing iterations between host syncs: the timed schedule)
   // (slots kSfSlot0 ..: the kernels of fasst_sf.hip, launch counts only)
-  static constexpr int kNK = 28, kSfSlot0 = 17, kProfRing = 32;
+  static constexpr int kNK = 32, kSfSlot0 = 17, kProfRing = 32;
   int prof = 0, pslot = 0;
   hipEvent_t ev0[kNK][kProfRing] = {}, ev1[kNK][kProfRing] = {};
   int used[kNK][kProfRing] = {{0}};

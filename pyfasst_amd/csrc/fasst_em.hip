@@ -3688,7 +3688,8 @@ static const char *kKernelNames[fasst_ctx::kNK] = {
     "k_mix_inst", "k_fb_contract", "k_fb_update", "k_tw_contract", "k_renorm", "k_tw_update",
     "k_fw_update", "k_tw_rowsum", "k_renorm_tail", "k_tw_statediv", "k_tw_decode",
     "k_sf_gemm", "k_sf_prod", "k_sf_ratio", "k_sf_update", "k_sf_renorm", "k_sf_wiener",
-    "k_sf_other", "k_sf_hatw", "k_sf_energy", "k_sf_bary", "k_sf_sparsify"};
+    "k_sf_other", "k_sf_hatw", "k_sf_energy", "k_sf_bary", "k_sf_sparsify",
+    "k_sfw_scale", "k_sfw_dgemm2", "k_sfw_update", "k_sfw_renorm"};
 
 // per-kernel timing: an event pair around the launch on the stream it runs on
 // (s = nullptr: the main stream), slot = the iteration's place in the ring

@@ -10,6 +10,9 @@
 namespace fasst {
 
 constexpr int kSfMaxFac = 2;
+constexpr int kSfWideK = 128;     // Kb above this: a wide candidate
+constexpr int kSfWideRows = 64;   // FB rows per column-max partial
+constexpr int kSfWidePart = 1024; // blocks (= partial sums) of the TW reduction
 
 struct SfFactor {
   int Kb = 0, Kw = 0, fb_free = 0, fw_free = 0, tw_free = 0;
@@ -17,6 +20,13 @@ struct SfFactor {
   // the matrices in use: this factor's own buffers, or those of an earlier
   // factor it shares a matrix with (fasst_sf_configure's alias)
   double *fb = nullptr, *fw = nullptr, *tw = nullptr;
+  // the wide arm (fasst_sf.hip, "wide factors"): cand = Kb > kSfWideK with FB
+  // and FW fixed and FW square (fasst_sf_configure); wide = cand and the FW
+  // last uploaded is diagonal (fasst_set_factors).  A wide factor holds
+  // W = FB.diag(FW) [F][ldw] and its transpose WT [Kb][ldwt], both leading
+  // dimensions even (the 16-byte row loads of k_dgemm2)
+  int cand = 0, wide = 0, ldw = 0, ldwt = 0;
+  DBuf<double> WT;
 };
 
 }  // namespace fasst
@@ -42,6 +52,10 @@ struct fasst_sf_model {
   // component j's barycentre track (0: none) and the track itself, mu [T]
   int sparsity[fasst::kMaxJ] = {0};
   fasst::DBuf<double> mu;
+  // wide factors only: rnd [F][2 T] = [rn | rd], cnd [Kb][2 T] = [num | den],
+  // wcmax [ceil(F / kSfWideRows)][Kb] column-max partials, wm / ww2 [Kb] the
+  // column maxima of FB and the column means of FW, wpart the block sums of TW
+  fasst::DBuf<double> rnd, cnd, wcmax, wm, ww2, wpart;
 };
 
 namespace fasst {

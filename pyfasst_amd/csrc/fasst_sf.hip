@@ -33,7 +33,8 @@
 namespace fasst {
 
 enum { KSF_GEMM = fasst_ctx::kSfSlot0, KSF_PROD, KSF_RATIO, KSF_UPDATE, KSF_RENORM, KSF_WIENER, KSF_OTHER,
-       KSF_HATW, KSF_ENERGY, KSF_BARY, KSF_SPARSIFY };
+       KSF_HATW, KSF_ENERGY, KSF_BARY, KSF_SPARSIFY, KSFW_SCALE, KSFW_DGEMM2, KSFW_UPDATE, KSFW_RENORM };
+static_assert(KSFW_RENORM == fasst_ctx::kNK - 1, "one profiling slot per kernel of this file");
 static inline void sf_count(fasst_ctx *c, int id) {
   if (c->prof) c->prof_cnt[id] += 1;
 }
@@ -169,6 +170,147 @@ __global__ __launch_bounds__(256) void k_sf_renorm(double *__restrict__ FB, doub
   }
   if (dead || last) return;
   for (size_t i = tid; i < n; i += 256) TW[i] /= ge;
+}
+
+// ------------------------------------------------------------ wide factors
+// A factor with Kb > kSfWideK, FB and FW fixed and FW diagonal (the F0 comb
+// dictionary of multiChanSourceF0Filter: FW starts as the identity, and the
+// renormalisation below, like the reference's, turns it into another diagonal
+// matrix at its first pass, so "identity" cannot be what the arm relies on).
+// W = FB.FW is then a column scaling, formed exactly by k_sfw_scale in both
+// layouts k_dgemm2 wants as its k-major operand; P = W.TW and [num | den] =
+// W^T [rn | rd] run on k_dgemm2, which has no split-K: one fixed summation
+// order per output.  The renormalisation is the reference's (:2003-2036) as
+// k_sf_renorm states it, spread over the chip: the launches below in stream
+// order, each leaving the factor alone after a dead predecessor.
+
+// W[f][k] = FB[f][k] FW[k][k] and WT = W^T, through a 32 x 32 LDS tile
+__global__ __launch_bounds__(256) void k_sfw_scale(const double *__restrict__ FB, const double *__restrict__ FW,
+                                                   double *__restrict__ W, double *__restrict__ WT, int F,
+                                                   int Kb, int ldw, int ldwt) {
+  __shared__ double tile[32][33];
+  const int k0 = blockIdx.x * 32, f0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int r = ty; r < 32; r += 8) {
+    const int f = f0 + r, k = k0 + tx;
+    double v = 0.0;
+    if (f < F && k < Kb) {
+      v = FB[(size_t)f * Kb + k] * FW[(size_t)k * Kb + k];
+      W[(size_t)f * ldw + k] = v;
+    }
+    tile[r][tx] = v;
+  }
+  __syncthreads();
+  for (int r = ty; r < 32; r += 8) {
+    const int k = k0 + r, f = f0 + tx;
+    if (k < Kb && f < F) WT[(size_t)k * ldwt + f] = tile[tx][r];
+  }
+}
+
+// k_sf_ratio writing rnd [F][2 T] = [rn | rd], the B operand of one product
+__global__ void k_sfw_ratio(const double *__restrict__ Ps, const double *__restrict__ Po,
+                            const double *__restrict__ other, const double *__restrict__ hatW,
+                            double *__restrict__ rnd, int T, size_t n) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const double v = fmax(Po ? Ps[i] * Po[i] : Ps[i], kEps), o = other[i];
+    const size_t q = i + (i / T) * (size_t)T;
+    rnd[q + T] = o * (1.0 / v);
+    rnd[q] = hatW[i] / (v * v) * o;
+  }
+}
+
+// TW[k][t] *= (num / max(den, eps))^omega from cnd [Kb][2 T] = [num | den]
+__global__ void k_sfw_update(double *__restrict__ TW, const double *__restrict__ cnd, int T, size_t n,
+                             double omega) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t q = i + (i / T) * (size_t)T;
+    const double g = cnd[q] / fmax(cnd[q + T], kEps);
+    TW[i] *= omega == 1.0 ? g : pow(g, omega);
+  }
+}
+
+struct SfwRenArgs {
+  double *FB, *FW, *TW;
+  int F, Kb, T, last;
+  const double *energy;
+  double *cmax, *m, *w2, *part;   // [G][Kb], [Kb], [Kb], [gridDim of k_sfw_twscale]
+  int *flag;
+  const int *prev_flag;
+  double *ge_out;
+};
+
+// block (x, y): the maximum of FB energy over rows [kSfWideRows y, + kSfWideRows)
+// of columns 256 x + tid (a maximum does not depend on its order)
+__global__ __launch_bounds__(256) void k_sfw_colmax(const SfwRenArgs a) {
+  if (a.prev_flag && *a.prev_flag) return;
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= a.Kb) return;
+  const double e = *a.energy;
+  const int f1 = min(a.F, ((int)blockIdx.y + 1) * kSfWideRows);
+  double m = -INFINITY;
+  for (int f = blockIdx.y * kSfWideRows; f < f1; ++f) m = fmax(m, a.FB[(size_t)f * a.Kb + k] * e);
+  a.cmax[(size_t)blockIdx.y * a.Kb + k] = m;
+}
+
+// column k: m = max of its G partials (0 -> 1); FW[k][k] *= m; the mean of a
+// column of a diagonal FW is FW[k][k] / Kb = w2 (0 -> 1); FW[k][k] /= w2
+__global__ __launch_bounds__(256) void k_sfw_colfin(const SfwRenArgs a, int G) {
+  if (a.prev_flag && *a.prev_flag) return;
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= a.Kb) return;
+  double m = -INFINITY;
+  for (int g = 0; g < G; ++g) m = fmax(m, a.cmax[(size_t)g * a.Kb + k]);
+  if (m == 0.0) m = 1.0;
+  a.m[k] = m;
+  const double d = a.FW[(size_t)k * a.Kb + k] * m;
+  double w2 = d / (double)a.Kb;
+  if (w2 == 0.0) w2 = 1.0;
+  a.FW[(size_t)k * a.Kb + k] = d / w2;
+  a.w2[k] = w2;
+}
+
+// FB[f][k] = FB[f][k] energy / m[k]
+__global__ void k_sfw_fbapply(const SfwRenArgs a) {
+  if (a.prev_flag && *a.prev_flag) return;
+  const double e = *a.energy;
+  const size_t n = (size_t)a.F * a.Kb;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    a.FB[i] = a.FB[i] * e / a.m[i % a.Kb];
+}
+
+// TW[k][t] *= w2[k]; part[block] = this block's sum of the scaled TW (a
+// thread's elements in ascending order, then the tree of block_sum)
+__global__ __launch_bounds__(256) void k_sfw_twscale(const SfwRenArgs a) {
+  __shared__ double s_red[256];
+  if (a.prev_flag && *a.prev_flag) return;
+  const size_t n = (size_t)a.Kb * a.T;
+  double s = 0.0;
+  for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const double v = a.TW[i] * a.w2[i / a.T];
+    a.TW[i] = v;
+    s += v;
+  }
+  const double tot = block_sum(s, s_red);
+  if (threadIdx.x == 0) a.part[blockIdx.x] = tot;
+}
+
+// one thread: the partials in index order -> the restart flag and mean(TW)
+__global__ void k_sfw_twfin(const SfwRenArgs a, int nb) {
+  if (a.prev_flag && *a.prev_flag) return;
+  if (blockIdx.x || threadIdx.x) return;
+  double tot = 0.0;
+  for (int b = 0; b < nb; ++b) tot += a.part[b];
+  *a.flag = tot < kEps ? 1 : 0;
+  *a.ge_out = tot / (double)((size_t)a.Kb * a.T);
+}
+
+// TW /= mean(TW), unless it is dead or the component's last factor
+__global__ void k_sfw_twdiv(const SfwRenArgs a) {
+  if ((a.prev_flag && *a.prev_flag) || *a.flag) return;
+  const double ge = *a.ge_out;
+  const size_t n = (size_t)a.Kb * a.T;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    a.TW[i] /= ge;
 }
 
 // reweigh_sparsity_constraint (audioModel.py:2981-3014) on one TW [K][T], K > 2,
@@ -359,6 +501,16 @@ static int sf_mm(fasst_ctx *c, const double *A, const double *B, double *C, int 
 static int sf_power(fasst_ctx *c, int j, int i, bool w = true) {
   SfFactor &x = c->sf->fac[j][i];
   int st;
+  if (x.wide) {   // the column scaling, then P = WT^T TW on k_dgemm2
+    if (w) {
+      sf_count(c, KSFW_SCALE);
+      k_sfw_scale<<<dim3((x.Kb + 31) / 32, (c->F + 31) / 32), 256, 0, c->stream>>>(x.fb, x.fw, x.W.p, x.WT.p, c->F,
+                                                                                 x.Kb, x.ldw, x.ldwt);
+      FASST_LAUNCH_CHECK();
+    }
+    sf_count(c, KSFW_DGEMM2);
+    return dgemm2(c->stream, c->F, c->T, x.Kb, x.WT.p, x.ldwt, x.tw, c->T, x.P.p, c->T);
+  }
   if (w && (st = sf_mm(c, x.fb, x.fw, x.W.p, c->F, x.Kw, x.Kb))) return st;
   return sf_mm(c, x.W.p, x.tw, x.P.p, c->F, c->T, x.Kw);
 }
@@ -446,7 +598,19 @@ static int sf_spectral_update(fasst_ctx *c, int j, double omega) {
       if ((st = sf_apply(c, x.fw, Kb, Kw, m->cn.p, m->cd.p, 1, omega))) return st;
       if ((more || x.tw_free) && (st = sf_power(c, j, i))) return st;
     }
-    if (x.tw_free) {
+    if (x.tw_free && x.wide) {
+      // [num | den] [Kb][2 T] = W^T [rn | rd]: one product, W read once
+      sf_count(c, KSF_RATIO);
+      k_sfw_ratio<<<sf_grid(FT), 256, 0, c->stream>>>(x.P.p, m->nfac[j] > 1 ? m->fac[j][1 - i].P.p : nullptr,
+                                                      m->other.p, m->hatW.p + (size_t)j * FT, m->rnd.p, T, FT);
+      FASST_LAUNCH_CHECK();
+      sf_count(c, KSFW_DGEMM2);
+      if ((st = dgemm2(c->stream, Kb, 2 * T, F, x.W.p, x.ldw, m->rnd.p, 2 * T, m->cnd.p, 2 * T))) return st;
+      sf_count(c, KSFW_UPDATE);
+      k_sfw_update<<<sf_grid((size_t)Kb * T), 256, 0, c->stream>>>(x.tw, m->cnd.p, T, (size_t)Kb * T, omega);
+      FASST_LAUNCH_CHECK();
+      if (more && (st = sf_power(c, j, i, false))) return st;
+    } else if (x.tw_free) {
       if ((st = sf_ratio(c, j, i))) return st;
       // num [Kw][T] = W^T rn, den = W^T rd
       double *Cs[2] = {m->cn.p, m->cd.p};
@@ -467,8 +631,46 @@ static int sf_renormalize(fasst_ctx *c) {
   for (int j = 0; j < m->J; ++j)
     for (int i = 0; i < m->nfac[j]; ++i) {
       SfFactor &x = m->fac[j][i];
-      sf_count(c, KSF_RENORM);
       int *flag = m->flags.p + 1 + 2 * j + i;
+      if (x.wide) {
+        SfwRenArgs a;
+        a.FB = x.fb;
+        a.FW = x.fw;
+        a.TW = x.tw;
+        a.F = c->F;
+        a.Kb = x.Kb;
+        a.T = c->T;
+        a.last = i == m->nfac[j] - 1;
+        a.energy = m->energy.p + (i ? kMaxJ + j : j);
+        a.cmax = m->wcmax.p;
+        a.m = m->wm.p;
+        a.w2 = m->ww2.p;
+        a.part = m->wpart.p;
+        a.flag = flag;
+        a.prev_flag = i ? flag - 1 : nullptr;
+        a.ge_out = m->energy.p + kMaxJ + j;
+        const int G = (c->F + kSfWideRows - 1) / kSfWideRows, kg = (x.Kb + 255) / 256;
+        const size_t n = (size_t)x.Kb * c->T;
+        const int nb = (int)std::min<size_t>((n + 255) / 256, kSfWidePart);
+        k_sfw_colmax<<<dim3(kg, G), 256, 0, c->stream>>>(a);
+        FASST_LAUNCH_CHECK();
+        k_sfw_colfin<<<kg, 256, 0, c->stream>>>(a, G);
+        FASST_LAUNCH_CHECK();
+        k_sfw_fbapply<<<sf_grid((size_t)c->F * x.Kb), 256, 0, c->stream>>>(a);
+        FASST_LAUNCH_CHECK();
+        k_sfw_twscale<<<nb, 256, 0, c->stream>>>(a);
+        FASST_LAUNCH_CHECK();
+        k_sfw_twfin<<<1, 64, 0, c->stream>>>(a, nb);
+        FASST_LAUNCH_CHECK();
+        if (c->prof) c->prof_cnt[KSFW_RENORM] += 5;
+        if (!a.last) {
+          sf_count(c, KSFW_RENORM);
+          k_sfw_twdiv<<<sf_grid(n), 256, 0, c->stream>>>(a);
+          FASST_LAUNCH_CHECK();
+        }
+        continue;
+      }
+      sf_count(c, KSF_RENORM);
       k_sf_renorm<<<1, 256, 0, c->stream>>>(x.fb, x.fw, x.tw, c->F, x.Kb, x.Kw, c->T,
                                             m->energy.p + (i ? kMaxJ + j : j), i == m->nfac[j] - 1,
                                             m->scal.p, flag, i ? flag - 1 : nullptr, m->energy.p + kMaxJ + j);
@@ -659,7 +861,7 @@ int fasst_sf_configure(fasst_ctx *c, int J, const int *rank, const int *mix_conv
   m->R = R;
   const int F = c->F, T = c->T;
   const size_t FT = (size_t)F * T;
-  size_t ncd = 1, nx = 1, nfwh = 1, nwork = 1, nscal = 1;
+  size_t ncd = 1, nx = 1, nfwh = 1, nwork = 1, nscal = 1, nwide = 0;
   int kind[kStepMaxR];
   for (int j = 0; j < J; ++j) {
     m->rank[j] = rank[j];
@@ -701,10 +903,15 @@ int fasst_sf_configure(fasst_ctx *c, int J, const int *rank, const int *mix_conv
         st = FASST_ERR_SHAPE;
         break;
       }
+      // a wide candidate: whether it is wide is known once its FW is uploaded
+      x.cand = kb > kSfWideK && kw == kb && !x.fb_free && !x.fw_free;
+      x.ldw = kw + (x.cand ? kw & 1 : 0);
+      x.ldwt = F + (F & 1);
       if ((!o[0] && (st = x.FB.alloc((size_t)F * kb))) || (!o[1] && (st = x.FW.alloc((size_t)kb * kw))) ||
-          (!o[2] && (st = x.TW.alloc((size_t)kw * T))) || (st = x.W.alloc((size_t)F * kw)) ||
-          (st = x.P.alloc(FT)))
+          (!o[2] && (st = x.TW.alloc((size_t)kw * T))) || (st = x.W.alloc((size_t)F * x.ldw)) ||
+          (x.cand && (st = x.WT.alloc((size_t)kb * x.ldwt))) || (st = x.P.alloc(FT)))
         break;
+      if (x.cand) nwide = std::max(nwide, (size_t)kb);
       x.fb = o[0] ? o[0]->fb : x.FB.p;
       x.fw = o[1] ? o[1]->fw : x.FW.p;
       x.tw = o[2] ? o[2]->tw : x.TW.p;
@@ -728,6 +935,11 @@ int fasst_sf_configure(fasst_ctx *c, int J, const int *rank, const int *mix_conv
         (st = m->flags.alloc(1 + 2 * kMaxJ)) || (st = m->cn.alloc(ncd)) || (st = m->cd.alloc(ncd)) ||
         (st = m->xn.alloc(nx)) || (st = m->xd.alloc(nx)) || (st = m->fwh.alloc(nfwh)) ||
         (st = m->work.alloc(nwork));
+  }
+  if (!st && nwide) {
+    (st = m->rnd.alloc(2 * FT)) || (st = m->cnd.alloc(nwide * 2 * T)) ||
+        (st = m->wcmax.alloc((size_t)((F + kSfWideRows - 1) / kSfWideRows) * nwide)) ||
+        (st = m->wm.alloc(nwide)) || (st = m->ww2.alloc(nwide)) || (st = m->wpart.alloc(kSfWidePart));
   }
   if (st) {
     sf_release(c);
@@ -794,6 +1006,22 @@ int fasst_set_factors(fasst_ctx *c, int j, int i, const double *FB, const double
   FASST_HIP(hipMemcpy(x.fb, FB, (size_t)c->F * x.Kb * sizeof(double), hipMemcpyHostToDevice));
   FASST_HIP(hipMemcpy(x.fw, FW, (size_t)x.Kb * x.Kw * sizeof(double), hipMemcpyHostToDevice));
   FASST_HIP(hipMemcpy(x.tw, TW, (size_t)x.Kw * c->T * sizeof(double), hipMemcpyHostToDevice));
+  if (x.cand) {   // wide: every entry finite and nothing off the diagonal
+    bool diag = true;
+    for (int b = 0; b < x.Kb && diag; ++b)
+      for (int k = 0; k < x.Kw; ++k) {
+        const double v = FW[(size_t)b * x.Kw + k];
+        if (!std::isfinite(v) || (b != k && v != 0.0)) {
+          diag = false;
+          break;
+        }
+      }
+    // (every candidate reading this FW buffer: the upload replaced theirs too)
+    fasst_sf_model *m = c->sf;
+    for (int oj = 0; oj < m->J; ++oj)
+      for (int oi = 0; oi < m->nfac[oj]; ++oi)
+        if (m->fac[oj][oi].cand && m->fac[oj][oi].fw == x.fw) m->fac[oj][oi].wide = diag ? 1 : 0;
+  }
   return FASST_OK;
 }
 
