@@ -1,7 +1,8 @@
 """ctypes binding of libfasst_hip.so (declared in include/fasst_hip.h,
 include/fasst_simm.h, include/fasst_nmf.h, include/fasst_cqt.h,
 include/fasst_viterbi.h, include/fasst_dict.h, include/fasst_sigtools.h,
-include/fasst_filter.h, include/fasst_demix.h and include/fasst_spatial.h).
+include/fasst_filter.h, include/fasst_demix.h, include/fasst_spatial.h and
+include/fasst_nsgt.h).
 
 The product path has no CPU fallback: if the HIP library is missing this
 module raises at import time, and every compute call raises if the device
@@ -255,6 +256,18 @@ SIGNATURES = {
     "fasst_spatial_launch_count": (ctypes.c_int, [_lp]),
     "fasst_spatial_last_ms": (ctypes.c_int, [_dp]),
     "fasst_spatial_transfer_bytes": (ctypes.c_int, [_lp]),
+    # include/fasst_nsgt.h, the non-stationary Gabor transform and its FFT
+    "fasst_nsgt_plan_create": (ctypes.c_int, [ctypes.c_int] * 4 + [_ip, _ip, _ip, _dp, _dp,
+                                                                   ctypes.c_int, ctypes.c_int,
+                                                                   ctypes.POINTER(_vp)]),
+    "fasst_nsgt_plan_destroy": (ctypes.c_int, [_vp]),
+    "fasst_nsgt_coef_len": (ctypes.c_int, [_vp, _lp]),
+    "fasst_nsgt_forward": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_int, _dp]),
+    "fasst_nsgt_backward": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_int, _dp]),
+    "fasst_nsgt_fft": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp]),
+    "fasst_nsgt_launch_count": (ctypes.c_int, [_lp]),
+    "fasst_nsgt_set_timing": (ctypes.c_int, [ctypes.c_int]),
+    "fasst_nsgt_last_ms": (ctypes.c_int, [_dp, _dp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

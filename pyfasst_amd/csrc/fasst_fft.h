@@ -26,6 +26,28 @@ __device__ inline void lds_fft(double2 *x, const double2 *__restrict__ tw, int N
   }
 }
 
+// `count` independent FFTs of size N laid end to end in LDS (x[c * N + i]), the
+// butterflies of all of them spread over the block; count == 1 is lds_fft.
+__device__ inline void lds_fft_batch(double2 *x, const double2 *__restrict__ tw, int N, int logN,
+                                     int count) {
+  const int half = N >> 1, total = half * count;
+  for (int s = 0; s < logN; ++s) {
+    const int m = 1 << s;
+    const int stride = N >> (s + 1);
+    for (int b = threadIdx.x; b < total; b += blockDim.x) {
+      const int which = b >> (logN - 1), bb = b & (half - 1);
+      const int grp = bb >> s, pos = bb & (m - 1);
+      const int i0 = which * N + grp * 2 * m + pos, i1 = i0 + m;
+      const double2 w = tw[pos * stride];
+      const double2 u = x[i0], v = x[i1];
+      const double2 t = make_double2(w.x * v.x - w.y * v.y, w.x * v.y + w.y * v.x);
+      x[i0] = make_double2(u.x + t.x, u.y + t.y);
+      x[i1] = make_double2(u.x - t.x, u.y - t.y);
+    }
+    __syncthreads();
+  }
+}
+
 __device__ __forceinline__ int bitrev(int i, int logN) { return (int)(__brev((unsigned)i) >> (32 - logN)); }
 
 // twiddles exp(sign 2 pi i k / N), k < N/2, computed on the host in long double

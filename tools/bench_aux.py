@@ -61,6 +61,9 @@
                     F = 2049, T = 10000, ntheta = 512: device time per kernel,
                     the resident and the host-array route
                     (profiles/dirdiag_bench.jsonl)
+  --workload nsgt   CQ_NSGT (tftransforms/nsgt) of 100 s at 44.1 kHz, 48 bins per
+                    octave: forward / backward device ms, the whole-signal FFT's
+                    share of the HBM copy rate, against the NumPy restatement.
   --workload viterbi  melody tracking (_tracking.pyx:11-93) at config 5:
                     S = 1092 F0 states, N = 20000 frames (runViterbi's
                     transitions, stepNotes 16): tracks/s, device time
@@ -1155,12 +1158,101 @@ def bench_dirdiag(steps, warmup, F=2049, T=10000, ntheta=512, seed=0):
                                        "once"}}
 
 
+def bench_nsgt(steps, warmup, fs=44100, Ls=4410000, bins=48, fmin=27.5, fmax=18000, seed=0):
+    """CQ_NSGT of 100 s of audio, one and two channels: device time of forward
+    and backward (plan resident; events around the kernels), host-inclusive
+    time from NumPy arrays, and the NumPy restatement on this box's cores; the
+    runs of the two channel counts alternate."""
+    import warnings
+    from pyfasst_amd.tftransforms.nsgt import CQ_NSGT, _device
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import nsgt_ref as NR
+    rs = np.random.RandomState(seed)
+    x2 = rs.randn(2, Ls)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        t0 = time.perf_counter()
+        tr = {1: CQ_NSGT(fmin, fmax, bins, fs, Ls, real=True),
+              2: CQ_NSGT(fmin, fmax, bins, fs, Ls, real=True, multichannel=True)}
+        plan_host_s = (time.perf_counter() - t0) / 2
+    sig = {1: x2[0], 2: x2}
+    _device.set_timing(True)
+    t0 = time.perf_counter()
+    coef = {n: tr[n].forward(sig[n]) for n in (1, 2)}    # builds the device plans
+    plan_dev_s = (time.perf_counter() - t0) / 2
+    acc = {(n, d): {"dev": [], "fft": [], "wall": []} for n in (1, 2) for d in "fb"}
+    for it in range(warmup + steps):
+        for n in (1, 2):
+            for d in "fb":
+                t0 = time.perf_counter()
+                if d == "f":
+                    tr[n].forward(sig[n])
+                else:
+                    y = tr[n].backward(coef[n])
+                wall = time.perf_counter() - t0
+                if it >= warmup:
+                    a = acc[(n, d)]
+                    tot, part = _device.last_ms()
+                    a["dev"].append(tot)
+                    a["fft"].append(part)
+                    a["wall"].append(wall * 1e3)
+    err = float(np.max(np.abs(np.asarray(y) - x2)) / np.max(np.abs(x2)))
+    p = tr[1].plan
+    sh = 1 << int(np.ceil(np.log2(2 * Ls - 1)))
+    # the convolution's 2 FFTs of P points (the chirp's spectrum, the third, is
+    # tabulated in the plan), 2 passes each, read + write, 16 B
+    fft_bytes = 2 * 2 * 2 * 16 * sh
+    cases = []
+    for n in (1, 2):
+        for d, nm in (("f", "forward"), ("b", "backward")):
+            a = acc[(n, d)]
+            dev, fft = float(np.median(a["dev"])), float(np.median(a["fft"]))
+            gbs = n * fft_bytes / (fft * 1e-3) / 1e9
+            cases.append({"case": "%s, %d channel%s" % (nm, n, "s" if n > 1 else ""),
+                          "device_ms": round(dev, 3), "signal_fft_ms": round(fft, 3),
+                          "band_stage_ms": round(dev - fft, 3),
+                          "host_inclusive_ms": round(float(np.median(a["wall"])), 1),
+                          "signal_fft_gb_per_s": round(gbs, 1),
+                          "signal_fft_frac_of_copy": round(gbs / COPY_GBS, 4)})
+    cpu = None
+    if not NO_CPU:
+        f, q = NR.oct_scale(fmin, fmax, bins)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            rp = NR.Plan(f, q, fs, Ls)
+        t0 = time.perf_counter()
+        rc = rp.forward(x2[0])
+        cf = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        rp.backward(rc)
+        cb = time.perf_counter() - t0
+        cpu = {"forward_ms": round(cf * 1e3, 1), "backward_ms": round(cb * 1e3, 1)}
+    return {"metric": "CQ_NSGT forward device ms, 1 channel", "value": cases[0]["device_ms"],
+            "unit": "ms", "ms_per_step": cases[0]["device_ms"], "steps": steps, "warmup": warmup,
+            "dtype": "f64", "data": "synthetic, RandomState(0)",
+            "config": {"workload": "CQ_NSGT fmin=%g fmax=%g bins=%d fs=%d Ls=%d real" % (
+                fmin, fmax, bins, fs, Ls), "bands": len(tr[1].g), "coef_len": int(p.coef_len),
+                "bluestein_P": sh},
+            "cases": cases, "round_trip_rel_err": err,
+            "plan_host_s": round(plan_host_s, 2), "plan_device_s": round(plan_dev_s, 2),
+            "roofline": {"bound": "hbm", "achieved": cases[0]["signal_fft_gb_per_s"],
+                         "peak": COPY_GBS, "unit": "GB/s",
+                         "frac": cases[0]["signal_fft_frac_of_copy"], "traffic": int(fft_bytes),
+                         "scope": "the Ls-point Bluestein FFT: 2 FFTs of P points per call (the "
+                                  "third, of the chirp, is tabulated) x 2 passes x (read + "
+                                  "write) x 16 B, device events"},
+            "cpu_baseline": {"value": cpu["forward_ms"] if cpu else None, "unit": "ms",
+                             "cores": _blas_threads(), "kind": "port", "detail": cpu,
+                             "sample": "tests/nsgt_ref.py forward / backward of one channel "
+                                       "(numpy.fft), once, planning excluded"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=("simm", "nmf", "cqt", "viterbi", "wf0", "separate",
                                            "nnls", "spatial", "hmm", "sf", "sfnmf", "sigtools",
                                            "separate_cqt", "filter", "stereo_nmf", "demix",
-                                           "wf0_chirped", "dirdiag"),
+                                           "wf0_chirped", "dirdiag", "nsgt"),
                     required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -1177,7 +1269,8 @@ def main():
           "sfnmf": bench_sfnmf, "sigtools": bench_sigtools,
           "separate_cqt": bench_separate_cqt, "filter": bench_filter,
           "stereo_nmf": bench_stereo_nmf, "demix": bench_demix,
-          "wf0_chirped": bench_wf0_chirped, "dirdiag": bench_dirdiag}[a.workload]
+          "wf0_chirped": bench_wf0_chirped, "dirdiag": bench_dirdiag,
+          "nsgt": bench_nsgt}[a.workload]
     out = fn(a.steps, a.warmup, sparsity=a.sparsity) if a.workload == "sf" else \
         fn(a.steps, a.warmup)
     if NO_CPU:
