@@ -49,10 +49,11 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 void set_error(const char *fmt, ...);
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-// blocks of 256 threads for a grid-stride loop over n elements
-inline int egrid(size_t n) {
+// blocks of 256 threads for a grid-stride loop over n elements, at most `cap`
+// (kernels that fix their summation order by grid keep the cap they had)
+inline int egrid(size_t n, size_t cap = 8192) {
   const size_t b = (n + 255) / 256;
-  return (int)(b < 8192 ? b : 8192);
+  return (int)(b < cap ? b : cap);
 }
 
 #define FASST_HIP(call)                                                      \
@@ -119,11 +120,58 @@ inline int elapsed_ms(hipEvent_t start, hipEvent_t end, hipStream_t stream, floa
   return FASST_OK;
 }
 
-// Device buffer owned by a context; freed in the destructor.
+// Return a callee's non-zero status from the calling function.
+#define FASST_TRY(expr)                                                      \
+  do {                                                                       \
+    int st_ = (expr);                                                        \
+    if (st_) return st_;                                                     \
+  } while (0)
+
+// Device buffer owned by a context or a call's scope; freed in the destructor.
+// The one host transfer path: put / get / upload count elements of T, check
+// the count against the allocation (FASST_ERR_SHAPE, nothing copied) and do
+// nothing for a count of 0.  Without a stream the copy blocks (hipMemcpy);
+// with one it is queued on it (hipMemcpyAsync).  The host pointer is untyped
+// because the C ABI passes double2 arrays as double *.
 template <typename T>
 struct DBuf {
   T *p = nullptr;
   size_t n = 0;
+  // FASST_OK when `count` elements lie inside the allocation
+  int fits(size_t count, const char *what) const {
+    if (count <= n) return FASST_OK;
+    set_error("DBuf::%s: %zu elements, the buffer holds %zu", what, count, n);
+    return FASST_ERR_SHAPE;
+  }
+  int put(const void *host, size_t count) {
+    FASST_TRY(fits(count, "put"));
+    if (count) FASST_HIP(hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice));
+    return FASST_OK;
+  }
+  int put(const void *host, size_t count, hipStream_t stream) {
+    FASST_TRY(fits(count, "put"));
+    if (count) FASST_HIP(hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, stream));
+    return FASST_OK;
+  }
+  int get(void *host, size_t count) const {
+    FASST_TRY(fits(count, "get"));
+    if (count) FASST_HIP(hipMemcpy(host, p, count * sizeof(T), hipMemcpyDeviceToHost));
+    return FASST_OK;
+  }
+  int get(void *host, size_t count, hipStream_t stream) const {
+    FASST_TRY(fits(count, "get"));
+    if (count) FASST_HIP(hipMemcpyAsync(host, p, count * sizeof(T), hipMemcpyDeviceToHost, stream));
+    return FASST_OK;
+  }
+  // a fresh buffer of exactly the uploaded elements: no zero fill, no sync
+  int upload(const void *host, size_t count) {
+    FASST_TRY(alloc_uninit(count));
+    return put(host, count);
+  }
+  int upload(const void *host, size_t count, hipStream_t stream) {
+    FASST_TRY(alloc_uninit(count));
+    return put(host, count, stream);
+  }
   int alloc(size_t count) {
     release();
     if (count == 0) return FASST_OK;

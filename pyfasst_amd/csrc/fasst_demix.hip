@@ -561,9 +561,7 @@ int demix_features(demix_ctx *c, const double *x0, const double *x1) {
   int st;
   const size_t nin = (size_t)2 * c->F * c->N;
   DBuf<double> d0, d1;
-  if ((st = d0.alloc_uninit(nin)) || (st = d1.alloc_uninit(nin))) return st;
-  FASST_HIP(hipMemcpy(d0.p, x0, nin * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(d1.p, x1, nin * sizeof(double), hipMemcpyHostToDevice));
+  if ((st = d0.upload(x0, nin)) || (st = d1.upload(x1, nin))) return st;
   return demix_features_dev(c, d0.p, d1.p);
 }
 
@@ -642,8 +640,7 @@ int demix_argmax(demix_ctx *c, double *out) {
   k_argmax1<<<a.nblocks, kDB>>>(a);
   k_argmax2<<<1, kDB>>>(a);
   if ((st = dmx_finish(c->tm, 2))) return st;
-  FASST_HIP(hipMemcpy(out, c->aout.p, 4 * sizeof(double), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  return c->aout.get(out, 4);
 }
 
 int demix_theta_pass(demix_ctx *c, double theta_c, double dist_bound, double *sums) {
@@ -661,8 +658,7 @@ int demix_theta_pass(demix_ctx *c, double theta_c, double dist_bound, double *su
   if ((st = dmx_start(c->tm))) return st;
   k_theta_pass<<<c->F, kDB>>>(a);
   if ((st = dmx_finish(c->tm, 1))) return st;
-  FASST_HIP(hipMemcpy(sums, c->sums.p, (size_t)3 * c->F * sizeof(double), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  return c->sums.get(sums, (size_t)3 * c->F);
 }
 
 int demix_delta_pass(demix_ctx *c, int slot, double theta_c, const double *v1, double conf_c,
@@ -685,14 +681,13 @@ int demix_delta_pass(demix_ctx *c, int slot, double theta_c, const double *v1, d
   a.sq_err = std::sqrt(max_err);
   a.centroid = centroid;
   a.only_centroid = only_centroid;
-  if (!only_centroid)
-    FASST_HIP(hipMemcpy(c->v1.p, v1, (size_t)c->F * sizeof(double2), hipMemcpyHostToDevice));
+  if (!only_centroid && (st = c->v1.put(v1, c->F))) return st;
   FASST_HIP(hipMemset(c->cnt.p, 0, 2 * sizeof(unsigned long long)));
   if ((st = dmx_start(c->tm))) return st;
   k_delta_pass<<<(unsigned)((c->n + kDB - 1) / kDB), kDB>>>(a);
   if ((st = dmx_finish(c->tm, 1))) return st;
   unsigned long long h[2];
-  FASST_HIP(hipMemcpy(h, c->cnt.p, sizeof(h), hipMemcpyDeviceToHost));
+  if ((st = c->cnt.get(h, 2))) return st;
   counts[0] = (long)h[0];
   counts[1] = (long)h[1];
   return FASST_OK;
@@ -709,9 +704,7 @@ static int ref_args(demix_ctx *c, int n, const int *slots, const char *fn, RefAr
       set_error("%s: mask %d outside 0 .. %d", fn, slots[k], c->maxc - 1);
       return FASST_ERR_SHAPE;
     }
-  int st;
-  if ((st = dslots.alloc_uninit(n))) return st;
-  FASST_HIP(hipMemcpy(dslots.p, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  FASST_TRY(dslots.upload(slots, n));
   a.masks = c->masks.p;
   a.slots = dslots.p;
   a.thr = nullptr;
@@ -746,8 +739,7 @@ int demix_exclusive(demix_ctx *c, int n, const int *slots, long *sizes) {
   k_exclusive<<<(unsigned)((c->n + kDB - 1) / kDB), kDB>>>(a);
   if ((st = dmx_finish(c->tm, 1))) return st;
   std::vector<unsigned long long> h(n);
-  FASST_HIP(hipMemcpy(h.data(), dsizes.p, (size_t)n * sizeof(unsigned long long),
-                      hipMemcpyDeviceToHost));
+  if ((st = dsizes.get(h.data(), n))) return st;
   for (int k = 0; k < n; ++k) sizes[k] = (long)h[k];
   return FASST_OK;
 }
@@ -765,10 +757,9 @@ int demix_cluster_sums(demix_ctx *c, int n, const int *slots, const double *thre
   DBuf<int> dslots;
   DBuf<double> dthr, part, out;
   if ((st = ref_args(c, n, slots, "demix_cluster_sums", a, dslots))) return st;
-  if ((st = dthr.alloc_uninit(n)) || (st = part.alloc_uninit((size_t)n * a.nblocks * 4)) ||
+  if ((st = dthr.upload(thresholds, n)) || (st = part.alloc_uninit((size_t)n * a.nblocks * 4)) ||
       (st = out.alloc_uninit((size_t)n * 4)))
     return st;
-  FASST_HIP(hipMemcpy(dthr.p, thresholds, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
   a.thr = dthr.p;
   a.part = part.p;
   a.out = out.p;
@@ -776,8 +767,7 @@ int demix_cluster_sums(demix_ctx *c, int n, const int *slots, const double *thre
   k_csums1<<<dim3(a.nblocks, n), kDB>>>(a);
   k_csums2<<<n, kDB>>>(a);
   if ((st = dmx_finish(c->tm, 2))) return st;
-  FASST_HIP(hipMemcpy(sums, out.p, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  return out.get(sums, out.n);
 }
 
 }  // extern "C"

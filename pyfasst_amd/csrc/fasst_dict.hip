@@ -155,18 +155,12 @@ int dict_wf0_stft(int device, int n_cols, const double *f1, const double *f2,
   DBuf<double> d1, d2, dw, dout;
   DBuf<int> dnp;
   DBuf<double2> damps, dtw;
-  if ((st = d1.alloc(n_cols)) || (st = d2.alloc(n_cols)) || (st = dnp.alloc(n_cols)) ||
-      (st = damps.alloc((size_t)n_cols * max_partials)) || (st = dw.alloc(wlen)) ||
-      (st = dtw.alloc(nfft / 2)) || (st = dout.alloc((size_t)F * n_cols)))
-    return st;
   auto tw = twiddles(nfft, -1);
-  FASST_HIP(hipMemcpy(d1.p, f1, n_cols * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(d2.p, f2, n_cols * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dnp.p, n_partials, n_cols * sizeof(int), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(damps.p, amps, (size_t)n_cols * max_partials * sizeof(double2),
-                      hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dw.p, window, wlen * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dtw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
+  if ((st = dout.alloc((size_t)F * n_cols)) || (st = d1.upload(f1, n_cols)) ||
+      (st = d2.upload(f2, n_cols)) || (st = dnp.upload(n_partials, n_cols)) ||
+      (st = damps.upload(amps, (size_t)n_cols * max_partials)) ||
+      (st = dw.upload(window, wlen)) || (st = dtw.upload(tw.data(), tw.size())))
+    return st;
   if (smem > 64 * 1024)
     FASST_HIP(hipFuncSetAttribute((const void *)k_wf0_column,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
@@ -191,8 +185,7 @@ int dict_wf0_stft(int device, int n_cols, const double *f1, const double *f2,
   k_wf0_column<<<n_cols, 256, smem>>>(a);
   FASST_LAUNCH_CHECK();
   if ((st = elapsed_ms(tm.e[0], tm.e[1], 0, &g_dict_ms))) return st;
-  FASST_HIP(hipMemcpy(wf0, dout.p, (size_t)F * n_cols * sizeof(double), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  return dout.get(wf0, dout.n);
 }
 
 int dict_odgd(int device, int n_cols, const double *f1, const double *f2, const int *n_partials,
@@ -228,22 +221,15 @@ int dict_odgd(int device, int n_cols, const double *f1, const double *f2, const 
   DBuf<double> d1, d2, dt, dw, dpow;
   DBuf<int> dnp, dsel;
   DBuf<double2> damps, dtw, dodgd, dspec;
-  if ((st = d1.alloc(C)) || (st = d2.alloc(C)) || (st = dt.alloc(C)) || (st = dnp.alloc(C)) ||
-      (st = dsel.alloc(C)) || (st = damps.alloc(C * max_partials)) ||
-      (st = dw.alloc((size_t)n_windows * L)) || (st = dtw.alloc(N / 2)) ||
-      (st = dodgd.alloc(odgd ? C * L : 0)) || (st = dspec.alloc(spectrum ? C * N : 0)) ||
-      (st = dpow.alloc(power ? N * C : 0)))
-    return st;
   auto tw = twiddles(nfft, -1);
-  FASST_HIP(hipMemcpy(d1.p, f1, C * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(d2.p, f2, C * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dt.p, t_offset, C * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dnp.p, n_partials, C * sizeof(int), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dsel.p, window_sel, C * sizeof(int), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(damps.p, amps, C * max_partials * sizeof(double2), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dw.p, windows, (size_t)n_windows * L * sizeof(double),
-                      hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dtw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
+  if ((st = dodgd.alloc(odgd ? C * L : 0)) || (st = dspec.alloc(spectrum ? C * N : 0)) ||
+      (st = dpow.alloc(power ? N * C : 0)) || (st = d1.upload(f1, C)) ||
+      (st = d2.upload(f2, C)) || (st = dt.upload(t_offset, C)) ||
+      (st = dnp.upload(n_partials, C)) || (st = dsel.upload(window_sel, C)) ||
+      (st = damps.upload(amps, C * max_partials)) ||
+      (st = dw.upload(windows, (size_t)n_windows * L)) ||
+      (st = dtw.upload(tw.data(), tw.size())))
+    return st;
   if (smem > 64 * 1024)
     FASST_HIP(hipFuncSetAttribute((const void *)k_odgd_column,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
@@ -270,11 +256,9 @@ int dict_odgd(int device, int n_cols, const double *f1, const double *f2, const 
   k_odgd_column<<<n_cols, 256, smem>>>(a);
   FASST_LAUNCH_CHECK();
   if ((st = elapsed_ms(tm.e[0], tm.e[1], 0, &g_dict_ms))) return st;
-  if (odgd) FASST_HIP(hipMemcpy(odgd, dodgd.p, C * L * sizeof(double2), hipMemcpyDeviceToHost));
-  if (spectrum)
-    FASST_HIP(hipMemcpy(spectrum, dspec.p, C * N * sizeof(double2), hipMemcpyDeviceToHost));
-  if (power) FASST_HIP(hipMemcpy(power, dpow.p, N * C * sizeof(double), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  // (a buffer whose output was not requested is empty: nothing is copied)
+  if ((st = dodgd.get(odgd, dodgd.n)) || (st = dspec.get(spectrum, dspec.n))) return st;
+  return dpow.get(power, dpow.n);
 }
 
 int dict_last_ms(double *device_ms) {

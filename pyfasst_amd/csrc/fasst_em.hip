@@ -3717,12 +3717,6 @@ static void prof_collect(fasst_ctx *c) {
     }
 }
 
-static int launch_grid(size_t n, int block = 256) {
-  size_t g = (n + block - 1) / block;
-  if (g > 8192) g = 8192;
-  return (int)(g ? g : 1);
-}
-
 // the E-step's default schedule and the fewest quad-steps a balanced block
 // takes by default (fasst_configure)
 constexpr bool kEsBalancedDefault = true;
@@ -4010,7 +4004,7 @@ int build_inst_A(fasst_ctx *c) {
     if (!(c->convm >> j & 1u))
       for (int r = c->roff[j]; r < c->roff[j + 1]; ++r) rowm |= 1u << r;
   prof_begin(c, KINSTA);
-  k_inst_A<<<launch_grid((size_t)c->R * 2 * c->Fp), 256, 0, c->stream>>>(c->Pinst.p, c->A.p, c->R,
+  k_inst_A<<<egrid((size_t)c->R * 2 * c->Fp), 256, 0, c->stream>>>(c->Pinst.p, c->A.p, c->R,
                                                                         c->F, c->Fp, rowm, c->halt);
   prof_end(c, KINSTA);
   FASST_LAUNCH_CHECK();

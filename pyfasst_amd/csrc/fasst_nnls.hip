@@ -280,13 +280,11 @@ int nnls_columns(int device, int m, int n, const double *A, int nf, const double
   const int slots = (int)std::min<size_t>(nf, std::max<size_t>(64, std::min<size_t>(1024, (16ull << 30) / per)));
   DBuf<double> dA, dB, dG, dCt, dX, dL, dLt;
   DBuf<int> dinfo;
-  if ((st = dA.alloc((size_t)m * n)) || (st = dB.alloc((size_t)m * nf)) ||
-      (st = dG.alloc((size_t)n * n)) || (st = dCt.alloc((size_t)nf * n)) ||
+  if ((st = dG.alloc((size_t)n * n)) || (st = dCt.alloc((size_t)nf * n)) ||
       (st = dX.alloc((size_t)n * nf)) || (st = dL.alloc_uninit((size_t)slots * n * n)) ||
-      (st = dLt.alloc_uninit((size_t)slots * n * n)) || (st = dinfo.alloc(nf)))
+      (st = dLt.alloc_uninit((size_t)slots * n * n)) || (st = dinfo.alloc(nf)) ||
+      (st = dA.upload(A, (size_t)m * n)) || (st = dB.upload(B, (size_t)m * nf)))
     return st;
-  FASST_HIP(hipMemcpy(dA.p, A, (size_t)m * n * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dB.p, B, (size_t)m * nf * sizeof(double), hipMemcpyHostToDevice));
   // G = A^T A and C^T = B^T A (k_dgemm2: C[i][j] = sum_k A[k][i] B[k][j])
   if ((st = dgemm2(s, n, n, m, dA.p, n, dA.p, n, dG.p, n))) return st;
   if ((st = dgemm2(s, nf, n, m, dB.p, nf, dA.p, n, dCt.p, n))) return st;
@@ -308,9 +306,8 @@ int nnls_columns(int device, int m, int n, const double *A, int nf, const double
   k_nnls<<<slots, 64, smem, s>>>(a);
   FASST_LAUNCH_CHECK();
   FASST_HIP(hipStreamSynchronize(s));
-  FASST_HIP(hipMemcpy(X, dX.p, (size_t)n * nf * sizeof(double), hipMemcpyDeviceToHost));
-  if (info) FASST_HIP(hipMemcpy(info, dinfo.p, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  FASST_TRY(dX.get(X, dX.n));
+  return info ? dinfo.get(info, dinfo.n) : FASST_OK;
 }
 
 }  // extern "C"

@@ -39,7 +39,7 @@ static inline void sf_count(fasst_ctx *c, int id) {
   if (c->prof) c->prof_cnt[id] += 1;
 }
 
-static int sf_grid(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 16384); }
+constexpr size_t kSfGridCap = 16384;  // blocks of this file's element-wise launches
 
 // V = P0 (one factor) or P0 P1
 __global__ void k_sf_prod(const double *__restrict__ P0, const double *__restrict__ P1,
@@ -519,7 +519,7 @@ static int sf_source_power(fasst_ctx *c, int j) {
   fasst_sf_model *m = c->sf;
   const size_t FT = (size_t)c->F * c->T;
   sf_count(c, KSF_PROD);
-  k_sf_prod<<<sf_grid(FT), 256, 0, c->stream>>>(m->fac[j][0].P.p, m->nfac[j] > 1 ? m->fac[j][1].P.p : nullptr,
+  k_sf_prod<<<egrid(FT, kSfGridCap), 256, 0, c->stream>>>(m->fac[j][0].P.p, m->nfac[j] > 1 ? m->fac[j][1].P.p : nullptr,
                                                 m->V.p + (size_t)j * FT, FT);
   FASST_LAUNCH_CHECK();
   return FASST_OK;
@@ -539,7 +539,7 @@ static int sf_ratio(fasst_ctx *c, int j, int i) {
   fasst_sf_model *m = c->sf;
   const size_t FT = (size_t)c->F * c->T;
   sf_count(c, KSF_RATIO);
-  k_sf_ratio<<<sf_grid(FT), 256, 0, c->stream>>>(m->fac[j][i].P.p, m->nfac[j] > 1 ? m->fac[j][1 - i].P.p : nullptr,
+  k_sf_ratio<<<egrid(FT, kSfGridCap), 256, 0, c->stream>>>(m->fac[j][i].P.p, m->nfac[j] > 1 ? m->fac[j][1 - i].P.p : nullptr,
                                                  m->other.p, m->hatW.p + (size_t)j * FT, m->rn.p, m->rd.p, FT);
   FASST_LAUNCH_CHECK();
   return FASST_OK;
@@ -548,7 +548,7 @@ static int sf_ratio(fasst_ctx *c, int j, int i) {
 static int sf_apply(fasst_ctx *c, double *P, int rows, int cols, const double *num, const double *den,
                     int tr, double omega) {
   sf_count(c, KSF_UPDATE);
-  k_sf_update<<<sf_grid((size_t)rows * cols), 256, 0, c->stream>>>(P, rows, cols, num, den, tr, omega);
+  k_sf_update<<<egrid((size_t)rows * cols, kSfGridCap), 256, 0, c->stream>>>(P, rows, cols, num, den, tr, omega);
   FASST_LAUNCH_CHECK();
   return FASST_OK;
 }
@@ -574,7 +574,7 @@ static int sf_spectral_update(fasst_ctx *c, int j, double omega) {
     // `other`, once per factor, from the powers as they stand
     const double *Po = m->nfac[j] > 1 ? m->fac[j][1 - i].P.p : x.P.p;
     sf_count(c, KSF_OTHER);
-    k_sf_other<<<sf_grid(FT), 256, 0, c->stream>>>(Po, m->other.p, FT);
+    k_sf_other<<<egrid(FT, kSfGridCap), 256, 0, c->stream>>>(Po, m->other.p, FT);
     FASST_LAUNCH_CHECK();
     const double *RB[2] = {m->rn.p, m->rd.p};
     if (x.fb_free) {
@@ -601,13 +601,13 @@ static int sf_spectral_update(fasst_ctx *c, int j, double omega) {
     if (x.tw_free && x.wide) {
       // [num | den] [Kb][2 T] = W^T [rn | rd]: one product, W read once
       sf_count(c, KSF_RATIO);
-      k_sfw_ratio<<<sf_grid(FT), 256, 0, c->stream>>>(x.P.p, m->nfac[j] > 1 ? m->fac[j][1 - i].P.p : nullptr,
+      k_sfw_ratio<<<egrid(FT, kSfGridCap), 256, 0, c->stream>>>(x.P.p, m->nfac[j] > 1 ? m->fac[j][1 - i].P.p : nullptr,
                                                       m->other.p, m->hatW.p + (size_t)j * FT, m->rnd.p, T, FT);
       FASST_LAUNCH_CHECK();
       sf_count(c, KSFW_DGEMM2);
       if ((st = dgemm2(c->stream, Kb, 2 * T, F, x.W.p, x.ldw, m->rnd.p, 2 * T, m->cnd.p, 2 * T))) return st;
       sf_count(c, KSFW_UPDATE);
-      k_sfw_update<<<sf_grid((size_t)Kb * T), 256, 0, c->stream>>>(x.tw, m->cnd.p, T, (size_t)Kb * T, omega);
+      k_sfw_update<<<egrid((size_t)Kb * T, kSfGridCap), 256, 0, c->stream>>>(x.tw, m->cnd.p, T, (size_t)Kb * T, omega);
       FASST_LAUNCH_CHECK();
       if (more && (st = sf_power(c, j, i, false))) return st;
     } else if (x.tw_free) {
@@ -656,7 +656,7 @@ static int sf_renormalize(fasst_ctx *c) {
         FASST_LAUNCH_CHECK();
         k_sfw_colfin<<<kg, 256, 0, c->stream>>>(a, G);
         FASST_LAUNCH_CHECK();
-        k_sfw_fbapply<<<sf_grid((size_t)c->F * x.Kb), 256, 0, c->stream>>>(a);
+        k_sfw_fbapply<<<egrid((size_t)c->F * x.Kb, kSfGridCap), 256, 0, c->stream>>>(a);
         FASST_LAUNCH_CHECK();
         k_sfw_twscale<<<nb, 256, 0, c->stream>>>(a);
         FASST_LAUNCH_CHECK();
@@ -665,7 +665,7 @@ static int sf_renormalize(fasst_ctx *c) {
         if (c->prof) c->prof_cnt[KSFW_RENORM] += 5;
         if (!a.last) {
           sf_count(c, KSFW_RENORM);
-          k_sfw_twdiv<<<sf_grid(n), 256, 0, c->stream>>>(a);
+          k_sfw_twdiv<<<egrid(n, kSfGridCap), 256, 0, c->stream>>>(a);
           FASST_LAUNCH_CHECK();
         }
         continue;
@@ -695,7 +695,7 @@ static int sf_iteration(fasst_ctx *c, const double *dpsd, double *dll, double om
     return st;
   for (int j = 0; j < m->J; ++j) {
     sf_count(c, KSF_HATW);
-    k_sf_hatw<<<sf_grid(FT), 256, 0, c->stream>>>(m->ws.p, m->hatW.p + (size_t)j * FT, m->roff[j], m->rank[j],
+    k_sf_hatw<<<egrid(FT, kSfGridCap), 256, 0, c->stream>>>(m->ws.p, m->hatW.p + (size_t)j * FT, m->roff[j], m->rank[j],
                                                   FT);
     FASST_LAUNCH_CHECK();
   }
@@ -707,7 +707,7 @@ static int sf_iteration(fasst_ctx *c, const double *dpsd, double *dll, double om
 static int sf_flags_mask(fasst_ctx *c, int *mask) {
   fasst_sf_model *m = c->sf;
   int h[1 + 2 * kMaxJ];
-  FASST_HIP(hipMemcpyAsync(h, m->flags.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  FASST_TRY(m->flags.get(h, 1 + 2 * kMaxJ, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   if (h[0]) {
     set_error("Singular Matrix");
@@ -945,10 +945,8 @@ int fasst_sf_configure(fasst_ctx *c, int J, const int *rank, const int *mix_conv
     sf_release(c);
     return st;
   }
-  FASST_HIP(hipMemcpy(m->kind.p, kind, R * sizeof(int), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(m->droff.p, m->roff, (J + 1) * sizeof(int), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(m->dconv.p, m->conv, J * sizeof(int), hipMemcpyHostToDevice));
-  return FASST_OK;
+  if ((st = m->kind.put(kind, R)) || (st = m->droff.put(m->roff, J + 1))) return st;
+  return m->dconv.put(m->conv, J);
 }
 
 int fasst_sf_set_spatial(fasst_ctx *c, int j, const double *params, int free_) {
@@ -1070,8 +1068,7 @@ static int sf_run(fasst_ctx *c, int n_iter, const double *psd, double omega, con
     if ((st = m->psd.alloc((size_t)n_iter * c->F)) || (st = m->ll.alloc(n_iter))) return st;
     m->psd_cap = n_iter;
   }
-  FASST_HIP(hipMemcpyAsync(m->psd.p, psd, (size_t)n_iter * c->F * sizeof(double), hipMemcpyHostToDevice,
-                           c->stream));
+  FASST_TRY(m->psd.put(psd, (size_t)n_iter * c->F, c->stream));
   FASST_HIP(hipMemsetAsync(m->flags.p, 0, (1 + 2 * kMaxJ) * sizeof(int), c->stream));
   int nconv = 0;
   for (int j = 0; j < m->J; ++j)
@@ -1091,7 +1088,7 @@ static int sf_run(fasst_ctx *c, int n_iter, const double *psd, double omega, con
     if (sigma && (st = sf_reweigh(c, sigma[it]))) return st;
   }
   if (iters_done) *iters_done = done;
-  FASST_HIP(hipMemcpy(logliks, m->ll.p, (size_t)done * sizeof(double), hipMemcpyDeviceToHost));
+  FASST_TRY(m->ll.get(logliks, done));
   if (mask) {
     if (restart_mask) *restart_mask = mask;
     return FASST_TW_RESTART;
@@ -1153,11 +1150,11 @@ int fasst_sf_wiener_images(fasst_ctx *c, const double *psd, int nsrc, const int 
   const size_t FT = (size_t)c->F * c->T;
   DBuf<double> dpsd;
   DBuf<double2> dS;
-  if ((st = dpsd.alloc_uninit(c->F)) || (st = dS.alloc_uninit((size_t)nsrc * 2 * FT))) return st;
-  FASST_HIP(hipMemcpyAsync(dpsd.p, psd, c->F * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if ((st = dpsd.upload(psd, c->F, c->stream)) || (st = dS.alloc_uninit((size_t)nsrc * 2 * FT)))
+    return st;
   if ((st = sf_all_powers(c))) return st;
   if ((st = sf_launch_wiener(c, dpsd.p, nsrc, src_of, dS.p, FT, (size_t)c->T, 1))) return st;
-  FASST_HIP(hipMemcpyAsync(S, dS.p, dS.n * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+  FASST_TRY(dS.get(S, dS.n, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -1200,7 +1197,7 @@ int fasst_sf_separate_waveforms(fasst_ctx *c, const double *psd, int nsrc, const
     if ((st = tf_launch_istft(c->stream, dS.p + (size_t)q * plane, c->Fp, T, dw.p, daw.p, dtw.p, wlen, nfft,
                               hop, dframes.p, dy.p + (size_t)q * len_out, len_out)))
       return st;
-  FASST_HIP(hipMemcpyAsync(y, dy.p, dy.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  FASST_TRY(dy.get(y, dy.n, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -1223,8 +1220,8 @@ int fasst_sf_separate_waveforms_cqt(fasst_ctx *c, cqt_ctx *q, const double *psd,
   const size_t plane = (size_t)c->Tp * c->Fp;
   DBuf<double> dpsd;
   DBuf<double2> dS;
-  if ((st = dpsd.alloc_uninit(c->F)) || (st = dS.alloc((size_t)nsrc * 2 * plane))) return st;
-  FASST_HIP(hipMemcpyAsync(dpsd.p, psd, c->F * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if ((st = dS.alloc((size_t)nsrc * 2 * plane)) || (st = dpsd.upload(psd, c->F, c->stream)))
+    return st;
   if ((st = sf_all_powers(c))) return st;
   if ((st = sf_launch_wiener(c, dpsd.p, nsrc, src_of, dS.p, plane, 1, (size_t)c->Fp))) return st;
   CqtImages im;

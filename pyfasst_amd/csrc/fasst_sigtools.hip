@@ -247,20 +247,6 @@ static int finish_launch(int n_kernels, Events &tm) {
   return FASST_OK;
 }
 
-template <typename T>
-static int upload(DBuf<T> &d, const T *h, size_t n) {
-  int st = d.alloc_uninit(n);
-  if (st) return st;
-  if (n) FASST_HIP(hipMemcpy(d.p, h, n * sizeof(T), hipMemcpyHostToDevice));
-  return FASST_OK;
-}
-
-template <typename T>
-static int download(T *h, const DBuf<T> &d, size_t n) {
-  if (n) FASST_HIP(hipMemcpy(h, d.p, n * sizeof(T), hipMemcpyDeviceToHost));
-  return FASST_OK;
-}
-
 static bool pca_shape_ok(int F, int N, int nb) {
   if (F < 1 || N < 1 || nb < 1 || nb > N) {
     set_error("sig_pca2d: bad shape (F %d, N %d, neighbor_nb %d: 1 <= neighbor_nb <= N)", F, N,
@@ -328,8 +314,7 @@ int sig_pca2d_dev(int device, int F, int N, int nb, const double *x0, const doub
   if ((st = tm.start(0))) return st;
   k_pca2d<<<a.nchunks * F, kPcaChunk, smem>>>(a);
   if ((st = finish_launch(1, tm))) return st;
-  FASST_HIP(hipMemcpy(flags, dflags.p, 2 * sizeof(int), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  return dflags.get(flags, 2);
 }
 
 int sig_pca2d(int device, int F, int N, int nb, const double *x0, const double *x1,
@@ -343,16 +328,15 @@ int sig_pca2d(int device, int F, int N, int nb, const double *x0, const double *
   int st;
   const size_t nin = (size_t)2 * F * N, nl = (size_t)F * (N - nb + 1);
   DBuf<double> d0, d1, dM, dm, dvM, dvm;
-  if ((st = upload(d0, x0, nin)) || (st = upload(d1, x1, nin)) || (st = dM.alloc_uninit(nl)) ||
+  if ((st = d0.upload(x0, nin)) || (st = d1.upload(x1, nin)) || (st = dM.alloc_uninit(nl)) ||
       (st = dm.alloc_uninit(nl)) || (st = dvM.alloc_uninit(4 * nl)) ||
       (st = dvm.alloc_uninit(4 * nl)))
     return st;
   if ((st = sig_pca2d_dev(device, F, N, nb, d0.p, d1.p, dM.p, dm.p, dvM.p, dvm.p, flags)))
     return st;
-  if ((st = download(lambda_M, dM, nl)) || (st = download(lambda_m, dm, nl)) ||
-      (st = download(v_M, dvM, 4 * nl)) || (st = download(v_m, dvm, 4 * nl)))
+  if ((st = dM.get(lambda_M, nl)) || (st = dm.get(lambda_m, nl)) || (st = dvM.get(v_M, 4 * nl)))
     return st;
-  return FASST_OK;
+  return dvm.get(v_m, 4 * nl);
 }
 
 static bool median_shape_ok(int R, int N, int length, const double *in, const double *out) {
@@ -394,9 +378,9 @@ int sig_median(int device, int R, int N, int length, const double *in, double *o
   int st;
   const size_t n = (size_t)R * N;
   DBuf<double> din, dout;
-  if ((st = upload(din, in, n)) || (st = dout.alloc_uninit(n))) return st;
+  if ((st = din.upload(in, n)) || (st = dout.alloc_uninit(n))) return st;
   if ((st = sig_median_dev(device, R, N, length, din.p, dout.p))) return st;
-  return download(out, dout, n);
+  return dout.get(out, n);
 }
 
 static bool hsum_shape_ok(int F, int T, int n_f0, int n_harm, const void *tf, const void *w,
@@ -478,14 +462,14 @@ int sig_hsum(int device, int F, int T, int n_f0, int n_harm, const double *tf,
   DBuf<double> dtf, dw, dhs;
   DBuf<int> dptr_, didx;
   const size_t nout = (size_t)n_f0 * T;
-  if ((st = upload(dtf, tf, (size_t)F * T)) || (st = upload(dw, weights, (size_t)F)) ||
-      (st = upload(dptr_, bin_ptr, np)) || (st = upload(didx, bin_idx, (size_t)nnz)) ||
+  if ((st = dtf.upload(tf, (size_t)F * T)) || (st = dw.upload(weights, (size_t)F)) ||
+      (st = dptr_.upload(bin_ptr, np)) || (st = didx.upload(bin_idx, (size_t)nnz)) ||
       (st = dhs.alloc_uninit(nout)))
     return st;
   if ((st = sig_hsum_dev(device, F, T, n_f0, n_harm, dtf.p, dw.p, dptr_.p, didx.p, nnz, prod,
                          dhs.p)))
     return st;
-  return download(hs, dhs, nout);
+  return dhs.get(hs, nout);
 }
 
 static bool invherm_shape_ok(long n, const void *a00, const void *a01, const void *a11,
@@ -520,8 +504,7 @@ int sig_invherm_dev(int device, long n, int off_complex, const double *a00, cons
   if ((st = tm.start(0))) return st;
   k_invherm_elem<<<(int)((n + 255) / 256), 256>>>(a);
   if ((st = finish_launch(1, tm))) return st;
-  FASST_HIP(hipMemcpy(n_zero_det, dz.p, sizeof(int), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  return dz.get(n_zero_det, 1);
 }
 
 int sig_invherm(int device, long n, int off_complex, const double *a00, const double *a01,
@@ -531,16 +514,14 @@ int sig_invherm(int device, long n, int off_complex, const double *a00, const do
   int st;
   const size_t m = (size_t)n, mo = off_complex ? 2 * m : m;
   DBuf<double> d00, d01, d11, o00, o01, o11;
-  if ((st = upload(d00, a00, m)) || (st = upload(d01, a01, mo)) || (st = upload(d11, a11, m)) ||
+  if ((st = d00.upload(a00, m)) || (st = d01.upload(a01, mo)) || (st = d11.upload(a11, m)) ||
       (st = o00.alloc_uninit(m)) || (st = o01.alloc_uninit(mo)) || (st = o11.alloc_uninit(m)))
     return st;
   if ((st = sig_invherm_dev(device, n, off_complex, d00.p, d01.p, d11.p, o00.p, o01.p, o11.p,
                             n_zero_det)))
     return st;
-  if ((st = download(i00, o00, m)) || (st = download(i01, o01, mo)) ||
-      (st = download(i11, o11, m)))
-    return st;
-  return FASST_OK;
+  if ((st = o00.get(i00, m)) || (st = o01.get(i01, mo))) return st;
+  return o11.get(i11, m);
 }
 
 }  // extern "C"

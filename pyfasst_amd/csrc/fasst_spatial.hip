@@ -279,18 +279,17 @@ static int finish_launch(int slot, int n_kernels, Events &tm, hipStream_t stream
   return elapsed_ms(tm.e[0], tm.e[1], stream, &g_sp_ms[slot]);
 }
 
+// DBuf's upload / get, counted into fasst_spatial_transfer_bytes
 template <typename T>
-static int upload(DBuf<T> &d, const T *h, size_t n) {
-  int st = d.alloc_uninit(n);
-  if (st) return st;
-  FASST_HIP(hipMemcpy(d.p, h, n * sizeof(T), hipMemcpyHostToDevice));
+static int sp_send(DBuf<T> &d, const void *h, size_t n) {
+  FASST_TRY(d.upload(h, n));
   g_sp_bytes += (long)(n * sizeof(T));
   return FASST_OK;
 }
 
 template <typename T>
-static int download(T *h, const T *d, size_t n) {
-  FASST_HIP(hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost));
+static int sp_fetch(void *h, const DBuf<T> &d, size_t n) {
+  FASST_TRY(d.get(h, n));
   g_sp_bytes += (long)(n * sizeof(T));
   return FASST_OK;
 }
@@ -385,7 +384,7 @@ int fasst_steer_ula(int device, int nch, int F, int ntheta, const double *freqs,
   DBuf<double> dfr, dsn;
   DBuf<double2> dout;
   const size_t nout = (size_t)ntheta * nch * F;
-  if ((st = upload(dfr, freqs, (size_t)F)) || (st = upload(dsn, sin_theta, (size_t)ntheta)) ||
+  if ((st = sp_send(dfr, freqs, (size_t)F)) || (st = sp_send(dsn, sin_theta, (size_t)ntheta)) ||
       (st = dout.alloc_uninit(nout)))
     return st;
   SteerArgs a;
@@ -401,7 +400,7 @@ int fasst_steer_ula(int device, int nch, int F, int ntheta, const double *freqs,
   if ((st = tm.start(0))) return st;
   k_steer_ula<<<dim3(bin_blocks(F), nch * ntheta), 256>>>(a);
   if ((st = finish_launch(FASST_SPATIAL_K_STEER_ULA, 1, tm, 0))) return st;
-  return download((double2 *)out, dout.p, nout);
+  return sp_fetch(out, dout, nout);
 }
 
 int fasst_steer_acous(int device, int nch, int F, const double *freqs, const double *dist,
@@ -416,7 +415,7 @@ int fasst_steer_acous(int device, int nch, int F, const double *freqs, const dou
   DBuf<double> dfr, dds;
   DBuf<double2> dout;
   const size_t nout = (size_t)nch * F;
-  if ((st = upload(dfr, freqs, (size_t)F)) || (st = upload(dds, dist, (size_t)nch)) ||
+  if ((st = sp_send(dfr, freqs, (size_t)F)) || (st = sp_send(dds, dist, (size_t)nch)) ||
       (st = dout.alloc_uninit(nout)))
     return st;
   SteerArgs a;
@@ -432,7 +431,7 @@ int fasst_steer_acous(int device, int nch, int F, const double *freqs, const dou
   if ((st = tm.start(0))) return st;
   k_steer_acous<<<dim3(bin_blocks(F), nch), 256>>>(a);
   if ((st = finish_launch(FASST_SPATIAL_K_STEER_ACOUS, 1, tm, 0))) return st;
-  return download((double2 *)out, dout.p, nout);
+  return sp_fetch(out, dout, nout);
 }
 
 int fasst_cx_tmean(fasst_ctx *c, double *mean) {
@@ -444,7 +443,7 @@ int fasst_cx_tmean(fasst_ctx *c, double *mean) {
   MeanWork w;
   int st;
   if ((st = run_cx_tmean(c, w))) return st;
-  return download(mean, w.mean.p, (size_t)4 * c->F);
+  return sp_fetch(mean, w.mean, (size_t)4 * c->F);
 }
 
 int fasst_dir_diag(fasst_ctx *c, int ntheta, const double *freqs, const double *sin_theta,
@@ -460,7 +459,7 @@ int fasst_dir_diag(fasst_ctx *c, int ntheta, const double *freqs, const double *
   MeanWork w;
   DBuf<double> dfr, dsn, did, ddet, dout;
   DBuf<double2> dioff;
-  if ((st = upload(dfr, freqs, (size_t)F)) || (st = upload(dsn, sin_theta, (size_t)ntheta)) ||
+  if ((st = sp_send(dfr, freqs, (size_t)F)) || (st = sp_send(dsn, sin_theta, (size_t)ntheta)) ||
       (st = did.alloc_uninit((size_t)2 * F)) || (st = ddet.alloc_uninit((size_t)F)) ||
       (st = dioff.alloc_uninit((size_t)F)) || (st = dout.alloc_uninit((size_t)ntheta * F)))
     return st;
@@ -479,9 +478,9 @@ int fasst_dir_diag(fasst_ctx *c, int ntheta, const double *freqs, const double *
   if ((st = tm.start(c->stream))) return st;
   k_capon_diagram<<<dim3(bin_blocks(F), ntheta), 256, 0, c->stream>>>(a);
   if ((st = finish_launch(FASST_SPATIAL_K_CAPON, 1, tm, c->stream))) return st;
-  if ((st = download(diagram, dout.p, (size_t)ntheta * F)) || (st = download(det, ddet.p, (size_t)F)))
+  if ((st = sp_fetch(diagram, dout, (size_t)ntheta * F)) || (st = sp_fetch(det, ddet, (size_t)F)))
     return st;
-  if (mean && (st = download(mean, w.mean.p, (size_t)4 * F))) return st;
+  if (mean && (st = sp_fetch(mean, w.mean, (size_t)4 * F))) return st;
   return FASST_OK;
 }
 
@@ -501,8 +500,8 @@ int fasst_ula_response(int device, int n, int F, int ntheta, const double *w, co
   DBuf<double> dfr, dsn, dout;
   DBuf<double2> dw;
   const size_t nout = (size_t)ntheta * F;
-  if ((st = upload(dfr, freqs, (size_t)F)) || (st = upload(dsn, sin_theta, (size_t)ntheta)) ||
-      (st = upload(dw, (const double2 *)w, (size_t)n * F)) || (st = dout.alloc_uninit(nout)))
+  if ((st = sp_send(dfr, freqs, (size_t)F)) || (st = sp_send(dsn, sin_theta, (size_t)ntheta)) ||
+      (st = sp_send(dw, w,(size_t)n * F)) || (st = dout.alloc_uninit(nout)))
     return st;
   RespArgs a;
   a.freqs = dfr.p;
@@ -518,7 +517,7 @@ int fasst_ula_response(int device, int n, int F, int ntheta, const double *w, co
   if ((st = tm.start(0))) return st;
   k_ula_response<<<dim3(bin_blocks(F), ntheta), 256>>>(a);
   if ((st = finish_launch(FASST_SPATIAL_K_ULA_RESPONSE, 1, tm, 0))) return st;
-  return download(diagram, dout.p, nout);
+  return sp_fetch(diagram, dout, nout);
 }
 
 int fasst_mvdr_target(int device, int F, int n_interf, const double *target, const double *interf,
@@ -530,8 +529,8 @@ int fasst_mvdr_target(int device, int F, int n_interf, const double *target, con
   DeviceGuard g(device);
   int st;
   DBuf<double2> dt, di, dw;
-  if ((st = upload(dt, (const double2 *)target, (size_t)2 * F)) ||
-      (n_interf > 0 && (st = upload(di, (const double2 *)interf, (size_t)n_interf * 2 * F))) ||
+  if ((st = sp_send(dt, target,(size_t)2 * F)) ||
+      (n_interf > 0 && (st = sp_send(di, interf,(size_t)n_interf * 2 * F))) ||
       (st = dw.alloc_uninit((size_t)2 * F)))
     return st;
   MvdrArgs a;
@@ -544,7 +543,7 @@ int fasst_mvdr_target(int device, int F, int n_interf, const double *target, con
   if ((st = tm.start(0))) return st;
   k_mvdr_target<<<bin_blocks(F), 256>>>(a);
   if ((st = finish_launch(FASST_SPATIAL_K_MVDR_TARGET, 1, tm, 0))) return st;
-  return download((double2 *)w, dw.p, (size_t)2 * F);
+  return sp_fetch(w, dw, (size_t)2 * F);
 }
 
 }  // extern "C"

@@ -492,8 +492,6 @@ __global__ void k_wiener_gain(const double *__restrict__ sd, const double2 *__re
   }
 }
 
-static int grid_of(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 16384); }
-
 int suff_stat_device(fasst_ctx *c, hipStream_t s, int R, const double *dV, const int *vmap,
                      const double2 *dmix, const double *dpsd, double2 *drxx, double2 *drxs,
                      double2 *drss, double *dws, double *dllb, double *dll) {
@@ -552,8 +550,7 @@ int fasst_source_powers(fasst_ctx *c, int j0, int nj, const unsigned long long *
     k_source_powers<<<dim3((c->T + 255) / 256, c->F, 1), 256, 0, c->stream>>>(
         c->Wkf.p, c->TW.p, dV.p, c->F, c->T, c->Fp, c->Tp, c->KP, j0 + jj, m0, m1);
     FASST_LAUNCH_CHECK();
-    FASST_HIP(hipMemcpyAsync(V + (size_t)jj * c->F * c->T, dV.p, (size_t)c->F * c->T * sizeof(double),
-                             hipMemcpyDeviceToHost, c->stream));
+    FASST_TRY(dV.get(V + (size_t)jj * c->F * c->T, dV.n, c->stream));
   }
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
@@ -578,27 +575,22 @@ int fasst_suff_stat(fasst_ctx *c, int R, const double *V, const double *mix, con
   DBuf<double> dV, dws, dpsd, dllb, dll;
   DBuf<double2> dmix, drss, drxs, drxx;
   int st;
-  if ((st = dV.alloc_uninit((size_t)R * FT)) || (st = dws.alloc_uninit((size_t)R * FT)) ||
-      (st = dpsd.alloc_uninit(c->F)) || (st = dllb.alloc_uninit(c->F)) || (st = dll.alloc_uninit(1)) ||
-      (st = dmix.alloc_uninit((size_t)R * 2 * c->F)) || (st = drss.alloc_uninit((size_t)c->F * R * R)) ||
-      (st = drxs.alloc_uninit((size_t)c->F * 2 * R)) || (st = drxx.alloc_uninit((size_t)3 * c->F)))
+  if ((st = dws.alloc_uninit((size_t)R * FT)) || (st = dllb.alloc_uninit(c->F)) ||
+      (st = dll.alloc_uninit(1)) || (st = drss.alloc_uninit((size_t)c->F * R * R)) ||
+      (st = drxs.alloc_uninit((size_t)c->F * 2 * R)) || (st = drxx.alloc_uninit((size_t)3 * c->F)) ||
+      (st = dV.upload(V, (size_t)R * FT, c->stream)) ||
+      (st = dmix.upload(mix, (size_t)R * 2 * c->F, c->stream)) ||
+      (st = dpsd.upload(psd, c->F, c->stream)))
     return st;
-  FASST_HIP(hipMemcpyAsync(dV.p, V, (size_t)R * FT * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(dmix.p, mix, (size_t)R * 2 * c->F * sizeof(double2), hipMemcpyHostToDevice,
-                           c->stream));
-  FASST_HIP(hipMemcpyAsync(dpsd.p, psd, c->F * sizeof(double), hipMemcpyHostToDevice, c->stream));
   int vmap[kStepMaxR];
   for (int r = 0; r < R; ++r) vmap[r] = r;
   if ((st = suff_stat_device(c, c->stream, R, dV.p, vmap, dmix.p, dpsd.p, drxx.p, drxs.p, drss.p, dws.p,
                              dllb.p, dll.p)))
     return st;
-  FASST_HIP(hipMemcpyAsync(rxx, drxx.p, 3 * c->F * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
-  FASST_HIP(hipMemcpyAsync(rxs, drxs.p, (size_t)c->F * 2 * R * sizeof(double2), hipMemcpyDeviceToHost,
-                           c->stream));
-  FASST_HIP(hipMemcpyAsync(rss, drss.p, (size_t)c->F * R * R * sizeof(double2), hipMemcpyDeviceToHost,
-                           c->stream));
-  FASST_HIP(hipMemcpyAsync(ws, dws.p, (size_t)R * FT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  FASST_HIP(hipMemcpyAsync(loglik, dll.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if ((st = drxx.get(rxx, drxx.n, c->stream)) || (st = drxs.get(rxs, drxs.n, c->stream)) ||
+      (st = drss.get(rss, drss.n, c->stream)) || (st = dws.get(ws, dws.n, c->stream)) ||
+      (st = dll.get(loglik, 1, c->stream)))
+    return st;
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -626,27 +618,18 @@ int fasst_mix_solve(int device, int F, int R, const double *rss, const double *r
   DBuf<double2> drss, drxs, dmix;
   DBuf<int> dkind, dsing;
   int st;
-  if ((st = drss.alloc_uninit((size_t)F * R * R)) || (st = drxs.alloc_uninit((size_t)F * 2 * R)) ||
-      (st = dmix.alloc_uninit((size_t)R * 2 * F)) || (st = dkind.alloc_uninit(R)) || (st = dsing.alloc(1)))
+  if ((st = dsing.alloc(1)) || (st = drss.upload(rss, (size_t)F * R * R)) ||
+      (st = drxs.upload(rxs, (size_t)F * 2 * R)) || (st = dmix.upload(mix, (size_t)R * 2 * F)) ||
+      (st = dkind.upload(kind, R)) ||
+      (st = mix_solve_device(nullptr, F, R, drss.p, drxs.p, dmix.p, dkind.p, nconv, dsing.p)))
     return st;
-  FASST_HIP(hipMemcpy(drss.p, rss, (size_t)F * R * R * sizeof(double2), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(drxs.p, rxs, (size_t)F * 2 * R * sizeof(double2), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dmix.p, mix, (size_t)R * 2 * F * sizeof(double2), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dkind.p, kind, R * sizeof(int), hipMemcpyHostToDevice));
-  k_mix_solve_inst<<<1, 1024, 0, nullptr>>>(drss.p, drxs.p, dmix.p, F, R, dkind.p, dsing.p);
-  FASST_LAUNCH_CHECK();
-  if (nconv) {
-    k_mix_solve_conv<<<(F + 63) / 64, 64, 0, nullptr>>>(drss.p, drxs.p, dmix.p, F, R, dsing.p);
-    FASST_LAUNCH_CHECK();
-  }
   int sing = 0;
-  FASST_HIP(hipMemcpy(&sing, dsing.p, sizeof(int), hipMemcpyDeviceToHost));
+  FASST_TRY(dsing.get(&sing, 1));
   if (sing) {
     set_error("Singular Matrix");
     return FASST_ERR_SINGULAR;
   }
-  FASST_HIP(hipMemcpy(mix, dmix.p, (size_t)R * 2 * F * sizeof(double2), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  return dmix.get(mix, dmix.n);
 }
 
 int fasst_sigma_comp(fasst_ctx *c, int j, const unsigned long long *colmask, double *diag,
@@ -663,8 +646,7 @@ int fasst_sigma_comp(fasst_ctx *c, int j, const unsigned long long *colmask, dou
       c->Wkf.p, c->TW.p, c->A.p, dd.p, doff.p, c->F, c->T, c->Fp, c->Tp, c->KP, j, c->roff[j],
       c->roff[j + 1], colmask[0], colmask[1]);
   FASST_LAUNCH_CHECK();
-  FASST_HIP(hipMemcpyAsync(diag, dd.p, 2 * FT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  FASST_HIP(hipMemcpyAsync(off, doff.p, FT * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+  if ((st = dd.get(diag, dd.n, c->stream)) || (st = doff.get(off, doff.n, c->stream))) return st;
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -677,17 +659,14 @@ int fasst_inv_sigma_mix(int device, int n, int F, int T, const double *diag, con
   DBuf<double> dd, dpsd, did;
   DBuf<double2> doff, dio;
   int st;
-  if ((st = dd.alloc_uninit((size_t)n * 2 * FT)) || (st = doff.alloc_uninit((size_t)n * FT)) ||
-      (st = dpsd.alloc_uninit(F)) || (st = did.alloc_uninit(2 * FT)) || (st = dio.alloc_uninit(FT)))
+  if ((st = did.alloc_uninit(2 * FT)) || (st = dio.alloc_uninit(FT)) ||
+      (st = dd.upload(diag, (size_t)n * 2 * FT)) || (st = doff.upload(off, (size_t)n * FT)) ||
+      (st = dpsd.upload(psd, F)))
     return st;
-  FASST_HIP(hipMemcpy(dd.p, diag, (size_t)n * 2 * FT * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(doff.p, off, (size_t)n * FT * sizeof(double2), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dpsd.p, psd, F * sizeof(double), hipMemcpyHostToDevice));
-  k_inv_sigma_mix<<<grid_of(FT), 256>>>(dd.p, doff.p, dpsd.p, did.p, dio.p, n, F, T);
+  k_inv_sigma_mix<<<egrid(FT, 16384), 256>>>(dd.p, doff.p, dpsd.p, did.p, dio.p, n, F, T);
   FASST_LAUNCH_CHECK();
-  FASST_HIP(hipMemcpy(idiag, did.p, 2 * FT * sizeof(double), hipMemcpyDeviceToHost));
-  FASST_HIP(hipMemcpy(ioff, dio.p, FT * sizeof(double2), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  FASST_TRY(did.get(idiag, did.n));
+  return dio.get(ioff, dio.n);
 }
 
 int fasst_wiener_gain(int device, long n, const double *sdiag, const double *soff,
@@ -697,17 +676,13 @@ int fasst_wiener_gain(int device, long n, const double *sdiag, const double *sof
   DBuf<double> dsd, did;
   DBuf<double2> dso, dio, dwg;
   int st;
-  if ((st = dsd.alloc_uninit(2 * (size_t)n)) || (st = did.alloc_uninit(2 * (size_t)n)) ||
-      (st = dso.alloc_uninit(n)) || (st = dio.alloc_uninit(n)) || (st = dwg.alloc_uninit(4 * (size_t)n)))
+  if ((st = dwg.alloc_uninit(4 * (size_t)n)) || (st = dsd.upload(sdiag, 2 * (size_t)n)) ||
+      (st = did.upload(idiag, 2 * (size_t)n)) || (st = dso.upload(soff, n)) ||
+      (st = dio.upload(ioff, n)))
     return st;
-  FASST_HIP(hipMemcpy(dsd.p, sdiag, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(did.p, idiag, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dso.p, soff, (size_t)n * sizeof(double2), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dio.p, ioff, (size_t)n * sizeof(double2), hipMemcpyHostToDevice));
-  k_wiener_gain<<<grid_of(n), 256>>>(dsd.p, dso.p, did.p, dio.p, dwg.p, (size_t)n);
+  k_wiener_gain<<<egrid(n, 16384), 256>>>(dsd.p, dso.p, did.p, dio.p, dwg.p, (size_t)n);
   FASST_LAUNCH_CHECK();
-  FASST_HIP(hipMemcpy(WG, dwg.p, 4 * (size_t)n * sizeof(double2), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  return dwg.get(WG, dwg.n);
 }
 
 }  // extern "C"

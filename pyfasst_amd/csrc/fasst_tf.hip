@@ -743,6 +743,46 @@ int tf_launch_istft(hipStream_t s, const double2 *S, int ld, int T, const double
   return FASST_OK;
 }
 
+// fasst_istft, and fasst_istft_simm (simm): the latter keeps the first half
+// window, refuses an output shorter than two windows (its edge copy) and
+// overlap-adds with k_ola_simm
+static int istft_host(bool simm, int device, const double *X, int n_frames, const double *window,
+                      const double *analysis_window, int wlen, int nfft, int hop, double *y) {
+  int st = check_fft(nfft, wlen, hop);
+  if (st) return st;
+  if (n_frames < 1 || !X || !y) return FASST_ERR_SHAPE;
+  const int F = nfft / 2 + 1, T = n_frames;
+  const int len_out = hop * (T - 1) + wlen - (simm ? 0 : wlen / 2);
+  if (simm && len_out < 2 * wlen) {
+    set_error("istft: %d samples < two windows (%d); the reference's edge copy fails", len_out,
+              wlen);
+    return FASST_ERR_SHAPE;
+  }
+  DeviceGuard g(device);
+  if ((st = fft_smem(nfft))) return st;
+  DBuf<double> dw, daw, dframes, dy;
+  DBuf<double2> dtw, dX, dXt;
+  auto tw = twiddles(nfft, +1);
+  if ((st = dXt.alloc((size_t)T * F)) || (st = dframes.alloc((size_t)T * wlen)) ||
+      (st = dy.alloc(len_out)) || (st = dw.upload(window, wlen)) ||
+      (st = daw.upload(analysis_window ? analysis_window : window, wlen)) ||
+      (st = dtw.upload(tw.data(), tw.size())) || (st = dX.upload(X, (size_t)T * F)))
+    return st;
+  // [F][T] -> [T][F]
+  k_ft_to_tf<<<dim3((T + 15) / 16, (F + 15) / 16, 1), 256>>>(dX.p, dXt.p, F, T, F, T);
+  FASST_LAUNCH_CHECK();
+  k_istft_frames<<<T, 256, nfft * sizeof(double2)>>>(dXt.p, F, dw.p, wlen, dtw.p, nfft,
+                                                     ilog2(nfft), dframes.p);
+  FASST_LAUNCH_CHECK();
+  if (simm)
+    k_ola_simm<<<(len_out + 255) / 256, 256>>>(dframes.p, T, wlen, hop, dw.p, daw.p, dy.p, len_out);
+  else
+    k_ola<<<(len_out + 255) / 256, 256>>>(dframes.p, T, wlen, hop, dw.p, daw.p, dy.p, len_out);
+  FASST_LAUNCH_CHECK();
+  FASST_HIP(hipDeviceSynchronize());
+  return dy.get(y, len_out);
+}
+
 }  // namespace fasst
 
 using namespace fasst;
@@ -761,13 +801,12 @@ int fasst_stft(int device, const double *x, int L, const double *window, int wle
   const int F = nfft / 2 + 1;
   DBuf<double> dx, dw;
   DBuf<double2> dtw, dX, dXt;
-  if ((st = dx.alloc(std::max(L, 1))) || (st = dw.alloc(wlen)) || (st = dtw.alloc(nfft / 2)) ||
-      (st = dX.alloc((size_t)T * F)) || (st = dXt.alloc((size_t)T * F)))
-    return st;
   auto tw = twiddles(nfft, -1);
-  FASST_HIP(hipMemcpy(dx.p, x, (size_t)L * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dw.p, window, (size_t)wlen * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dtw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
+  // dx is larger than the signal when L == 0: zero-filled, then the copy
+  if ((st = dx.alloc(std::max(L, 1))) || (st = dX.alloc((size_t)T * F)) ||
+      (st = dXt.alloc((size_t)T * F)) || (st = dx.put(x, L)) || (st = dw.upload(window, wlen)) ||
+      (st = dtw.upload(tw.data(), tw.size())))
+    return st;
   k_stft_frames<<<dim3(T, 1), 256, nfft * sizeof(double2)>>>(dx.p, L, dw.p, wlen, dtw.p, nfft,
                                                              ilog2(nfft), hop, dX.p, F, 0);
   FASST_LAUNCH_CHECK();
@@ -775,80 +814,17 @@ int fasst_stft(int device, const double *x, int L, const double *window, int wle
   k_tf_to_ft<<<dim3((T + 15) / 16, (F + 15) / 16, 1), 256>>>(dX.p, dXt.p, F, T, F, T);
   FASST_LAUNCH_CHECK();
   FASST_HIP(hipDeviceSynchronize());
-  FASST_HIP(hipMemcpy(X, dXt.p, (size_t)T * F * sizeof(double2), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  return dXt.get(X, dXt.n);
 }
 
 int fasst_istft(int device, const double *X, int n_frames, const double *window,
                 const double *analysis_window, int wlen, int nfft, int hop, double *y) {
-  int st = check_fft(nfft, wlen, hop);
-  if (st) return st;
-  if (n_frames < 1 || !X || !y) return FASST_ERR_SHAPE;
-  DeviceGuard g(device);
-  if ((st = fft_smem(nfft))) return st;
-  const int F = nfft / 2 + 1, T = n_frames;
-  const int len_out = hop * (T - 1) + wlen - wlen / 2;
-  DBuf<double> dw, daw, dframes, dy;
-  DBuf<double2> dtw, dX, dXt;
-  if ((st = dw.alloc(wlen)) || (st = daw.alloc(wlen)) || (st = dtw.alloc(nfft / 2)) ||
-      (st = dX.alloc((size_t)T * F)) || (st = dXt.alloc((size_t)T * F)) ||
-      (st = dframes.alloc((size_t)T * wlen)) || (st = dy.alloc(len_out)))
-    return st;
-  auto tw = twiddles(nfft, +1);
-  FASST_HIP(hipMemcpy(dw.p, window, (size_t)wlen * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(daw.p, analysis_window ? analysis_window : window,
-                      (size_t)wlen * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dtw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dX.p, X, (size_t)T * F * sizeof(double2), hipMemcpyHostToDevice));
-  // [F][T] -> [T][F]
-  k_ft_to_tf<<<dim3((T + 15) / 16, (F + 15) / 16, 1), 256>>>(dX.p, dXt.p, F, T, F, T);
-  FASST_LAUNCH_CHECK();
-  k_istft_frames<<<T, 256, nfft * sizeof(double2)>>>(dXt.p, F, dw.p, wlen, dtw.p, nfft,
-                                                     ilog2(nfft), dframes.p);
-  FASST_LAUNCH_CHECK();
-  k_ola<<<(len_out + 255) / 256, 256>>>(dframes.p, T, wlen, hop, dw.p, daw.p, dy.p, len_out);
-  FASST_LAUNCH_CHECK();
-  FASST_HIP(hipDeviceSynchronize());
-  FASST_HIP(hipMemcpy(y, dy.p, (size_t)len_out * sizeof(double), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  return istft_host(false, device, X, n_frames, window, analysis_window, wlen, nfft, hop, y);
 }
 
 int fasst_istft_simm(int device, const double *X, int n_frames, const double *window,
                      const double *analysis_window, int wlen, int nfft, int hop, double *y) {
-  int st = check_fft(nfft, wlen, hop);
-  if (st) return st;
-  if (n_frames < 1 || !X || !y) return FASST_ERR_SHAPE;
-  const int F = nfft / 2 + 1, T = n_frames;
-  const int len_out = hop * (T - 1) + wlen;
-  if (len_out < 2 * wlen) {
-    set_error("istft: %d samples < two windows (%d); the reference's edge copy fails", len_out,
-              wlen);
-    return FASST_ERR_SHAPE;
-  }
-  DeviceGuard g(device);
-  if ((st = fft_smem(nfft))) return st;
-  DBuf<double> dw, daw, dframes, dy;
-  DBuf<double2> dtw, dX, dXt;
-  if ((st = dw.alloc(wlen)) || (st = daw.alloc(wlen)) || (st = dtw.alloc(nfft / 2)) ||
-      (st = dX.alloc((size_t)T * F)) || (st = dXt.alloc((size_t)T * F)) ||
-      (st = dframes.alloc((size_t)T * wlen)) || (st = dy.alloc(len_out)))
-    return st;
-  auto tw = twiddles(nfft, +1);
-  FASST_HIP(hipMemcpy(dw.p, window, (size_t)wlen * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(daw.p, analysis_window ? analysis_window : window,
-                      (size_t)wlen * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dtw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dX.p, X, (size_t)T * F * sizeof(double2), hipMemcpyHostToDevice));
-  k_ft_to_tf<<<dim3((T + 15) / 16, (F + 15) / 16, 1), 256>>>(dX.p, dXt.p, F, T, F, T);
-  FASST_LAUNCH_CHECK();
-  k_istft_frames<<<T, 256, nfft * sizeof(double2)>>>(dXt.p, F, dw.p, wlen, dtw.p, nfft,
-                                                     ilog2(nfft), dframes.p);
-  FASST_LAUNCH_CHECK();
-  k_ola_simm<<<(len_out + 255) / 256, 256>>>(dframes.p, T, wlen, hop, dw.p, daw.p, dy.p, len_out);
-  FASST_LAUNCH_CHECK();
-  FASST_HIP(hipDeviceSynchronize());
-  FASST_HIP(hipMemcpy(y, dy.p, (size_t)len_out * sizeof(double), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  return istft_host(true, device, X, n_frames, window, analysis_window, wlen, nfft, hop, y);
 }
 
 int fasst_set_audio(fasst_ctx *c, const double *data, int L, const double *window, int wlen,
@@ -871,15 +847,11 @@ int fasst_set_audio(fasst_ctx *c, const double *data, int L, const double *windo
   }
   DBuf<double> dx, dw;
   DBuf<double2> dtw;
-  if ((st = dx.alloc((size_t)2 * L)) || (st = dw.alloc(wlen)) || (st = dtw.alloc(nfft / 2)))
-    return st;
   auto tw = twiddles(nfft, -1);
-  FASST_HIP(hipMemcpyAsync(dx.p, chans.data(), chans.size() * sizeof(double),
-                           hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(dw.p, window, (size_t)wlen * sizeof(double), hipMemcpyHostToDevice,
-                           c->stream));
-  FASST_HIP(hipMemcpyAsync(dtw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice,
-                           c->stream));
+  if ((st = dx.upload(chans.data(), chans.size(), c->stream)) ||
+      (st = dw.upload(window, wlen, c->stream)) ||
+      (st = dtw.upload(tw.data(), tw.size(), c->stream)))
+    return st;
   FASST_HIP(hipMemsetAsync(c->X.p, 0, c->X.n * sizeof(double2), c->stream));
   k_stft_frames<<<dim3(T, 2), 256, nfft * sizeof(double2), c->stream>>>(
       dx.p, L, dw.p, wlen, dtw.p, nfft, ilog2(nfft), hop, c->X.p, c->Fp, (size_t)c->Tp * c->Fp);
@@ -906,7 +878,7 @@ int fasst_mix_psd(fasst_ctx *c, double *mix_psd) {
   FASST_LAUNCH_CHECK();
   k_mix_psd<<<(c->F + 255) / 256, 256, 0, c->stream>>>(part.p, c->F, c->T, c->Fp, d.p);
   FASST_LAUNCH_CHECK();
-  FASST_HIP(hipMemcpyAsync(mix_psd, d.p, c->F * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  FASST_TRY(d.get(mix_psd, c->F, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -916,8 +888,7 @@ int fasst_set_cx(fasst_ctx *c, const double *cx) {
   DeviceGuard g(c->device);
   DBuf<double2> h;
   int st;
-  if ((st = h.alloc((size_t)3 * c->F * c->T))) return st;
-  FASST_HIP(hipMemcpyAsync(h.p, cx, h.n * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+  if ((st = h.upload(cx, (size_t)3 * c->F * c->T, c->stream))) return st;
   k_cx_unpack<<<dim3(c->ntt, c->nft), 256, 0, c->stream>>>(h.p, c->cx.p, c->F, c->T, c->Fp, c->Tp);
   FASST_LAUNCH_CHECK();
   FASST_HIP(hipStreamSynchronize(c->stream));
@@ -934,7 +905,7 @@ int fasst_get_cx(fasst_ctx *c, double *cx) {
   if ((st = h.alloc((size_t)3 * c->F * c->T))) return st;
   k_cx_pack<<<dim3(c->ntt, c->nft), 256, 0, c->stream>>>(c->cx.p, h.p, c->F, c->T, c->Fp, c->Tp);
   FASST_LAUNCH_CHECK();
-  FASST_HIP(hipMemcpyAsync(cx, h.p, h.n * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+  FASST_TRY(h.get(cx, h.n, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -946,8 +917,7 @@ static int upload_stft(fasst_ctx *c, const double *X) {
   int st;
   if (!c->X.p && (st = c->X.alloc((size_t)2 * c->Tp * c->Fp))) return st;
   DBuf<double2> h;
-  if ((st = h.alloc((size_t)2 * c->F * c->T))) return st;
-  FASST_HIP(hipMemcpyAsync(h.p, X, h.n * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+  if ((st = h.upload(X, (size_t)2 * c->F * c->T, c->stream))) return st;
   k_ft_to_tf<<<dim3(c->ntt, c->nft, 2), 256, 0, c->stream>>>(h.p, c->X.p, c->F, c->T, c->Fp, c->Tp);
   FASST_LAUNCH_CHECK();
   FASST_HIP(hipStreamSynchronize(c->stream));
@@ -1034,8 +1004,8 @@ int fasst_wiener_images(fasst_ctx *c, const double *psd, const double *X, double
       (st = droff.alloc(kMaxJ + 1)) || (st = dS.alloc((size_t)NS * 2 * plane)) ||
       (st = hS.alloc((size_t)NS * 2 * c->F * c->T)))
     return st;
-  FASST_HIP(hipMemcpyAsync(dpsd.p, psd, c->F * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(droff.p, c->roff, (J + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if ((st = dpsd.put(psd, c->F, c->stream)) || (st = droff.put(c->roff, J + 1, c->stream)))
+    return st;
   // W = FB.FW and the per-bin mixing for 'inst'
   if ((st = build_inst_A(c))) return st;
   if ((st = launch_w_old(c))) return st;
@@ -1044,7 +1014,7 @@ int fasst_wiener_images(fasst_ctx *c, const double *psd, const double *X, double
   if ((st = launch_wiener(c, coef.p, dpsd.p, dS.p))) return st;
   k_tf_to_ft<<<dim3(c->ntt, c->nft, NS * 2), 256, 0, c->stream>>>(dS.p, hS.p, c->F, c->T, c->Fp, c->Tp);
   FASST_LAUNCH_CHECK();
-  FASST_HIP(hipMemcpyAsync(S, hS.p, hS.n * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+  FASST_TRY(hS.get(S, hS.n, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -1077,18 +1047,14 @@ int fasst_separate_waveforms(fasst_ctx *c, const double *psd, const double *wind
   DBuf<double2> dS, dtw;
   if ((st = dpsd.alloc(c->Fp)) || (st = coef.alloc((size_t)J * 4 * c->Fp)) ||
       (st = droff.alloc(kMaxJ + 1)) || (st = dS.alloc((size_t)NS * 2 * plane)) ||
-      (st = dw.alloc(wlen)) || (st = daw.alloc(wlen)) || (st = dtw.alloc(nfft / 2)) ||
       (st = dframes.alloc((size_t)T * wlen)) || (st = dy.alloc((size_t)NS * 2 * len_out)))
     return st;
   auto tw = twiddles(nfft, +1);
-  FASST_HIP(hipMemcpyAsync(dpsd.p, psd, c->F * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(droff.p, c->roff, (J + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(dw.p, window, (size_t)wlen * sizeof(double), hipMemcpyHostToDevice,
-                           c->stream));
-  FASST_HIP(hipMemcpyAsync(daw.p, analysis_window ? analysis_window : window,
-                           (size_t)wlen * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(dtw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice,
-                           c->stream));
+  if ((st = dpsd.put(psd, c->F, c->stream)) || (st = droff.put(c->roff, J + 1, c->stream)) ||
+      (st = dw.upload(window, wlen, c->stream)) ||
+      (st = daw.upload(analysis_window ? analysis_window : window, wlen, c->stream)) ||
+      (st = dtw.upload(tw.data(), tw.size(), c->stream)))
+    return st;
   if ((st = build_inst_A(c))) return st;
   if ((st = launch_w_old(c))) return st;
   k_mixcoef<<<(c->Fp + 255) / 256, 256, 0, c->stream>>>(c->A.p, coef.p, J, droff.p, c->F, c->Fp);
@@ -1104,7 +1070,7 @@ int fasst_separate_waveforms(fasst_ctx *c, const double *psd, const double *wind
                                                         dy.p + (size_t)q * len_out, len_out);
     FASST_LAUNCH_CHECK();
   }
-  FASST_HIP(hipMemcpyAsync(y, dy.p, dy.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  FASST_TRY(dy.get(y, dy.n, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -1128,9 +1094,7 @@ static int spatial_gains(fasst_ctx *c, DBuf<int> &droff, DBuf<double2> &G) {
   int st;
   if ((st = droff.alloc_uninit(kMaxJ + 1)) || (st = G.alloc_uninit((size_t)c->J * 4 * c->Fp)))
     return st;
-  FASST_HIP(hipMemcpyAsync(droff.p, c->roff, (c->J + 1) * sizeof(int), hipMemcpyHostToDevice,
-                           c->stream));
-  if ((st = build_inst_A(c))) return st;
+  if ((st = droff.put(c->roff, c->J + 1, c->stream)) || (st = build_inst_A(c))) return st;
   k_spatial_gain<<<(c->Fp + 255) / 256, 256, 0, c->stream>>>(c->A.p, droff.p, c->J, c->F, c->Fp,
                                                              G.p);
   FASST_LAUNCH_CHECK();
@@ -1175,7 +1139,7 @@ int fasst_spatial_filter_images(fasst_ctx *c, double *S) {
   FASST_LAUNCH_CHECK();
   k_tf_to_ft<<<dim3(c->ntt, c->nft, J * 2), 256, 0, c->stream>>>(dS.p, hS.p, c->F, c->T, c->Fp, c->Tp);
   FASST_LAUNCH_CHECK();
-  FASST_HIP(hipMemcpyAsync(S, hS.p, hS.n * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+  FASST_TRY(hS.get(S, hS.n, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -1204,17 +1168,13 @@ int fasst_spatial_filter_waveforms(fasst_ctx *c, const double *window,
   DBuf<double> dw, daw, dframes, dy;
   DBuf<int> droff;
   DBuf<double2> G, dtw;
-  if ((st = dw.alloc(wlen)) || (st = daw.alloc(wlen)) || (st = dtw.alloc(nfft / 2)) ||
-      (st = dframes.alloc_uninit((size_t)T * wlen)) ||
-      (st = dy.alloc_uninit((size_t)J * 2 * len_out)))
-    return st;
   auto tw = twiddles(nfft, +1);
-  FASST_HIP(hipMemcpyAsync(dw.p, window, (size_t)wlen * sizeof(double), hipMemcpyHostToDevice,
-                           c->stream));
-  FASST_HIP(hipMemcpyAsync(daw.p, analysis_window ? analysis_window : window,
-                           (size_t)wlen * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(dtw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice,
-                           c->stream));
+  if ((st = dframes.alloc_uninit((size_t)T * wlen)) ||
+      (st = dy.alloc_uninit((size_t)J * 2 * len_out)) ||
+      (st = dw.upload(window, wlen, c->stream)) ||
+      (st = daw.upload(analysis_window ? analysis_window : window, wlen, c->stream)) ||
+      (st = dtw.upload(tw.data(), tw.size(), c->stream)))
+    return st;
   if ((st = spatial_gains(c, droff, G))) return st;
   // image q = (n, channel): its frames are g0 X0 + g1 X1 of the resident X
   // rows, formed in the iSTFT's LDS buffer; only waveforms are written
@@ -1227,7 +1187,7 @@ int fasst_spatial_filter_waveforms(fasst_ctx *c, const double *window,
                                                         dy.p + (size_t)q * len_out, len_out);
     FASST_LAUNCH_CHECK();
   }
-  FASST_HIP(hipMemcpyAsync(y, dy.p, dy.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  FASST_TRY(dy.get(y, dy.n, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -1250,12 +1210,10 @@ int fasst_gcc_phat(fasst_ctx *c, int nfft, double *out) {
   const size_t plane = (size_t)c->Tp * c->Fp;
   DBuf<double> d, dt;
   DBuf<double2> dtw;
-  if ((st = d.alloc_uninit((size_t)T * nfft)) || (st = dt.alloc_uninit((size_t)T * nfft)) ||
-      (st = dtw.alloc(nfft / 2)))
-    return st;
   auto tw = twiddles(nfft, +1);
-  FASST_HIP(hipMemcpyAsync(dtw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice,
-                           c->stream));
+  if ((st = d.alloc_uninit((size_t)T * nfft)) || (st = dt.alloc_uninit((size_t)T * nfft)) ||
+      (st = dtw.upload(tw.data(), tw.size(), c->stream)))
+    return st;
   // Cx01 is resident whichever way the observation came (k_cx_from_X forms it
   // from the channel STFTs): planes 2 and 3 of cx
   k_gcc_phat<<<T, 256, nfft * sizeof(double2), c->stream>>>(c->cx.p + 2 * plane, c->cx.p + 3 * plane,
@@ -1263,7 +1221,7 @@ int fasst_gcc_phat(fasst_ctx *c, int nfft, double *out) {
   FASST_LAUNCH_CHECK();
   k_real_transpose<<<dim3((T + 15) / 16, (nfft + 15) / 16), 256, 0, c->stream>>>(d.p, dt.p, T, nfft);
   FASST_LAUNCH_CHECK();
-  FASST_HIP(hipMemcpyAsync(out, dt.p, dt.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  FASST_TRY(dt.get(out, dt.n, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -1276,18 +1234,14 @@ int fasst_inv_herm_mat_2d(int device, int n, const double *diag, const double *o
   DBuf<double> dd, did, ddet;
   DBuf<double2> doff, dioff;
   int st;
-  if ((st = dd.alloc((size_t)2 * n)) || (st = did.alloc((size_t)2 * n)) || (st = ddet.alloc(n)) ||
-      (st = doff.alloc(n)) || (st = dioff.alloc(n)))
+  if ((st = did.alloc((size_t)2 * n)) || (st = ddet.alloc(n)) || (st = dioff.alloc(n)) ||
+      (st = dd.upload(diag, (size_t)2 * n)) || (st = doff.upload(off, n)))
     return st;
-  FASST_HIP(hipMemcpy(dd.p, diag, (size_t)2 * n * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(doff.p, off, (size_t)n * sizeof(double2), hipMemcpyHostToDevice));
   k_inv_herm<<<std::min((n + 255) / 256, 4096), 256>>>(n, dd.p, doff.p, did.p, dioff.p, ddet.p);
   FASST_LAUNCH_CHECK();
   FASST_HIP(hipDeviceSynchronize());
-  FASST_HIP(hipMemcpy(inv_diag, did.p, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost));
-  FASST_HIP(hipMemcpy(inv_off, dioff.p, (size_t)n * sizeof(double2), hipMemcpyDeviceToHost));
-  FASST_HIP(hipMemcpy(det, ddet.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  if ((st = did.get(inv_diag, did.n)) || (st = dioff.get(inv_off, dioff.n))) return st;
+  return ddet.get(det, ddet.n);
 }
 
 }  // extern "C"
@@ -1337,8 +1291,8 @@ int fasst_separate_waveforms_cqt(fasst_ctx *c, cqt_ctx *q, const double *psd, lo
   if ((st = dpsd.alloc(c->Fp)) || (st = coef.alloc((size_t)J * 4 * c->Fp)) ||
       (st = droff.alloc(kMaxJ + 1)) || (st = dS.alloc((size_t)NS * 2 * plane)))
     return st;
-  FASST_HIP(hipMemcpyAsync(dpsd.p, psd, c->F * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(droff.p, c->roff, (J + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if ((st = dpsd.put(psd, c->F, c->stream)) || (st = droff.put(c->roff, J + 1, c->stream)))
+    return st;
   if ((st = build_inst_A(c))) return st;
   if ((st = launch_w_old(c))) return st;
   k_mixcoef<<<(c->Fp + 255) / 256, 256, 0, c->stream>>>(c->A.p, coef.p, J, droff.p, c->F, c->Fp);
