@@ -127,42 +127,127 @@ inline int elapsed_ms(hipEvent_t start, hipEvent_t end, hipStream_t stream, floa
     if (st_) return st_;                                                     \
   } while (0)
 
-// Device buffer owned by a context or a call's scope; freed in the destructor.
-// The one host transfer path: put / get / upload count elements of T, check
-// the count against the allocation (FASST_ERR_SHAPE, nothing copied) and do
-// nothing for a count of 0.  Without a stream the copy blocks (hipMemcpy);
-// with one it is queued on it (hipMemcpyAsync).  The host pointer is untyped
-// because the C ABI passes double2 arrays as double *.
+// The bounds rule of every host transfer, in elements: `rows` rows of `width`,
+// `host_pitch` apart on the host and `dev_pitch` apart on the device, lie in a
+// device span of `n`.  A linear copy of `count` is one row of pitch `count`.
+constexpr bool span_fits(size_t n, size_t rows, size_t width, size_t host_pitch,
+                         size_t dev_pitch) {
+  return rows == 0 || width == 0 ||
+         (width <= host_pitch && width <= dev_pitch && width <= n &&
+          rows - 1 <= (n - width) / dev_pitch);
+}
+static_assert(span_fits(12, 1, 12, 12, 12), "exact fit");
+static_assert(!span_fits(12, 1, 13, 13, 13), "one element over");
+static_assert(span_fits(0, 0, 5, 5, 16) && span_fits(0, 3, 0, 0, 0), "rows == 0, width == 0");
+static_assert(!span_fits(0, 1, 1, 1, 1), "anything into an empty span");
+static_assert(span_fits(48, 3, 16, 16, 16), "width == pitch");
+static_assert(!span_fits(48, 3, 16, 16, 15) && !span_fits(48, 3, 16, 15, 16), "width > pitch");
+static_assert(span_fits(37, 3, 5, 5, 16), "the last row ends exactly at n");
+static_assert(!span_fits(36, 3, 5, 5, 16), "the last row ends one past n");
+static_assert(span_fits(37, 3, 5, 7, 16), "host pitch above the width");
+static_assert(!span_fits(47, 4, 5, 5, 16) && span_fits(53, 4, 5, 5, 16), "four rows");
+static_assert(!span_fits(4, 2, 3, 3, 0), "zero device pitch");
+static_assert(!span_fits(~(size_t)0, 3, 5, 5, ~(size_t)0 / 2 + 1), "no wrap-around in rows * pitch");
+
+// Non-owning view of `n` elements of device memory, the one host transfer path:
+// every count, width and pitch is in elements of T, checked with span_fits
+// (FASST_ERR_SHAPE, nothing copied); an empty transfer does nothing.  Without a
+// stream a call blocks (hipMemcpy, hipMemcpy2D, hipMemset); with one it is queued
+// on it.  The host pointer is untyped: the C ABI passes double2 arrays as double *.
 template <typename T>
-struct DBuf {
+struct DSpan {
   T *p = nullptr;
   size_t n = 0;
-  // FASST_OK when `count` elements lie inside the allocation
-  int fits(size_t count, const char *what) const {
-    if (count <= n) return FASST_OK;
-    set_error("DBuf::%s: %zu elements, the buffer holds %zu", what, count, n);
+  // the part from `off` (of `count`); empty, so refusing a transfer, if outside
+  DSpan at(size_t off) const { return off <= n ? DSpan{p + off, n - off} : DSpan{}; }
+  DSpan at(size_t off, size_t count) const {
+    return off <= n && count <= n - off ? DSpan{p + off, count} : DSpan{};
+  }
+  int fits(size_t rows, size_t width, size_t hp, size_t dp, const char *what) const {
+    if (span_fits(n, rows, width, hp, dp)) return FASST_OK;
+    set_error("DSpan::%s: %zu rows of %zu elements, pitch %zu (host %zu), the span holds %zu",
+              what, rows, width, dp, hp, n);
     return FASST_ERR_SHAPE;
   }
-  int put(const void *host, size_t count) {
-    FASST_TRY(fits(count, "put"));
+  int put(const void *host, size_t count) const {
+    FASST_TRY(fits(1, count, count, count, "put"));
     if (count) FASST_HIP(hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice));
     return FASST_OK;
   }
-  int put(const void *host, size_t count, hipStream_t stream) {
-    FASST_TRY(fits(count, "put"));
+  int put(const void *host, size_t count, hipStream_t stream) const {
+    FASST_TRY(fits(1, count, count, count, "put"));
     if (count) FASST_HIP(hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, stream));
     return FASST_OK;
   }
   int get(void *host, size_t count) const {
-    FASST_TRY(fits(count, "get"));
+    FASST_TRY(fits(1, count, count, count, "get"));
     if (count) FASST_HIP(hipMemcpy(host, p, count * sizeof(T), hipMemcpyDeviceToHost));
     return FASST_OK;
   }
   int get(void *host, size_t count, hipStream_t stream) const {
-    FASST_TRY(fits(count, "get"));
+    FASST_TRY(fits(1, count, count, count, "get"));
     if (count) FASST_HIP(hipMemcpyAsync(host, p, count * sizeof(T), hipMemcpyDeviceToHost, stream));
     return FASST_OK;
   }
+  // `rows` rows of `width` elements between a host matrix of row pitch `hp`
+  // and a device image of row pitch `dp`
+  int put_rows(const void *host, size_t rows, size_t width, size_t hp, size_t dp) const {
+    FASST_TRY(fits(rows, width, hp, dp, "put_rows"));
+    if (rows && width)
+      FASST_HIP(hipMemcpy2D(p, dp * sizeof(T), host, hp * sizeof(T), width * sizeof(T), rows,
+                            hipMemcpyHostToDevice));
+    return FASST_OK;
+  }
+  int put_rows(const void *host, size_t rows, size_t width, size_t hp, size_t dp,
+               hipStream_t stream) const {
+    FASST_TRY(fits(rows, width, hp, dp, "put_rows"));
+    if (rows && width)
+      FASST_HIP(hipMemcpy2DAsync(p, dp * sizeof(T), host, hp * sizeof(T), width * sizeof(T), rows,
+                                 hipMemcpyHostToDevice, stream));
+    return FASST_OK;
+  }
+  int get_rows(void *host, size_t rows, size_t width, size_t hp, size_t dp) const {
+    FASST_TRY(fits(rows, width, hp, dp, "get_rows"));
+    if (rows && width)
+      FASST_HIP(hipMemcpy2D(host, hp * sizeof(T), p, dp * sizeof(T), width * sizeof(T), rows,
+                            hipMemcpyDeviceToHost));
+    return FASST_OK;
+  }
+  int get_rows(void *host, size_t rows, size_t width, size_t hp, size_t dp,
+               hipStream_t stream) const {
+    FASST_TRY(fits(rows, width, hp, dp, "get_rows"));
+    if (rows && width)
+      FASST_HIP(hipMemcpy2DAsync(host, hp * sizeof(T), p, dp * sizeof(T), width * sizeof(T), rows,
+                                 hipMemcpyDeviceToHost, stream));
+    return FASST_OK;
+  }
+  int zero(size_t count) const {
+    FASST_TRY(fits(1, count, count, count, "zero"));
+    if (count) FASST_HIP(hipMemset(p, 0, count * sizeof(T)));
+    return FASST_OK;
+  }
+  int zero(size_t count, hipStream_t stream) const {
+    FASST_TRY(fits(1, count, count, count, "zero"));
+    if (count) FASST_HIP(hipMemsetAsync(p, 0, count * sizeof(T), stream));
+    return FASST_OK;
+  }
+};
+
+// Device buffer owned by a context or a call's scope; freed in the destructor.
+// put / get / zero go through the span over the whole buffer; a part of it, and
+// every pitched copy, names its span: at(off).get(..), at(0).put_rows(..).
+template <typename T>
+struct DBuf {
+  T *p = nullptr;
+  size_t n = 0;
+  DSpan<T> at(size_t off) const { return DSpan<T>{p, n}.at(off); }
+  DSpan<T> at(size_t off, size_t count) const { return DSpan<T>{p, n}.at(off, count); }
+  int put(const void *host, size_t count) { return at(0).put(host, count); }
+  int put(const void *host, size_t count, hipStream_t stream) { return at(0).put(host, count, stream); }
+  int get(void *host, size_t count) const { return at(0).get(host, count); }
+  int get(void *host, size_t count, hipStream_t stream) const { return at(0).get(host, count, stream); }
+  int zero(size_t count) const { return at(0).zero(count); }
+  int zero(size_t count, hipStream_t stream) const { return at(0).zero(count, stream); }
   // a fresh buffer of exactly the uploaded elements: no zero fill, no sync
   int upload(const void *host, size_t count) {
     FASST_TRY(alloc_uninit(count));

@@ -768,7 +768,7 @@ int forward_dev(cqt_ctx *c, const Geo &g, hipStream_t s, int B, double2 *sp, int
 
 // one signal into the context's own raster c->sp ([W][F])
 int forward_dev(cqt_ctx *c, const Geo &g, hipStream_t s) {
-  FASST_HIP(hipMemsetAsync(c->sp.p, 0, (size_t)g.W * g.F * sizeof(double2), s));
+  FASST_TRY(c->sp.zero((size_t)g.W * g.F, s));
   return forward_dev(c, g, s, 1, c->sp.p, g.F, 0);
 }
 
@@ -795,9 +795,9 @@ int ensure_cells(cqt_ctx *c, const Geo &g, long L) {
 // from the raster in c->sp (MinQT: invertFromSpCQTRast; CQT: invertFromCellCQT
 // on the cells spCQT2CellCQT derives).  cells given (perfRast=0): invertFromCellCQT
 // on them (minqt.py:1019-1055), then invertLinearPart on the linear cell.
-// The B rasters of a batch are `im`; signal b's result is at *yout_p + b * n_y.
+// The B rasters of a batch are `im`; signal b's result is at yout_p->p + b * n_y.
 int inverse_dev(cqt_ctx *c, const Geo &g, long L, const double2 *cells, hipStream_t s,
-                double **yout_p, const CqtImages &im, int B) {
+                DSpan<double> *yout_p, const CqtImages &im, int B) {
   int st;
   c->signals = B;
   c->launches = 0;
@@ -805,9 +805,9 @@ int inverse_dev(cqt_ctx *c, const Geo &g, long L, const double2 *cells, hipStrea
   const double empty_hops = (double)c->first_center / (double)c->atom_hop;
   long ysize = (long)std::ceil((double)L / std::ldexp(1.0, c->oct - 1));
   const long ycap = (long)c->n_y;
-  double *ycur = c->yb.p, *yalt = c->yc.p;
+  DSpan<double> ycur = c->yb.at(0), yalt = c->yc.at(0);
   // every signal's overlap-add accumulator starts from zero
-  FASST_HIP(hipMemsetAsync(ycur, 0, (size_t)B * ycap * sizeof(double), s));
+  FASST_TRY(ycur.zero((size_t)B * ycap, s));
   for (int noct = c->oct - 1; noct >= 0; --noct) {
     const long step = 1L << noct;
     const int ns = rast ? (int)step : 1;
@@ -859,7 +859,7 @@ int inverse_dev(cqt_ctx *c, const Geo &g, long L, const double2 *cells, hipStrea
         k_icqt_frames<false><<<gfr, 256, ((size_t)c->N + c->M) * sizeof(double2), s>>>(a);
       CQT_LAUNCH_CHECK();
       k_icqt_ola<<<dim3((unsigned)((ysize + 255) / 256), B), 256, 0, s>>>(
-          c->frames.p, nfr, c->N, c->fft_hop, rast ? sh * inc : 0.0, ycur, ysize, c->n_fr,
+          c->frames.p, nfr, c->N, c->fft_hop, rast ? sh * inc : 0.0, ycur.p, ysize, c->n_fr,
           c->n_y);
       CQT_LAUNCH_CHECK();
     }
@@ -868,8 +868,8 @@ int inverse_dev(cqt_ctx *c, const Geo &g, long L, const double2 *cells, hipStrea
         set_error("inverse CQT buffer overflow (%ld > %ld)", 2 * ysize, ycap);
         return FASST_ERR_SHAPE;
       }
-      FASST_HIP(hipMemsetAsync(yalt, 0, (size_t)B * ycap * sizeof(double), s));
-      if ((st = filtfilt(c, s, B, ycur, c->n_y, 2 * ysize, 1, yalt, c->n_y, 0, 2.0))) return st;
+      FASST_TRY(yalt.zero((size_t)B * ycap, s));
+      if ((st = filtfilt(c, s, B, ycur.p, c->n_y, 2 * ysize, 1, yalt.p, c->n_y, 0, 2.0))) return st;
       std::swap(ycur, yalt);
       ysize *= 2;
     }
@@ -878,7 +878,7 @@ int inverse_dev(cqt_ctx *c, const Geo &g, long L, const double2 *cells, hipStrea
     set_error("inverse CQT: %ld samples < prefix %ld + %ld", ysize, g.maxBlock, L);
     return FASST_ERR_SHAPE;
   }
-  double *yout = ycur + g.maxBlock;   // y[prefixZeros:][:datalen_init]
+  const DSpan<double> yout = ycur.at(g.maxBlock);   // y[prefixZeros:][:datalen_init]
   *yout_p = yout;
   if (c->lin_N) {                     // + invertLinearPart (minqt.py:1469-1485)
     long dropped0 = (long)(empty_hops * (std::ldexp(1.0, c->oct - 1) - 1.0));
@@ -905,7 +905,7 @@ int inverse_dev(cqt_ctx *c, const Geo &g, long L, const double2 *cells, hipStrea
         c->n_fr);
     CQT_LAUNCH_CHECK();
     k_icqt_lin_ola<<<dim3((unsigned)((L + 255) / 256), B), 256, 0, s>>>(
-        c->frames.p, g.W, c->lin_N, c->atom_hop, c->lwin.p, off + c->lin_N / 2, yout, L, c->n_fr,
+        c->frames.p, g.W, c->lin_N, c->atom_hop, c->lwin.p, off + c->lin_N / 2, yout.p, L, c->n_fr,
         c->n_y);
     CQT_LAUNCH_CHECK();
   }
@@ -914,7 +914,7 @@ int inverse_dev(cqt_ctx *c, const Geo &g, long L, const double2 *cells, hipStrea
 
 // one signal from the context's own raster c->sp ([W][F]) or the given cells
 int inverse_dev(cqt_ctx *c, const Geo &g, long L, const double2 *cells, hipStream_t s,
-                double **yout_p) {
+                DSpan<double> *yout_p) {
   CqtImages im;
   im.S = c->sp.p;
   im.ld = g.F;
@@ -1041,20 +1041,17 @@ int cqt_create(int device, int bins, int octave_nr, int win_nr, int fft_len, int
   for (auto &e : c->ev)
     if (hipEventCreate(&e) != hipSuccess) return fail(FASST_ERR_DEVICE);
   auto twf = twiddles(fft_len, -1), twi = twiddles(fft_len, +1);
-  if (hipMemcpy(c->K.p, hK.data(), hK.size() * sizeof(double2), hipMemcpyHostToDevice) ||
-      hipMemcpy(c->S.p, hS.data(), hS.size() * sizeof(double2), hipMemcpyHostToDevice) ||
-      hipMemcpy(c->tw_f.p, twf.data(), twf.size() * sizeof(double2), hipMemcpyHostToDevice) ||
-      hipMemcpy(c->tw_i.p, twi.data(), twi.size() * sizeof(double2), hipMemcpyHostToDevice))
-    return fail(FASST_ERR_DEVICE);
+  if ((st = c->K.put(hK.data(), hK.size())) || (st = c->S.put(hS.data(), hS.size())) ||
+      (st = c->tw_f.put(twf.data(), twf.size())) || (st = c->tw_i.put(twi.data(), twi.size())))
+    return fail(st);
   if (lin_ft_len) {
     if ((st = c->ltw_f.alloc(lin_ft_len / 2)) || (st = c->ltw_i.alloc(lin_ft_len / 2)) ||
         (st = c->lwin.alloc(lin_ft_len)))
       return fail(st);
     auto lf = twiddles(lin_ft_len, -1), li = twiddles(lin_ft_len, +1);
-    if (hipMemcpy(c->ltw_f.p, lf.data(), lf.size() * sizeof(double2), hipMemcpyHostToDevice) ||
-        hipMemcpy(c->ltw_i.p, li.data(), li.size() * sizeof(double2), hipMemcpyHostToDevice) ||
-        hipMemcpy(c->lwin.p, lin_window, lin_ft_len * sizeof(double), hipMemcpyHostToDevice))
-      return fail(FASST_ERR_DEVICE);
+    if ((st = c->ltw_f.put(lf.data(), lf.size())) || (st = c->ltw_i.put(li.data(), li.size())) ||
+        (st = c->lwin.put(lin_window, lin_ft_len)))
+      return fail(st);
   }
   const int big = std::max(fft_len, lin_ft_len);
   if ((st = set_smem((const void *)k_cqt_frames, (size_t)fft_len * sizeof(double2))) ||
@@ -1109,16 +1106,15 @@ int cqt_forward(cqt_ctx *c, const double *x, long L, double *sp) {
   DeviceGuard dg(c->device);
   if ((st = ensure_work(c, g, L))) return st;
   hipStream_t s = c->stream;
-  FASST_HIP(hipMemsetAsync(c->xp.p, 0, g.Lp * sizeof(double), s));
-  FASST_HIP(hipMemcpyAsync(c->xp.p + g.maxBlock, x, L * sizeof(double), hipMemcpyHostToDevice, s));
+  FASST_TRY(c->xp.zero(g.Lp, s));
+  FASST_TRY(c->xp.at(g.maxBlock).put(x, L, s));
   FASST_HIP(hipEventRecord(c->ev[0], s));
   if ((st = forward_dev(c, g, s))) return st;
   k_cqt_transpose<<<dim3((g.F + 15) / 16, (g.W + 15) / 16), 256, 0, s>>>(c->sp.p, c->sph.p, g.W,
                                                                           g.F);
   FASST_LAUNCH_CHECK();
   FASST_HIP(hipEventRecord(c->ev[1], s));
-  FASST_HIP(hipMemcpyAsync(sp, c->sph.p, (size_t)g.W * g.F * sizeof(double2),
-                           hipMemcpyDeviceToHost, s));
+  FASST_TRY(c->sph.get(sp, (size_t)g.W * g.F, s));
   FASST_HIP(hipStreamSynchronize(s));
   FASST_HIP(hipEventElapsedTime(&c->ms_fwd, c->ev[0], c->ev[1]));
   return FASST_OK;
@@ -1132,16 +1128,15 @@ int cqt_inverse(cqt_ctx *c, const double *sp, long L, double *y) {
   DeviceGuard dg(c->device);
   if ((st = ensure_work(c, g, L))) return st;
   hipStream_t s = c->stream;
-  FASST_HIP(hipMemcpyAsync(c->sph.p, sp, (size_t)g.W * g.F * sizeof(double2),
-                           hipMemcpyHostToDevice, s));
+  FASST_TRY(c->sph.put(sp, (size_t)g.W * g.F, s));
   FASST_HIP(hipEventRecord(c->ev[2], s));
   k_cqt_transpose<<<dim3((g.W + 15) / 16, (g.F + 15) / 16), 256, 0, s>>>(c->sph.p, c->sp.p, g.F,
                                                                           g.W);
   FASST_LAUNCH_CHECK();
-  double *yout = nullptr;
+  DSpan<double> yout;
   if ((st = inverse_dev(c, g, L, nullptr, s, &yout))) return st;
   FASST_HIP(hipEventRecord(c->ev[3], s));
-  FASST_HIP(hipMemcpyAsync(y, yout, L * sizeof(double), hipMemcpyDeviceToHost, s));
+  FASST_TRY(yout.get(y, L, s));
   FASST_HIP(hipStreamSynchronize(s));
   FASST_HIP(hipEventElapsedTime(&c->ms_inv, c->ev[2], c->ev[3]));
   return FASST_OK;
@@ -1165,8 +1160,8 @@ int cqt_forward_cells(cqt_ctx *c, const double *x, long L, double *cells) {
   DeviceGuard dg(c->device);
   if ((st = ensure_work(c, g, L)) || (st = ensure_cells(c, g, L))) return st;
   hipStream_t s = c->stream;
-  FASST_HIP(hipMemsetAsync(c->xp.p, 0, g.Lp * sizeof(double), s));
-  FASST_HIP(hipMemcpyAsync(c->xp.p + g.maxBlock, x, L * sizeof(double), hipMemcpyHostToDevice, s));
+  FASST_TRY(c->xp.zero(g.Lp, s));
+  FASST_TRY(c->xp.at(g.maxBlock).put(x, L, s));
   FASST_HIP(hipEventRecord(c->ev[0], s));
   if (c->lin_N) {   // cellCQT['linear'] = stft(xpad[first_center:])[Kmax:, :W]  (minqt.py:1420-1435)
     const long off = (long)c->first_center - c->lin_N / 2;
@@ -1182,7 +1177,7 @@ int cqt_forward_cells(cqt_ctx *c, const double *x, long L, double *cells) {
   double *next = c->sa.p;
   for (int i = 0; i < c->oct; ++i) {
     const int nfr = g.nfr[i];
-    double2 *cell = c->cells.p + cell_offset(c, g, i);
+    const DSpan<double2> cell = c->cells.at(cell_offset(c, g, i), (size_t)c->M * nfr);
     if (c->nb > 0) {
       k_cqt_frames<<<nfr, 256, c->N * sizeof(double2), s>>>(cur, g.len[i], c->fft_hop, c->tw_f.p,
                                                            c->N, c->logN, c->kb, c->nb, c->nbp,
@@ -1190,10 +1185,10 @@ int cqt_forward_cells(cqt_ctx *c, const double *x, long L, double *cells) {
       FASST_LAUNCH_CHECK();
       k_cqt_band_cells<<<(nfr + kBandFrames - 1) / kBandFrames, 256,
                          kBandFrames * c->nbp * sizeof(double2), s>>>(c->K.p, c->XX.p, c->M, c->nb,
-                                                                      c->nbp, nfr, cell);
+                                                                      c->nbp, nfr, cell.p);
       FASST_LAUNCH_CHECK();
     } else {
-      FASST_HIP(hipMemsetAsync(cell, 0, (size_t)c->M * nfr * sizeof(double2), s));
+      FASST_TRY(cell.zero(cell.n, s));
     }
     // The reference's guard `i != self.octaveNr` (minqt.py:520) is always true,
     // so it also filters and decimates after the last octave; nothing reads
@@ -1205,8 +1200,7 @@ int cqt_forward_cells(cqt_ctx *c, const double *x, long L, double *cells) {
     }
   }
   FASST_HIP(hipEventRecord(c->ev[1], s));
-  FASST_HIP(hipMemcpyAsync(cells, c->cells.p, cells_total(c, g) * sizeof(double2),
-                           hipMemcpyDeviceToHost, s));
+  FASST_TRY(c->cells.get(cells, cells_total(c, g), s));
   FASST_HIP(hipStreamSynchronize(s));
   FASST_HIP(hipEventElapsedTime(&c->ms_fwd, c->ev[0], c->ev[1]));
   return FASST_OK;
@@ -1220,8 +1214,7 @@ int cqt_cells_to_raster(cqt_ctx *c, const double *cells, long L, double *sp) {
   DeviceGuard dg(c->device);
   if ((st = ensure_work(c, g, L)) || (st = ensure_cells(c, g, L))) return st;
   hipStream_t s = c->stream;
-  FASST_HIP(hipMemcpyAsync(c->cells.p, cells, cells_total(c, g) * sizeof(double2),
-                           hipMemcpyHostToDevice, s));
+  FASST_TRY(c->cells.put(cells, cells_total(c, g), s));
   FASST_HIP(hipEventRecord(c->ev[0], s));
   const int gx = (g.W + 255) / 256;
   for (int i = 0; i < c->oct; ++i) {   // every element of sp is written: no memset
@@ -1244,8 +1237,7 @@ int cqt_cells_to_raster(cqt_ctx *c, const double *cells, long L, double *sp) {
     FASST_LAUNCH_CHECK();
   }
   FASST_HIP(hipEventRecord(c->ev[1], s));
-  FASST_HIP(hipMemcpyAsync(sp, c->sph.p, (size_t)g.W * g.F * sizeof(double2),
-                           hipMemcpyDeviceToHost, s));
+  FASST_TRY(c->sph.get(sp, (size_t)g.W * g.F, s));
   FASST_HIP(hipStreamSynchronize(s));
   FASST_HIP(hipEventElapsedTime(&c->ms_rast, c->ev[0], c->ev[1]));
   return FASST_OK;
@@ -1259,8 +1251,7 @@ int cqt_raster_to_cells(cqt_ctx *c, const double *sp, long L, double *cells) {
   DeviceGuard dg(c->device);
   if ((st = ensure_work(c, g, L)) || (st = ensure_cells(c, g, L))) return st;
   hipStream_t s = c->stream;
-  FASST_HIP(hipMemcpyAsync(c->sph.p, sp, (size_t)g.W * g.F * sizeof(double2),
-                           hipMemcpyHostToDevice, s));
+  FASST_TRY(c->sph.put(sp, (size_t)g.W * g.F, s));
   FASST_HIP(hipEventRecord(c->ev[2], s));
   const double empty_hops = (double)c->first_center / (double)c->atom_hop;
   for (int i = 0; i < c->oct; ++i) {
@@ -1276,8 +1267,7 @@ int cqt_raster_to_cells(cqt_ctx *c, const double *sp, long L, double *cells) {
     FASST_LAUNCH_CHECK();
   }
   FASST_HIP(hipEventRecord(c->ev[3], s));
-  FASST_HIP(hipMemcpyAsync(cells, c->cells.p, cells_total(c, g) * sizeof(double2),
-                           hipMemcpyDeviceToHost, s));
+  FASST_TRY(c->cells.get(cells, cells_total(c, g), s));
   FASST_HIP(hipStreamSynchronize(s));
   FASST_HIP(hipEventElapsedTime(&c->ms_cell, c->ev[2], c->ev[3]));
   return FASST_OK;
@@ -1291,13 +1281,12 @@ int cqt_inverse_cells(cqt_ctx *c, const double *cells, long L, double *y) {
   DeviceGuard dg(c->device);
   if ((st = ensure_work(c, g, L)) || (st = ensure_cells(c, g, L))) return st;
   hipStream_t s = c->stream;
-  FASST_HIP(hipMemcpyAsync(c->cells.p, cells, cells_total(c, g) * sizeof(double2),
-                           hipMemcpyHostToDevice, s));
+  FASST_TRY(c->cells.put(cells, cells_total(c, g), s));
   FASST_HIP(hipEventRecord(c->ev[2], s));
-  double *yout = nullptr;
+  DSpan<double> yout;
   if ((st = inverse_dev(c, g, L, c->cells.p, s, &yout))) return st;
   FASST_HIP(hipEventRecord(c->ev[3], s));
-  FASST_HIP(hipMemcpyAsync(y, yout, L * sizeof(double), hipMemcpyDeviceToHost, s));
+  FASST_TRY(yout.get(y, L, s));
   FASST_HIP(hipStreamSynchronize(s));
   FASST_HIP(hipEventElapsedTime(&c->ms_inv, c->ev[2], c->ev[3]));
   return FASST_OK;
@@ -1342,10 +1331,9 @@ int dict_wf0_cqt(cqt_ctx *c, int n_cols, const double *f1, const double *f2,
   if ((st = damps.alloc((size_t)n_cols * max_partials)) || (st = keep.alloc(g.F)) ||
       (st = dim.alloc(L)) || (st = dout.alloc((size_t)g.F * n_cols)))
     return st;
-  FASST_HIP(hipMemcpy(damps.p, amps, (size_t)n_cols * max_partials * sizeof(double2),
-                      hipMemcpyHostToDevice));
+  FASST_TRY(damps.put(amps, (size_t)n_cols * max_partials));
   hipStream_t s = c->stream;
-  FASST_HIP(hipMemsetAsync(c->xp.p, 0, g.Lp * sizeof(double), s));   // the zero padding
+  FASST_TRY(c->xp.zero(g.Lp, s));   // the zero padding
   FASST_HIP(hipEventRecord(c->ev[0], s));
   const int ncq = c->bins * c->oct;
   const int gF = (g.F + 255) / 256;
@@ -1357,6 +1345,7 @@ int dict_wf0_cqt(cqt_ctx *c, int n_cols, const double *f1, const double *f2,
     if ((st = forward_dev(c, g, s))) return st;
     k_wf0_take<<<gF, 256, 0, s>>>(c->sp.p, g.F, col, ncq, 0, keep.p, dout.p, n_cols, j);
     FASST_LAUNCH_CHECK();
+    // (device to device: no DSpan)
     FASST_HIP(hipMemcpyAsync(c->xp.p + g.maxBlock, dim.p, L * sizeof(double),
                              hipMemcpyDeviceToDevice, s));
     if ((st = forward_dev(c, g, s))) return st;
@@ -1364,8 +1353,7 @@ int dict_wf0_cqt(cqt_ctx *c, int n_cols, const double *f1, const double *f2,
     FASST_LAUNCH_CHECK();
   }
   FASST_HIP(hipEventRecord(c->ev[1], s));
-  FASST_HIP(hipMemcpyAsync(wf0, dout.p, (size_t)g.F * n_cols * sizeof(double),
-                           hipMemcpyDeviceToHost, s));
+  FASST_TRY(dout.get(wf0, (size_t)g.F * n_cols, s));
   FASST_HIP(hipStreamSynchronize(s));
   FASST_HIP(hipEventElapsedTime(&c->ms_fwd, c->ev[0], c->ev[1]));
   return FASST_OK;
@@ -1423,10 +1411,9 @@ int cqt_forward_pair(cqt_ctx *c, hipStream_t s, const double *data, long L, doub
     chans[i] = data[(size_t)i * 2];
     chans[(size_t)L + i] = data[(size_t)i * 2 + 1];
   }
-  FASST_HIP(hipMemsetAsync(c->xp.p, 0, 2 * c->n_xp * sizeof(double), s));
+  FASST_TRY(c->xp.zero(2 * c->n_xp, s));
   for (int ch = 0; ch < 2; ++ch)
-    FASST_HIP(hipMemcpyAsync(c->xp.p + ch * c->n_xp + g.maxBlock, chans.data() + (size_t)ch * L,
-                             L * sizeof(double), hipMemcpyHostToDevice, s));
+    FASST_TRY(c->xp.at(ch * c->n_xp + g.maxBlock).put(chans.data() + (size_t)ch * L, L, s));
   FASST_HIP(hipStreamSynchronize(s));   // chans is read until here
   FASST_HIP(hipEventRecord(c->ev[0], s));
   if ((st = forward_dev(c, g, s, 2, X, ld, plane))) return st;
@@ -1446,11 +1433,10 @@ int cqt_inverse_batch(cqt_ctx *c, hipStream_t s, const CqtImages &im, int B, lon
   }
   if ((st = ensure_work(c, g, L, B))) return st;
   FASST_HIP(hipEventRecord(c->ev[2], s));
-  double *yout = nullptr;
+  DSpan<double> yout;
   if ((st = inverse_dev(c, g, L, nullptr, s, &yout, im, B))) return st;
   FASST_HIP(hipEventRecord(c->ev[3], s));
-  FASST_HIP(hipMemcpy2DAsync(y, L * sizeof(double), yout, c->n_y * sizeof(double),
-                             L * sizeof(double), B, hipMemcpyDeviceToHost, s));
+  FASST_TRY(yout.get_rows(y, B, L, L, c->n_y, s));
   FASST_HIP(hipStreamSynchronize(s));
   FASST_HIP(hipEventElapsedTime(&c->ms_inv, c->ev[2], c->ev[3]));
   return FASST_OK;

@@ -572,7 +572,7 @@ int demix_get_plane(demix_ctx *c, int which, double *out) {
     return FASST_ERR_SHAPE;
   }
   DeviceGuard g(c->device);
-  FASST_HIP(hipMemcpy(out, c->plane(which), c->n * sizeof(double), hipMemcpyDeviceToHost));
+  FASST_TRY(c->planes.at(which * c->n, c->n).get(out, c->n));
   ++g_dmx_transfers;
   return FASST_OK;
 }
@@ -584,44 +584,44 @@ int demix_set_plane(demix_ctx *c, int which, const double *in) {
     return FASST_ERR_SHAPE;
   }
   DeviceGuard g(c->device);
-  FASST_HIP(hipMemcpy(c->plane(which), in, c->n * sizeof(double), hipMemcpyHostToDevice));
+  FASST_TRY(c->planes.at(which * c->n, c->n).put(in, c->n));
   c->have_features = true;
   return FASST_OK;
 }
 
-static unsigned char *mask_ptr(demix_ctx *c, int slot, const char *fn) {
-  if (slot == DEMIX_MASK_SUBSET) return c->rem.p;
-  if (slot == DEMIX_MASK_CANDIDATES) return c->cand.p;
+// the n bytes of mask `slot`; p == nullptr (and the error set) for a bad slot
+static DSpan<unsigned char> mask_span(demix_ctx *c, int slot, const char *fn) {
+  if (slot == DEMIX_MASK_SUBSET) return c->rem.at(0, c->n);
+  if (slot == DEMIX_MASK_CANDIDATES) return c->cand.at(0, c->n);
   if (slot < 0 || slot >= c->maxc) {
     set_error("%s: mask %d outside 0 .. %d", fn, slot, c->maxc - 1);
-    return nullptr;
+    return {};
   }
-  return c->masks.p + (size_t)slot * c->n;
+  return c->masks.at((size_t)slot * c->n, c->n);
 }
 
 int demix_get_mask(demix_ctx *c, int slot, unsigned char *out) {
   if (!ctx_ok(c, "demix_get_mask", false)) return FASST_ERR_SHAPE;
-  unsigned char *p = mask_ptr(c, slot, "demix_get_mask");
-  if (!p || !out) return FASST_ERR_SHAPE;
+  const DSpan<unsigned char> m = mask_span(c, slot, "demix_get_mask");
+  if (!m.p || !out) return FASST_ERR_SHAPE;
   DeviceGuard g(c->device);
-  FASST_HIP(hipMemcpy(out, p, c->n, hipMemcpyDeviceToHost));
+  FASST_TRY(m.get(out, c->n));
   ++g_dmx_transfers;
   return FASST_OK;
 }
 
 int demix_set_mask(demix_ctx *c, int slot, const unsigned char *in) {
   if (!ctx_ok(c, "demix_set_mask", false)) return FASST_ERR_SHAPE;
-  unsigned char *p = mask_ptr(c, slot, "demix_set_mask");
-  if (!p || !in) return FASST_ERR_SHAPE;
+  const DSpan<unsigned char> m = mask_span(c, slot, "demix_set_mask");
+  if (!m.p || !in) return FASST_ERR_SHAPE;
   DeviceGuard g(c->device);
-  FASST_HIP(hipMemcpy(p, in, c->n, hipMemcpyHostToDevice));
-  return FASST_OK;
+  return m.put(in, c->n);
 }
 
 int demix_init_subset(demix_ctx *c) {
   if (!ctx_ok(c, "demix_init_subset", false)) return FASST_ERR_SHAPE;
   DeviceGuard g(c->device);
-  FASST_HIP(hipMemset(c->rem.p, 1, c->n));
+  FASST_HIP(hipMemset(c->rem.p, 1, c->n));   // (a fill with 1, not 0: no DSpan::zero)
   FASST_HIP(hipDeviceSynchronize());
   return FASST_OK;
 }
@@ -682,7 +682,7 @@ int demix_delta_pass(demix_ctx *c, int slot, double theta_c, const double *v1, d
   a.centroid = centroid;
   a.only_centroid = only_centroid;
   if (!only_centroid && (st = c->v1.put(v1, c->F))) return st;
-  FASST_HIP(hipMemset(c->cnt.p, 0, 2 * sizeof(unsigned long long)));
+  FASST_TRY(c->cnt.zero(2));
   if ((st = dmx_start(c->tm))) return st;
   k_delta_pass<<<(unsigned)((c->n + kDB - 1) / kDB), kDB>>>(a);
   if ((st = dmx_finish(c->tm, 1))) return st;

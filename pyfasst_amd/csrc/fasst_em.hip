@@ -4920,7 +4920,7 @@ static int multi_step(fasst_ctx *c, double omega, int b, int only_j) {
   }
   if (c->anytwc && b == 0)   // (a constrained source has one component: block 0)
     if (int st = launch_tw_constr(c, omega, true)) return st;
-  // the step's W = FB FW is the current W of the next step
+  // the step's W = FB FW is the current W of the next step (device to device: no DSpan)
   FASST_HIP(hipMemcpyAsync(c->Wkf.p, c->Wkf_new.p, (size_t)J * c->KP * c->Fp * sizeof(double),
                            hipMemcpyDeviceToDevice, c->stream));
   return FASST_OK;
@@ -5304,17 +5304,14 @@ int fasst_set_spatial(fasst_ctx *c, int j, const double *params, int free_) {
   const double2 *p = reinterpret_cast<const double2 *>(params);
   if (c->convm >> j & 1u) {
     // params [r][C][F] -> A[r][c][f] (row pitch Fp)
-    FASST_HIP(hipMemcpy2DAsync(c->A.p + (size_t)2 * r0 * c->Fp, c->Fp * sizeof(double2), p,
-                               c->F * sizeof(double2), c->F * sizeof(double2), (size_t)nr * 2,
-                               hipMemcpyHostToDevice, c->stream));
+    FASST_TRY(c->A.at((size_t)2 * r0 * c->Fp, (size_t)2 * nr * c->Fp)
+                  .put_rows(p, (size_t)nr * 2, c->F, c->F, c->Fp, c->stream));
   } else {
     // params [C][r] -> Pinst[r][c]
     std::vector<double2> tmp((size_t)nr * 2);
     for (int r = 0; r < nr; ++r)
       for (int ch = 0; ch < 2; ++ch) tmp[(size_t)r * 2 + ch] = p[(size_t)ch * nr + r];
-    FASST_HIP(hipMemcpyAsync(c->Pinst.p + 2 * r0, tmp.data(), tmp.size() * sizeof(double2),
-                             hipMemcpyHostToDevice, c->stream));
-    FASST_HIP(hipStreamSynchronize(c->stream));
+    FASST_TRY(c->Pinst.at(2 * r0, tmp.size()).put(tmp.data(), tmp.size(), c->stream));
   }
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
@@ -5327,14 +5324,12 @@ int fasst_get_spatial(fasst_ctx *c, int j, double *params) {
   const int r0 = c->roff[j], nr = c->rank[j];
   double2 *p = reinterpret_cast<double2 *>(params);
   if (c->convm >> j & 1u) {
-    FASST_HIP(hipMemcpy2DAsync(p, c->F * sizeof(double2), c->A.p + (size_t)2 * r0 * c->Fp,
-                               c->Fp * sizeof(double2), c->F * sizeof(double2), (size_t)nr * 2,
-                               hipMemcpyDeviceToHost, c->stream));
+    FASST_TRY(c->A.at((size_t)2 * r0 * c->Fp, (size_t)2 * nr * c->Fp)
+                  .get_rows(p, (size_t)nr * 2, c->F, c->F, c->Fp, c->stream));
     FASST_HIP(hipStreamSynchronize(c->stream));
   } else {
     std::vector<double2> tmp((size_t)nr * 2);
-    FASST_HIP(hipMemcpyAsync(tmp.data(), c->Pinst.p + 2 * r0, tmp.size() * sizeof(double2),
-                             hipMemcpyDeviceToHost, c->stream));
+    FASST_TRY(c->Pinst.at(2 * r0, tmp.size()).get(tmp.data(), tmp.size(), c->stream));
     FASST_HIP(hipStreamSynchronize(c->stream));
     for (int r = 0; r < nr; ++r)
       for (int ch = 0; ch < 2; ++ch) p[(size_t)ch * nr + r] = tmp[(size_t)r * 2 + ch];
@@ -5480,13 +5475,10 @@ int fasst_set_tb(fasst_ctx *c, int j, int b, int L, const double *TW, const doub
   if (c->tb[j][b].n < o.n) {
     if ((st = c->tb[j][b].alloc(o.n))) return st;
   } else {
-    FASST_HIP(hipMemsetAsync(c->tb[j][b].p, 0, o.n * sizeof(double), c->stream));
+    FASST_TRY(c->tb[j][b].zero(o.n, c->stream));
   }
-  FASST_HIP(hipMemcpyAsync(c->tb[j][b].p + o.tws, TW, (size_t)kbw * L * sizeof(double),
-                           hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpy2DAsync(c->tb[j][b].p + o.tb, c->Tp * sizeof(double), TB,
-                             c->T * sizeof(double), c->T * sizeof(double), L,
-                             hipMemcpyHostToDevice, c->stream));
+  FASST_TRY(c->tb[j][b].at(o.tws).put(TW, (size_t)kbw * L, c->stream));
+  FASST_TRY(c->tb[j][b].at(o.tb).put_rows(TB, L, c->T, c->T, c->Tp, c->stream));
   c->tbl[j][b] = L;
   c->btb[j][b] = tb_free ? 1 : 0;
   if (c->twc[j]) {   // time blobs and a discrete-state TW exclude each other (:1736-1742)
@@ -5512,12 +5504,8 @@ int fasst_get_tb(fasst_ctx *c, int j, int b, double *TW, double *TB) {
   const int kbw = c->kb[j][b + 1] - c->kb[j][b], L = c->tbl[j][b];
   const TBLayout o = tb_layout(kbw, L, c->Tp);
   if (TW)
-    FASST_HIP(hipMemcpyAsync(TW, c->tb[j][b].p + o.tws, (size_t)kbw * L * sizeof(double),
-                             hipMemcpyDeviceToHost, c->stream));
-  if (TB)
-    FASST_HIP(hipMemcpy2DAsync(TB, c->T * sizeof(double), c->tb[j][b].p + o.tb,
-                               c->Tp * sizeof(double), c->T * sizeof(double), L,
-                               hipMemcpyDeviceToHost, c->stream));
+    FASST_TRY(c->tb[j][b].at(o.tws).get(TW, (size_t)kbw * L, c->stream));
+  if (TB) FASST_TRY(c->tb[j][b].at(o.tb).get_rows(TB, L, c->T, c->T, c->Tp, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -5534,17 +5522,14 @@ int fasst_set_spectral(fasst_ctx *c, int j, const double *FB, const double *FW, 
     c->bfb[j][0] = c->fb_free[j];
     c->btw[j][0] = c->tw_free[j];
   }
-  FASST_HIP(hipMemsetAsync(c->FW.p + (size_t)j * KP * KP, 0, (size_t)KP * KP * sizeof(double),
-                           c->stream));
-  FASST_HIP(hipMemcpy2DAsync(c->FB.p + (size_t)j * c->Fp * KP, KP * sizeof(double), FB,
-                             K * sizeof(double), K * sizeof(double), c->F, hipMemcpyHostToDevice,
-                             c->stream));
-  FASST_HIP(hipMemcpy2DAsync(c->FW.p + (size_t)j * KP * KP, KP * sizeof(double), FW,
-                             K * sizeof(double), K * sizeof(double), K, hipMemcpyHostToDevice,
-                             c->stream));
-  FASST_HIP(hipMemcpy2DAsync(c->TW.p + (size_t)j * KP * c->Tp, c->Tp * sizeof(double), TW,
-                             c->T * sizeof(double), c->T * sizeof(double), K,
-                             hipMemcpyHostToDevice, c->stream));
+  // source j's rows of the padded images FB [Fp][KP], FW [KP][KP], TW [KP][Tp]
+  const DSpan<double> fb = c->FB.at((size_t)j * c->Fp * KP, (size_t)c->Fp * KP),
+                      fw = c->FW.at((size_t)j * KP * KP, (size_t)KP * KP),
+                      tw = c->TW.at((size_t)j * KP * c->Tp, (size_t)KP * c->Tp);
+  FASST_TRY(fw.zero(fw.n, c->stream));
+  FASST_TRY(fb.put_rows(FB, c->F, K, K, KP, c->stream));
+  FASST_TRY(fw.put_rows(FW, K, K, K, KP, c->stream));
+  FASST_TRY(tw.put_rows(TW, K, c->T, c->T, c->Tp, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -5555,17 +5540,13 @@ int fasst_get_spectral(fasst_ctx *c, int j, double *FB, double *FW, double *TW) 
   DeviceGuard g(c->device);
   const int K = c->K[j], KP = c->KP;
   if (FB)
-    FASST_HIP(hipMemcpy2DAsync(FB, K * sizeof(double), c->FB.p + (size_t)j * c->Fp * KP,
-                               KP * sizeof(double), K * sizeof(double), c->F,
-                               hipMemcpyDeviceToHost, c->stream));
+    FASST_TRY(c->FB.at((size_t)j * c->Fp * KP, (size_t)c->Fp * KP)
+                  .get_rows(FB, c->F, K, K, KP, c->stream));
   if (FW)
-    FASST_HIP(hipMemcpy2DAsync(FW, K * sizeof(double), c->FW.p + (size_t)j * KP * KP,
-                               KP * sizeof(double), K * sizeof(double), K, hipMemcpyDeviceToHost,
-                               c->stream));
+    FASST_TRY(c->FW.at((size_t)j * KP * KP, (size_t)KP * KP).get_rows(FW, K, K, K, KP, c->stream));
   if (TW)
-    FASST_HIP(hipMemcpy2DAsync(TW, c->T * sizeof(double), c->TW.p + (size_t)j * KP * c->Tp,
-                               c->Tp * sizeof(double), c->T * sizeof(double), K,
-                               hipMemcpyDeviceToHost, c->stream));
+    FASST_TRY(c->TW.at((size_t)j * KP * c->Tp, (size_t)KP * c->Tp)
+                  .get_rows(TW, K, c->T, c->T, c->Tp, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -5578,11 +5559,11 @@ int fasst_spectral_update(fasst_ctx *c, const double *hat_W, double omega) {
   const size_t n = (size_t)c->J * c->F * c->T;
   DBuf<double> dh;
   if ((st = dh.alloc_uninit(n))) return st;
-  FASST_HIP(hipMemcpyAsync(dh.p, hat_W, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemsetAsync(c->flags.p, 0, kNFlags * sizeof(int), c->stream));
+  FASST_TRY(dh.put(hat_W, n, c->stream));
+  FASST_TRY(c->flags.zero(kNFlags, c->stream));
   c->halt = nullptr;
   if ((st = launch_spectral_prep(c, false)) || (st = launch_w_old(c))) return st;
-  FASST_HIP(hipMemsetAsync(c->hatW.p, 0, (size_t)c->J * c->Tp * c->Fp * sizeof(double), c->stream));
+  FASST_TRY(c->hatW.zero((size_t)c->J * c->Tp * c->Fp, c->stream));
   k_rho_from_hatw<<<dim3((c->F + 63) / 64, (c->T + 3) / 4, c->J), 256, 0, c->stream>>>(
       dh.p, c->Wkf.p, c->TW.p, c->hatW.p, c->F, c->T, c->Fp, c->Tp, c->KP);
   FASST_LAUNCH_CHECK();
@@ -5595,12 +5576,11 @@ int fasst_renormalize(fasst_ctx *c, int *restart_mask) {
   int st = need_model(c, 0);
   if (st) return st;
   DeviceGuard g(c->device);
-  FASST_HIP(hipMemsetAsync(c->flags.p, 0, kNFlags * sizeof(int), c->stream));
+  FASST_TRY(c->flags.zero(kNFlags, c->stream));
   c->halt = nullptr;
   st = launch_renorm(c, 0);
   if (st) return st;
-  FASST_HIP(hipMemcpyAsync(c->h_flags, c->flags.p, kNFlags * sizeof(int),
-                           hipMemcpyDeviceToHost, c->stream));
+  FASST_TRY(c->flags.get(c->h_flags, kNFlags, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   int mask = 0;
   for (int sl = 0; sl < c->nslot; ++sl)
@@ -5626,10 +5606,9 @@ int fasst_run(fasst_ctx *c, int n_iter, const double *psd, double omega, double 
     if ((st = c->ll.alloc(n_iter))) return st;
     c->ll_cap = n_iter;
   }
-  FASST_HIP(hipMemsetAsync(c->psd.p, 0, (size_t)n_iter * c->Fp * sizeof(double), c->stream));
-  FASST_HIP(hipMemcpy2DAsync(c->psd.p, c->Fp * sizeof(double), psd, c->F * sizeof(double),
-                             c->F * sizeof(double), n_iter, hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemsetAsync(c->flags.p, 0, kNFlags * sizeof(int), c->stream));
+  FASST_TRY(c->psd.zero((size_t)n_iter * c->Fp, c->stream));
+  FASST_TRY(c->psd.at(0).put_rows(psd, n_iter, c->F, c->F, c->Fp, c->stream));
+  FASST_TRY(c->flags.zero(kNFlags, c->stream));
   // Without profiling the whole batch is enqueued at once: a flag raised in
   // iteration i halts every later kernel on the device (HALT_GUARD), and the
   // host reads the flags once at the end.  Profiling keeps one sync per
@@ -5646,8 +5625,7 @@ int fasst_run(fasst_ctx *c, int n_iter, const double *psd, double omega, double 
       return st;
     }
     if ((it + 1) % sync_every && it + 1 < n_iter) continue;
-    FASST_HIP(hipMemcpyAsync(c->h_flags, c->flags.p, kNFlags * sizeof(int),
-                             hipMemcpyDeviceToHost, c->stream));
+    FASST_TRY(c->flags.get(c->h_flags, kNFlags, c->stream));
     FASST_HIP(hipStreamSynchronize(c->stream));
     prof_collect(c);
     done = it + 1;
@@ -5670,7 +5648,7 @@ int fasst_run(fasst_ctx *c, int n_iter, const double *psd, double omega, double 
     if (c->h_flags[1 + sl]) mask |= 1 << sl;
   if (mask) done = c->h_flags[kFlagIter] + 1;
   if (iters_done) *iters_done = done;
-  FASST_HIP(hipMemcpy(logliks, c->ll.p, (size_t)done * sizeof(double), hipMemcpyDeviceToHost));
+  FASST_TRY(c->ll.get(logliks, done));
   if (mask) {
     if (restart_mask) *restart_mask = mask;
     return FASST_TW_RESTART;

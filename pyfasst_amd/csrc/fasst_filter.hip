@@ -264,8 +264,8 @@ static int filter_run(hipStream_t st, const double *dx, int L, int Min, int Mout
   const bool transpose = w_tv && w_layout == FILTER_W_NUMPY;
   if (transpose && (rc = dWt.alloc_uninit((size_t)MM * nwf * F))) return rc;
   const auto twf = twiddles(nfft, -1), twi = twiddles(nfft, +1);
-  FASST_HIP(hipMemcpyAsync(dtwf.p, twf.data(), twf.size() * sizeof(double2), hipMemcpyHostToDevice, st));
-  FASST_HIP(hipMemcpyAsync(dtwi.p, twi.data(), twi.size() * sizeof(double2), hipMemcpyHostToDevice, st));
+  FASST_TRY(dtwf.put(twf.data(), twf.size(), st));
+  FASST_TRY(dtwi.put(twi.data(), twi.size(), st));
   const bool timing = t_filter_timing;
   Events ev;   // start, after the transpose, end
   if (timing) {
@@ -365,15 +365,14 @@ int fasst_filter_stft(int device, const double *data, int L, int M_in, int M_out
   if ((rc = dx.alloc_uninit(nx)) || (rc = daw.alloc_uninit(wlen)) || (rc = dsw.alloc_uninit(wlen)) ||
       (rc = dy.alloc_uninit(ny)) || (rc = dW.alloc_uninit(nW)))
     return rc;
-  FASST_HIP(hipMemcpy(dx.p, data, nx * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(daw.p, awin, (size_t)wlen * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dsw.p, swin, (size_t)wlen * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dW.p, W, nW * sizeof(double2), hipMemcpyHostToDevice));
+  FASST_TRY(dx.put(data, nx));
+  FASST_TRY(daw.put(awin, wlen));
+  FASST_TRY(dsw.put(swin, wlen));
+  FASST_TRY(dW.put(W, nW));
   if ((rc = filter_run(nullptr, dx.p, L, M_in, M_out, dW.p, w_tv, n_w_frames, FILTER_W_NUMPY, daw.p,
                        dsw.p, wlen, nfft, hop, dy.p, s)))
     return rc;
-  FASST_HIP(hipMemcpy(y_out, dy.p, ny * sizeof(double), hipMemcpyDeviceToHost));
-  return FASST_OK;
+  return dy.get(y_out, ny);
 }
 
 int fasst_filter_set_timing(int on) {

@@ -232,23 +232,16 @@ struct GuardBuf {
     int st = d.alloc_uninit(sk + count + guard);
     if (st) return st;
     std::vector<unsigned long long> g(sk + guard, kGuardBits);
-    if (sk) FASST_HIP(hipMemcpy(d.p, g.data(), sk * sizeof(double), hipMemcpyHostToDevice));
-    FASST_HIP(hipMemcpy(d.p + sk + count, g.data(), guard * sizeof(double), hipMemcpyHostToDevice));
-    return FASST_OK;
+    FASST_TRY(d.at(0, sk).put(g.data(), sk));   // (the guard words are as wide as a double)
+    return d.at(sk + count, guard).put(g.data(), guard);
   }
-  int upload(const double *h) {
-    FASST_HIP(hipMemcpy(p(), h, n * sizeof(double), hipMemcpyHostToDevice));
-    return FASST_OK;
-  }
-  int download(double *h) const {
-    FASST_HIP(hipMemcpy(h, p(), n * sizeof(double), hipMemcpyDeviceToHost));
-    return FASST_OK;
-  }
+  int upload(const double *h) { return d.at(skew, n).put(h, n); }
+  int download(double *h) const { return d.at(skew, n).get(h, n); }
   // *ok &= every guard double still holds kGuardBits
   int intact(int *ok) const {
     std::vector<unsigned long long> g(skew + tail);
-    if (skew) FASST_HIP(hipMemcpy(g.data(), d.p, skew * sizeof(double), hipMemcpyDeviceToHost));
-    FASST_HIP(hipMemcpy(g.data() + skew, d.p + skew + n, tail * sizeof(double), hipMemcpyDeviceToHost));
+    FASST_TRY(d.at(0, skew).get(g.data(), skew));
+    FASST_TRY(d.at(skew + n, tail).get(g.data() + skew, tail));
     for (unsigned long long v : g)
       if (v != kGuardBits) *ok = 0;
     return FASST_OK;

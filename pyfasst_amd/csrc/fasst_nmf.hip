@@ -637,11 +637,11 @@ int wiener_images_dev(hipStream_t s, int F, int N, int K, const double *W, const
       (st = d.psd.alloc(F)) || (st = d.koff.alloc(J + 1)) || (st = d.Xh.alloc((size_t)F * N)) ||
       (st = d.X.alloc((size_t)d.Np * d.Fp)) || (st = d.S.alloc((size_t)J * d.Np * d.Fp)))
     return st;
-  FASST_HIP(hipMemcpyAsync(d.W.p, Wg.data(), Wg.size() * 8, hipMemcpyHostToDevice, s));
-  FASST_HIP(hipMemcpyAsync(d.H.p, Hg.data(), Hg.size() * 8, hipMemcpyHostToDevice, s));
-  FASST_HIP(hipMemcpyAsync(d.koff.p, koff.data(), koff.size() * sizeof(int), hipMemcpyHostToDevice, s));
-  if (psd) FASST_HIP(hipMemcpyAsync(d.psd.p, psd, (size_t)F * 8, hipMemcpyHostToDevice, s));
-  FASST_HIP(hipMemcpyAsync(d.Xh.p, X, (size_t)F * N * sizeof(double2), hipMemcpyHostToDevice, s));
+  FASST_TRY(d.W.put(Wg.data(), Wg.size(), s));
+  FASST_TRY(d.H.put(Hg.data(), Hg.size(), s));
+  FASST_TRY(d.koff.put(koff.data(), koff.size(), s));
+  if (psd) FASST_TRY(d.psd.put(psd, F, s));
+  FASST_TRY(d.Xh.put(X, (size_t)F * N, s));
   if ((st = tf_launch_ft_to_tf(s, d.Xh.p, d.X.p, F, N, d.Fp, d.Np, 1))) return st;
   const size_t smem = (size_t)(16 * (K + 1) + K * 64) * sizeof(double);
   if (smem > 64 * 1024)
@@ -825,7 +825,7 @@ int nmf_destroy(nmf_ctx *c) {
 int nmf_set_data(nmf_ctx *c, const double *SX) {
   if (!c || !SX) return FASST_ERR_SHAPE;
   DeviceGuard g(c->device);
-  FASST_HIP(hipMemcpyAsync(c->SX.p, SX, (size_t)c->F * c->N * 8, hipMemcpyHostToDevice, c->stream));
+  FASST_TRY(c->SX.put(SX, (size_t)c->F * c->N, c->stream));
   if (c->fused)  // frame-major copy: the W-update contraction reads 16 bins per row segment
     k_nmf_transpose<<<dim3((c->N + 15) / 16, (c->F + 15) / 16), 256, 0, c->stream>>>(
         c->SX.p, c->SXt.p, c->F, c->N);
@@ -836,8 +836,8 @@ int nmf_set_data(nmf_ctx *c, const double *SX) {
 int nmf_set_params(nmf_ctx *c, const double *W, const double *H) {
   if (!c || !W || !H) return FASST_ERR_SHAPE;
   DeviceGuard g(c->device);
-  FASST_HIP(hipMemcpyAsync(c->W.p, W, (size_t)c->F * c->K * 8, hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(c->H.p, H, (size_t)c->K * c->N * 8, hipMemcpyHostToDevice, c->stream));
+  FASST_TRY(c->W.put(W, (size_t)c->F * c->K, c->stream));
+  FASST_TRY(c->H.put(H, (size_t)c->K * c->N, c->stream));
   if (c->fused)
     k_nmf_transpose<<<dim3((c->N + 15) / 16, (c->K + 15) / 16), 256, 0, c->stream>>>(
         c->H.p, c->Ht.p, c->K, c->N);
@@ -867,8 +867,7 @@ int nmf_wiener_images(int device, int F, int N, int K, const double *W, const do
   DBuf<double2> hS;
   if (!st) st = hS.alloc((size_t)J * F * N);
   if (!st) st = tf_launch_tf_to_ft(s, d.S.p, hS.p, F, N, d.Fp, d.Np, J);
-  if (!st && hipMemcpyAsync(S, hS.p, hS.n * sizeof(double2), hipMemcpyDeviceToHost, s) != hipSuccess)
-    st = FASST_ERR_DEVICE;
+  if (!st) st = hS.get(S, hS.n, s);
   if (hipStreamSynchronize(s) != hipSuccess && !st) st = FASST_ERR_DEVICE;
   (void)hipStreamDestroy(s);
   return st;
@@ -894,16 +893,13 @@ int nmf_wiener_waveforms(int device, int F, int N, int K, const double *W, const
               (st = frames.alloc((size_t)N * wlen)) || (st = dy.alloc((size_t)J * len_out)))) {
   }
   auto tw = twiddles(nfft, +1);
-  if (!st && (hipMemcpyAsync(dw.p, window, (size_t)wlen * 8, hipMemcpyHostToDevice, s) ||
-              hipMemcpyAsync(daw.p, analysis_window ? analysis_window : window, (size_t)wlen * 8,
-                             hipMemcpyHostToDevice, s) ||
-              hipMemcpyAsync(dtw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice, s)))
-    st = FASST_ERR_DEVICE;
+  if (!st) st = dw.put(window, wlen, s);
+  if (!st) st = daw.put(analysis_window ? analysis_window : window, wlen, s);
+  if (!st) st = dtw.put(tw.data(), tw.size(), s);
   for (int n = 0; n < J && !st; ++n)
     st = tf_launch_istft(s, d.S.p + (size_t)n * d.Np * d.Fp, d.Fp, N, dw.p, daw.p, dtw.p, wlen,
                          nfft, hop, frames.p, dy.p + (size_t)n * len_out, len_out);
-  if (!st && hipMemcpyAsync(y, dy.p, dy.n * 8, hipMemcpyDeviceToHost, s) != hipSuccess)
-    st = FASST_ERR_DEVICE;
+  if (!st) st = dy.get(y, dy.n, s);
   if (hipStreamSynchronize(s) != hipSuccess && !st) st = FASST_ERR_DEVICE;
   (void)hipStreamDestroy(s);
   return st;
@@ -912,11 +908,11 @@ int nmf_wiener_waveforms(int device, int F, int N, int K, const double *W, const
 int nmf_get_params(nmf_ctx *c, double *W, double *H) {
   if (!c) return FASST_ERR_SHAPE;
   DeviceGuard g(c->device);
-  if (W) FASST_HIP(hipMemcpyAsync(W, c->W.p, (size_t)c->F * c->K * 8, hipMemcpyDeviceToHost, c->stream));
+  if (W) FASST_TRY(c->W.get(W, (size_t)c->F * c->K, c->stream));
   if (H && c->fused)
     k_nmf_transpose<<<dim3((c->K + 15) / 16, (c->N + 15) / 16), 256, 0, c->stream>>>(
         c->Ht.p, c->H.p, c->N, c->K);
-  if (H) FASST_HIP(hipMemcpyAsync(H, c->H.p, (size_t)c->K * c->N * 8, hipMemcpyDeviceToHost, c->stream));
+  if (H) FASST_TRY(c->H.get(H, (size_t)c->K * c->N, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }

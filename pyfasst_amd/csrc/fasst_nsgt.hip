@@ -497,7 +497,7 @@ int Tables::build(hipStream_t st) {
   }
   int e = tw.alloc_uninit(h_tw.size());
   if (e) return e;
-  FASST_HIP(hipMemcpy(tw.p, h_tw.data(), h_tw.size() * sizeof(double2), hipMemcpyHostToDevice));
+  FASST_TRY(tw.put(h_tw.data(), h_tw.size()));
   if ((e = dummy.alloc(1))) return e;
   if (want.empty()) return FASST_OK;
   std::sort(want.begin(), want.end(), [](const Shape &x, const Shape &y) {
@@ -535,9 +535,8 @@ int Tables::build(hipStream_t st) {
   }
   if ((e = chirp.alloc_uninit((size_t)nch_tot))) return e;
   if ((e = bhat.alloc((size_t)nbh_tot))) return e;   // zero-filled
-  FASST_HIP(hipMemcpy(chirp.p, h_ch.data(), h_ch.size() * sizeof(double2), hipMemcpyHostToDevice));
-  if (nbh_small)
-    FASST_HIP(hipMemcpy(bhat.p, h_bh.data(), h_bh.size() * sizeof(double2), hipMemcpyHostToDevice));
+  FASST_TRY(chirp.put(h_ch.data(), h_ch.size()));
+  FASST_TRY(bhat.put(h_bh.data(), h_bh.size()));
   // the large chirp spectra on the device, left in [k1][k2] order
   for (const Shape &s : want) {
     if (s.small) continue;
@@ -719,7 +718,7 @@ int upload_groups(std::vector<Group> &groups) {
     std::stable_sort(gr.h.begin(), gr.h.end(), [](const Job &x, const Job &y) { return x.P > y.P; });
     int e = gr.jobs.alloc_uninit(gr.h.size());
     if (e) return e;
-    FASST_HIP(hipMemcpy(gr.jobs.p, gr.h.data(), gr.h.size() * sizeof(Job), hipMemcpyHostToDevice));
+    FASST_TRY(gr.jobs.put(gr.h.data(), gr.h.size()));
   }
   return FASST_OK;
 }
@@ -759,8 +758,7 @@ Job single_job(const Tables &T, const Shape &s, int n_in, int n_out, double scal
 int upload_job(DBuf<Job> &d, const Job &j) {
   int e = d.alloc_uninit(1);
   if (e) return e;
-  FASST_HIP(hipMemcpy(d.p, &j, sizeof(Job), hipMemcpyHostToDevice));
-  return FASST_OK;
+  return d.put(&j, 1);
 }
 
 struct CallTimer {
@@ -939,18 +937,10 @@ int fasst_nsgt_plan_create(int device, int Ls, int nn, int nbands, const int *M,
       (e = p->terms.alloc_uninit(terms.size())) || (e = p->cov_ptr.alloc_uninit(cptr.size())) ||
       (e = p->cov.alloc_uninit(cov.size())))
     return fail(e);
-  hipError_t he = hipMemcpy(p->g.p, g, glen * sizeof(double), hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(p->gd.p, gd, glen * sizeof(double), hipMemcpyHostToDevice);
-  if (he == hipSuccess)
-    he = hipMemcpy(p->terms.p, terms.data(), terms.size() * sizeof(OlaTerm), hipMemcpyHostToDevice);
-  if (he == hipSuccess)
-    he = hipMemcpy(p->cov_ptr.p, cptr.data(), cptr.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (he == hipSuccess)
-    he = hipMemcpy(p->cov.p, cov.data(), cov.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (he != hipSuccess) {
-    set_error("nsgt_plan_create: copying the tables: %s", hipGetErrorString(he));
-    return fail(FASST_ERR_DEVICE);
-  }
+  if ((e = p->g.put(g, glen)) || (e = p->gd.put(gd, glen)) ||
+      (e = p->terms.put(terms.data(), terms.size())) ||
+      (e = p->cov_ptr.put(cptr.data(), cptr.size())) || (e = p->cov.put(cov.data(), cov.size())))
+    return fail(e);
   *plan = p;
   return FASST_OK;
 }
@@ -980,7 +970,7 @@ int fasst_nsgt_forward(void *plan, int nch, const double *x, int is_device, doub
   const double *dx = x;
   double *dc = coef;
   if (!is_device) {
-    FASST_HIP(hipMemcpy(p->sig_h.p, x, sizeof(double) * (size_t)nch * p->Ls, hipMemcpyHostToDevice));
+    FASST_TRY(p->sig_h.put(x, (size_t)nch * p->Ls));
     dx = p->sig_h.p;
     dc = (double *)p->coef_h.p;
   }
@@ -1004,9 +994,7 @@ int fasst_nsgt_forward(void *plan, int nch, const double *x, int is_device, doub
   if ((e = run_groups(st, p, p->fwd, +1, nch, bio))) return e;
   if ((e = tm.finish(st, true))) return e;
   FASST_HIP(hipStreamSynchronize(st));
-  if (!is_device)
-    FASST_HIP(hipMemcpy(coef, dc, sizeof(double2) * (size_t)nch * p->coef_len,
-                        hipMemcpyDeviceToHost));
+  if (!is_device) FASST_TRY(p->coef_h.get(coef, (size_t)nch * p->coef_len));
   return FASST_OK;
 }
 
@@ -1020,10 +1008,10 @@ int fasst_nsgt_backward(void *plan, int nch, const double *coef, int is_device, 
   if (e) return e;
   const double *dc = coef;
   double *dy = y;
-  const size_t ybytes = (p->real ? sizeof(double) : sizeof(double2)) * (size_t)nch * p->Ls;
+  // y_h holds doubles: a complex output is two of them per sample
+  const size_t ny = (p->real ? 1 : 2) * (size_t)nch * p->Ls;
   if (!is_device) {
-    FASST_HIP(hipMemcpy(p->coef_h.p, coef, sizeof(double2) * (size_t)nch * p->coef_len,
-                        hipMemcpyHostToDevice));
+    FASST_TRY(p->coef_h.put(coef, (size_t)nch * p->coef_len));
     dc = (const double *)p->coef_h.p;
     dy = p->y_h.p;
   }
@@ -1059,7 +1047,7 @@ int fasst_nsgt_backward(void *plan, int nch, const double *coef, int is_device, 
   if ((e = run_batch(st, p->T, p->sh_nn, p->job_nn.p, 1, +1, nch, io, p->W.p))) return e;
   if ((e = tm.finish(st, false))) return e;
   FASST_HIP(hipStreamSynchronize(st));
-  if (!is_device) FASST_HIP(hipMemcpy(y, dy, ybytes, hipMemcpyDeviceToHost));
+  if (!is_device) FASST_TRY(p->y_h.get(y, ny));
   return FASST_OK;
 }
 
@@ -1081,14 +1069,13 @@ int fasst_nsgt_fft(int device, int n, int sign, const double *in, double *out) {
   if ((e = din.alloc_uninit(n)) || (e = dout.alloc_uninit(n)) ||
       (e = W.alloc_uninit(s.small ? 1 : s.P)))
     return e;
-  FASST_HIP(hipMemcpy(din.p, in, sizeof(double2) * (size_t)n, hipMemcpyHostToDevice));
+  FASST_TRY(din.put(in, n));
   Io io;
   io.in = (const double *)din.p;
   io.out = (double *)dout.p;
   if ((e = run_batch(st, T, s, job.p, 1, sign, 1, io, W.p))) return e;
   FASST_HIP(hipStreamSynchronize(st));
-  FASST_HIP(hipMemcpy(out, dout.p, sizeof(double2) * (size_t)n, hipMemcpyDeviceToHost));
-  return FASST_OK;
+  return dout.get(out, n);
 }
 
 int fasst_nsgt_launch_count(long *count) {

@@ -967,10 +967,8 @@ int fasst_sf_set_spatial(fasst_ctx *c, int j, const double *params, int free_) {
   }
   m->spat_free[j] = free_ ? 1 : 0;
   std::vector<int> kind(nr, free_ ? (m->conv[j] ? 2 : 1) : 0);
-  FASST_HIP(hipMemcpy(m->mix.p + (size_t)r0 * 2 * F, h.data(), h.size() * sizeof(double2),
-                      hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(m->kind.p + r0, kind.data(), nr * sizeof(int), hipMemcpyHostToDevice));
-  return FASST_OK;
+  FASST_TRY(m->mix.at((size_t)r0 * 2 * F, h.size()).put(h.data(), h.size()));
+  return m->kind.at(r0, nr).put(kind.data(), nr);
 }
 
 int fasst_sf_get_spatial(fasst_ctx *c, int j, double *params) {
@@ -982,8 +980,7 @@ int fasst_sf_get_spatial(fasst_ctx *c, int j, double *params) {
   const int F = c->F, r0 = m->roff[j], nr = m->rank[j];
   std::vector<double2> h((size_t)nr * 2 * F);
   FASST_HIP(hipStreamSynchronize(c->stream));
-  FASST_HIP(hipMemcpy(h.data(), m->mix.p + (size_t)r0 * 2 * F, h.size() * sizeof(double2),
-                      hipMemcpyDeviceToHost));
+  FASST_TRY(m->mix.at((size_t)r0 * 2 * F, h.size()).get(h.data(), h.size()));
   double2 *p = (double2 *)params;
   if (m->conv[j]) {
     std::copy(h.begin(), h.end(), p);
@@ -1001,9 +998,12 @@ int fasst_set_factors(fasst_ctx *c, int j, int i, const double *FB, const double
   SfFactor &x = c->sf->fac[j][i];
   DeviceGuard g(c->device);
   FASST_HIP(hipStreamSynchronize(c->stream));
-  FASST_HIP(hipMemcpy(x.fb, FB, (size_t)c->F * x.Kb * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(x.fw, FW, (size_t)x.Kb * x.Kw * sizeof(double), hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(x.tw, TW, (size_t)x.Kw * c->T * sizeof(double), hipMemcpyHostToDevice));
+  // x.fb / x.fw / x.tw may be another factor's buffers, of these shapes (fasst_sf_configure)
+  const DSpan<double> fb{x.fb, (size_t)c->F * x.Kb}, fw{x.fw, (size_t)x.Kb * x.Kw},
+      tw{x.tw, (size_t)x.Kw * c->T};
+  FASST_TRY(fb.put(FB, fb.n));
+  FASST_TRY(fw.put(FW, fw.n));
+  FASST_TRY(tw.put(TW, tw.n));
   if (x.cand) {   // wide: every entry finite and nothing off the diagonal
     bool diag = true;
     for (int b = 0; b < x.Kb && diag; ++b)
@@ -1029,9 +1029,11 @@ int fasst_get_factors(fasst_ctx *c, int j, int i, double *FB, double *FW, double
   SfFactor &x = c->sf->fac[j][i];
   DeviceGuard g(c->device);
   FASST_HIP(hipStreamSynchronize(c->stream));
-  if (FB) FASST_HIP(hipMemcpy(FB, x.fb, (size_t)c->F * x.Kb * sizeof(double), hipMemcpyDeviceToHost));
-  if (FW) FASST_HIP(hipMemcpy(FW, x.fw, (size_t)x.Kb * x.Kw * sizeof(double), hipMemcpyDeviceToHost));
-  if (TW) FASST_HIP(hipMemcpy(TW, x.tw, (size_t)x.Kw * c->T * sizeof(double), hipMemcpyDeviceToHost));
+  const DSpan<double> fb{x.fb, (size_t)c->F * x.Kb}, fw{x.fw, (size_t)x.Kb * x.Kw},
+      tw{x.tw, (size_t)x.Kw * c->T};
+  if (FB) FASST_TRY(fb.get(FB, fb.n));
+  if (FW) FASST_TRY(fw.get(FW, fw.n));
+  if (TW) FASST_TRY(tw.get(TW, tw.n));
   return FASST_OK;
 }
 
@@ -1039,7 +1041,7 @@ int fasst_sf_renormalize(fasst_ctx *c, int *restart_mask) {
   int st = need_sf(c, 0);
   if (st) return st;
   DeviceGuard g(c->device);
-  FASST_HIP(hipMemsetAsync(c->sf->flags.p, 0, (1 + 2 * kMaxJ) * sizeof(int), c->stream));
+  FASST_TRY(c->sf->flags.zero(1 + 2 * kMaxJ, c->stream));
   if ((st = sf_renormalize(c))) return st;
   int mask = 0;
   if ((st = sf_flags_mask(c, &mask))) return st;
@@ -1069,7 +1071,7 @@ static int sf_run(fasst_ctx *c, int n_iter, const double *psd, double omega, con
     m->psd_cap = n_iter;
   }
   FASST_TRY(m->psd.put(psd, (size_t)n_iter * c->F, c->stream));
-  FASST_HIP(hipMemsetAsync(m->flags.p, 0, (1 + 2 * kMaxJ) * sizeof(int), c->stream));
+  FASST_TRY(m->flags.zero(1 + 2 * kMaxJ, c->stream));
   int nconv = 0;
   for (int j = 0; j < m->J; ++j)
     if (m->conv[j] && m->spat_free[j]) nconv += m->rank[j];
@@ -1185,11 +1187,10 @@ int fasst_sf_separate_waveforms(fasst_ctx *c, const double *psd, int nsrc, const
       (st = dy.alloc((size_t)nsrc * 2 * len_out)))
     return st;
   auto tw = twiddles(nfft, +1);
-  FASST_HIP(hipMemcpyAsync(dpsd.p, psd, c->F * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(dw.p, window, (size_t)wlen * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(daw.p, analysis_window ? analysis_window : window, (size_t)wlen * sizeof(double),
-                           hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(dtw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+  FASST_TRY(dpsd.put(psd, c->F, c->stream));
+  FASST_TRY(dw.put(window, wlen, c->stream));
+  FASST_TRY(daw.put(analysis_window ? analysis_window : window, wlen, c->stream));
+  FASST_TRY(dtw.put(tw.data(), tw.size(), c->stream));
   if ((st = sf_all_powers(c))) return st;
   // images frame-major [Tp][Fp], the layout the device iSTFT reads
   if ((st = sf_launch_wiener(c, dpsd.p, nsrc, src_of, dS.p, plane, 1, (size_t)c->Fp))) return st;

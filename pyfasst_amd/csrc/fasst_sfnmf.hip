@@ -437,8 +437,7 @@ int sfnmf_destroy(sfnmf_ctx *c) {
 int sfnmf_set_data(sfnmf_ctx *c, const double *SX) {
   if (!c || !SX) return FASST_ERR_SHAPE;
   DeviceGuard g(c->device);
-  FASST_HIP(hipMemcpy2DAsync(c->SX.p, (size_t)c->pN * 8, SX, (size_t)c->N * 8, (size_t)c->N * 8,
-                             c->F, hipMemcpyHostToDevice, c->stream));
+  FASST_TRY(c->SX.at(0).put_rows(SX, c->F, c->N, c->N, c->pN, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -450,10 +449,8 @@ int sfnmf_set_params(sfnmf_ctx *c, const double *W, const double *H, const doubl
   const double *Ws[3] = {W, WFilt, Wres}, *Hs[3] = {H, HFilt, Hres};
   for (int i = 0; i < 3; ++i) {
     SfFactor &f = c->fac[i];
-    FASST_HIP(hipMemcpy2DAsync(f.W.p, (size_t)f.pK * 8, Ws[i], (size_t)f.K * 8, (size_t)f.K * 8,
-                               c->F, hipMemcpyHostToDevice, c->stream));
-    FASST_HIP(hipMemcpy2DAsync(f.H.p, (size_t)c->pN * 8, Hs[i], (size_t)c->N * 8,
-                               (size_t)c->N * 8, f.K, hipMemcpyHostToDevice, c->stream));
+    FASST_TRY(f.W.at(0).put_rows(Ws[i], c->F, f.K, f.K, f.pK, c->stream));
+    FASST_TRY(f.H.at(0).put_rows(Hs[i], f.K, c->N, c->N, c->pN, c->stream));
     f.wt_ok = f.ht_ok = false;
     c->valid[i] = false;
   }
@@ -480,12 +477,8 @@ int sfnmf_get_params(sfnmf_ctx *c, double *W, double *H, double *WFilt, double *
   double *Ws[3] = {W, WFilt, Wres}, *Hs[3] = {H, HFilt, Hres};
   for (int i = 0; i < 3; ++i) {
     SfFactor &f = c->fac[i];
-    if (Ws[i])
-      FASST_HIP(hipMemcpy2DAsync(Ws[i], (size_t)f.K * 8, f.W.p, (size_t)f.pK * 8, (size_t)f.K * 8,
-                                 c->F, hipMemcpyDeviceToHost, c->stream));
-    if (Hs[i])
-      FASST_HIP(hipMemcpy2DAsync(Hs[i], (size_t)c->N * 8, f.H.p, (size_t)c->pN * 8,
-                                 (size_t)c->N * 8, f.K, hipMemcpyDeviceToHost, c->stream));
+    if (Ws[i]) FASST_TRY(f.W.at(0).get_rows(Ws[i], c->F, f.K, f.K, f.pK, c->stream));
+    if (Hs[i]) FASST_TRY(f.H.at(0).get_rows(Hs[i], f.K, c->N, c->N, c->pN, c->stream));
   }
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;

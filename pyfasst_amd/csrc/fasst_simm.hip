@@ -1543,18 +1543,15 @@ int simm_set_data(simm_ctx *c, const double *SXR, const double *SXL, const doubl
   if (!c || !WF0 || !WGAMMA) return FASST_ERR_SHAPE;
   DeviceGuard g(c->device);
   const size_t FN = (size_t)c->F * c->N;
-  if (SXR) FASST_HIP(hipMemcpyAsync(c->SXR.p, SXR, FN * 8, hipMemcpyHostToDevice, c->stream));
-  if (c->stereo && SXL)
-    FASST_HIP(hipMemcpyAsync(c->SXL.p, SXL, FN * 8, hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(c->WF0.p, WF0, (size_t)c->F * c->NF0 * 8, hipMemcpyHostToDevice, c->stream));
+  if (SXR) FASST_TRY(c->SXR.put(SXR, FN, c->stream));
+  if (c->stereo && SXL) FASST_TRY(c->SXL.put(SXL, FN, c->stream));
+  FASST_TRY(c->WF0.put(WF0, (size_t)c->F * c->NF0, c->stream));
   // the k-major operands of k_dgemm2: WF0 with an even row pitch, and WF0^T
-  FASST_HIP(hipMemcpy2DAsync(c->WF0K.p, (size_t)c->NF0p * 8, WF0, (size_t)c->NF0 * 8,
-                             (size_t)c->NF0 * 8, c->F, hipMemcpyHostToDevice, c->stream));
+  FASST_TRY(c->WF0K.at(0).put_rows(WF0, c->F, c->NF0, c->NF0, c->NF0p, c->stream));
   k_simm_transpose<<<dim3((c->NF0 + 15) / 16, (c->F + 15) / 16), 256, 0, c->stream>>>(
       c->WF0.p, c->WF0T.p, c->F, c->NF0, c->NF0, c->Fp);
   FASST_LAUNCH_CHECK();
-  FASST_HIP(hipMemcpyAsync(c->WGAMMA.p, WGAMMA, (size_t)c->F * c->P * 8, hipMemcpyHostToDevice,
-                           c->stream));
+  FASST_TRY(c->WGAMMA.put(WGAMMA, (size_t)c->F * c->P, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -1565,17 +1562,17 @@ int simm_set_params(simm_ctx *c, const double *HGAMMA, const double *HPHI, const
   if (!c || !HGAMMA || !HPHI || !HF0 || !HM || !WM) return FASST_ERR_SHAPE;
   DeviceGuard g(c->device);
   const int F = c->F, N = c->N, K = c->K, R = c->R;
-  FASST_HIP(hipMemcpyAsync(c->HGAMMA.p, HGAMMA, (size_t)c->P * K * 8, hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(c->HPHI.p, HPHI, (size_t)K * N * 8, hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(c->HF0.p, HF0, (size_t)c->NF0 * N * 8, hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(c->HM.p, HM, (size_t)R * N * 8, hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(c->WM.p, WM, (size_t)F * R * 8, hipMemcpyHostToDevice, c->stream));
+  FASST_TRY(c->HGAMMA.put(HGAMMA, (size_t)c->P * K, c->stream));
+  FASST_TRY(c->HPHI.put(HPHI, (size_t)K * N, c->stream));
+  FASST_TRY(c->HF0.put(HF0, (size_t)c->NF0 * N, c->stream));
+  FASST_TRY(c->HM.put(HM, (size_t)R * N, c->stream));
+  FASST_TRY(c->WM.put(WM, (size_t)F * R, c->stream));
   if (c->stereo) {
     std::vector<double> bl(R);
     for (int r = 0; r < R; ++r) bl[r] = betaL ? betaL[r] : 1 - betaR[r];  // (:576)
-    FASST_HIP(hipMemcpyAsync(c->alpha.p, alpha, 2 * 8, hipMemcpyHostToDevice, c->stream));
-    FASST_HIP(hipMemcpyAsync(c->bR.p, betaR, R * 8, hipMemcpyHostToDevice, c->stream));
-    FASST_HIP(hipMemcpyAsync(c->bL.p, bl.data(), R * 8, hipMemcpyHostToDevice, c->stream));
+    FASST_TRY(c->alpha.put(alpha, 2, c->stream));
+    FASST_TRY(c->bR.put(betaR, R, c->stream));
+    FASST_TRY(c->bL.put(bl.data(), R, c->stream));
     FASST_HIP(hipStreamSynchronize(c->stream));
   }
   return rebuild_model(c);
@@ -1593,9 +1590,7 @@ int simm_run(simm_ctx *c, int n_iter, double omega, int update_hgamma, double *r
                             reco_err ? c->reco.p + 2 * it : nullptr);
     if (st) return st;
   }
-  if (reco_err && n_iter > 0)
-    FASST_HIP(hipMemcpyAsync(reco_err, c->reco.p, (size_t)2 * n_iter * 8, hipMemcpyDeviceToHost,
-                             c->stream));
+  if (reco_err && n_iter > 0) FASST_TRY(c->reco.get(reco_err, (size_t)2 * n_iter, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -1609,7 +1604,7 @@ int simm_reco_error(simm_ctx *c, double *out) {
   }
   reco_error(c, c->reco.p);
   FASST_LAUNCH_CHECK();
-  FASST_HIP(hipMemcpyAsync(out, c->reco.p, 8, hipMemcpyDeviceToHost, c->stream));
+  FASST_TRY(c->reco.get(out, 1, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -1626,15 +1621,14 @@ int simm_separate(simm_ctx *c, const double *XR, const double *XL, double *VR, d
     if ((st = b.alloc(FN))) return st;
   for (auto &b : dout)
     if ((st = b.alloc(FN))) return st;
-  FASST_HIP(hipMemcpyAsync(dx[0].p, XR, FN * 16, hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(dx[1].p, XL, FN * 16, hipMemcpyHostToDevice, c->stream));
+  FASST_TRY(dx[0].put(XR, FN, c->stream));
+  FASST_TRY(dx[1].put(XL, FN, c->stream));
   k_lead_masks<<<egrid(FN), 256, 0, c->stream>>>(c->SF0.p, c->SPHI.p, c->SMR.p, c->SML.p,
                                                   c->alpha.p, dx[0].p, dx[1].p, dout[0].p,
                                                   dout[1].p, dout[2].p, dout[3].p, FN);
   FASST_LAUNCH_CHECK();
   double *outs[4] = {VR, VL, MR, ML};
-  for (int q = 0; q < 4; ++q)
-    FASST_HIP(hipMemcpyAsync(outs[q], dout[q].p, FN * 16, hipMemcpyDeviceToHost, c->stream));
+  for (int q = 0; q < 4; ++q) FASST_TRY(dout[q].get(outs[q], FN, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -1644,15 +1638,15 @@ int simm_get_params(simm_ctx *c, double *HGAMMA, double *HPHI, double *HF0, doub
   if (!c) return FASST_ERR_SHAPE;
   DeviceGuard g(c->device);
   const int N = c->N, K = c->K, R = c->R;
-  if (HGAMMA) FASST_HIP(hipMemcpyAsync(HGAMMA, c->HGAMMA.p, (size_t)c->P * K * 8, hipMemcpyDeviceToHost, c->stream));
-  if (HPHI) FASST_HIP(hipMemcpyAsync(HPHI, c->HPHI.p, (size_t)K * N * 8, hipMemcpyDeviceToHost, c->stream));
-  if (HF0) FASST_HIP(hipMemcpyAsync(HF0, c->HF0.p, (size_t)c->NF0 * N * 8, hipMemcpyDeviceToHost, c->stream));
-  if (HM) FASST_HIP(hipMemcpyAsync(HM, c->HM.p, (size_t)R * N * 8, hipMemcpyDeviceToHost, c->stream));
-  if (WM) FASST_HIP(hipMemcpyAsync(WM, c->WM.p, (size_t)c->F * R * 8, hipMemcpyDeviceToHost, c->stream));
+  if (HGAMMA) FASST_TRY(c->HGAMMA.get(HGAMMA, (size_t)c->P * K, c->stream));
+  if (HPHI) FASST_TRY(c->HPHI.get(HPHI, (size_t)K * N, c->stream));
+  if (HF0) FASST_TRY(c->HF0.get(HF0, (size_t)c->NF0 * N, c->stream));
+  if (HM) FASST_TRY(c->HM.get(HM, (size_t)R * N, c->stream));
+  if (WM) FASST_TRY(c->WM.get(WM, (size_t)c->F * R, c->stream));
   if (c->stereo) {
-    if (alpha) FASST_HIP(hipMemcpyAsync(alpha, c->alpha.p, 2 * 8, hipMemcpyDeviceToHost, c->stream));
-    if (betaR) FASST_HIP(hipMemcpyAsync(betaR, c->bR.p, R * 8, hipMemcpyDeviceToHost, c->stream));
-    if (betaL) FASST_HIP(hipMemcpyAsync(betaL, c->bL.p, R * 8, hipMemcpyDeviceToHost, c->stream));
+    if (alpha) FASST_TRY(c->alpha.get(alpha, 2, c->stream));
+    if (betaR) FASST_TRY(c->bR.get(betaR, R, c->stream));
+    if (betaL) FASST_TRY(c->bL.get(betaL, R, c->stream));
   }
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;

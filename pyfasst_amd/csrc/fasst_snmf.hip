@@ -535,9 +535,9 @@ int snmf_destroy(snmf_ctx *c) {
 int snmf_set_data(snmf_ctx *c, const double *SXR, const double *SXL) {
   if (!c || !SXR || !SXL) return FASST_ERR_SHAPE;
   DeviceGuard g(c->device);
-  const size_t bytes = (size_t)c->F * c->N * 8;
-  FASST_HIP(hipMemcpyAsync(c->SXR.p, SXR, bytes, hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(c->SXL.p, SXL, bytes, hipMemcpyHostToDevice, c->stream));
+  const size_t FN = (size_t)c->F * c->N;
+  FASST_TRY(c->SXR.put(SXR, FN, c->stream));
+  FASST_TRY(c->SXL.put(SXL, FN, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -560,10 +560,10 @@ int snmf_set_params(snmf_ctx *c, const double *WM, const double *HM, const doubl
     b2[r] = b[r] * b[r];
     b2[Rp + r] = b[Rp + r] * b[Rp + r];
   }
-  FASST_HIP(hipMemcpyAsync(c->W.p, w.data(), w.size() * 8, hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(c->Ht.p, ht.data(), ht.size() * 8, hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(c->beta.p, b.data(), b.size() * 8, hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemcpyAsync(c->b2.p, b2.data(), b2.size() * 8, hipMemcpyHostToDevice, c->stream));
+  FASST_TRY(c->W.put(w.data(), w.size(), c->stream));
+  FASST_TRY(c->Ht.put(ht.data(), ht.size(), c->stream));
+  FASST_TRY(c->beta.put(b.data(), b.size(), c->stream));
+  FASST_TRY(c->b2.put(b2.data(), b2.size(), c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -594,9 +594,7 @@ int snmf_run(snmf_ctx *c, int n_iter, double omega, double *reco_err) {
     FASST_LAUNCH_CHECK();
     if (reco_err && (st = snmf_error(c, slot++))) return st;
   }
-  if (reco_err)
-    FASST_HIP(hipMemcpyAsync(reco_err, c->err.p, ((size_t)3 * n_iter + 1) * 8,
-                             hipMemcpyDeviceToHost, c->stream));
+  if (reco_err) FASST_TRY(c->err.get(reco_err, (size_t)3 * n_iter + 1, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -606,9 +604,9 @@ int snmf_get_params(snmf_ctx *c, double *WM, double *HM, double *betaR, double *
   DeviceGuard g(c->device);
   const int F = c->F, N = c->N, R = c->R, Rp = c->Rp;
   std::vector<double> w((size_t)c->Fa * Rp), ht((size_t)c->Na * Rp), b(2 * Rp);
-  FASST_HIP(hipMemcpyAsync(w.data(), c->W.p, w.size() * 8, hipMemcpyDeviceToHost, c->stream));
-  FASST_HIP(hipMemcpyAsync(ht.data(), c->Ht.p, ht.size() * 8, hipMemcpyDeviceToHost, c->stream));
-  FASST_HIP(hipMemcpyAsync(b.data(), c->beta.p, b.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  FASST_TRY(c->W.get(w.data(), w.size(), c->stream));
+  FASST_TRY(c->Ht.get(ht.data(), ht.size(), c->stream));
+  FASST_TRY(c->beta.get(b.data(), b.size(), c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   if (WM)
     for (int f = 0; f < F; ++f)

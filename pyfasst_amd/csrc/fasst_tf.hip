@@ -852,7 +852,7 @@ int fasst_set_audio(fasst_ctx *c, const double *data, int L, const double *windo
       (st = dw.upload(window, wlen, c->stream)) ||
       (st = dtw.upload(tw.data(), tw.size(), c->stream)))
     return st;
-  FASST_HIP(hipMemsetAsync(c->X.p, 0, c->X.n * sizeof(double2), c->stream));
+  FASST_TRY(c->X.zero(c->X.n, c->stream));
   k_stft_frames<<<dim3(T, 2), 256, nfft * sizeof(double2), c->stream>>>(
       dx.p, L, dw.p, wlen, dtw.p, nfft, ilog2(nfft), hop, c->X.p, c->Fp, (size_t)c->Tp * c->Fp);
   FASST_LAUNCH_CHECK();
@@ -1112,9 +1112,7 @@ int fasst_spatial_filter_gains(fasst_ctx *c, double *WG) {
   DBuf<int> droff;
   DBuf<double2> G;
   if ((st = spatial_gains(c, droff, G))) return st;
-  FASST_HIP(hipMemcpy2DAsync(WG, c->F * sizeof(double2), G.p, c->Fp * sizeof(double2),
-                             c->F * sizeof(double2), (size_t)c->J * 4, hipMemcpyDeviceToHost,
-                             c->stream));
+  FASST_TRY(G.at(0).get_rows(WG, (size_t)c->J * 4, c->F, c->F, c->Fp, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -1260,7 +1258,7 @@ int fasst_set_audio_cqt(fasst_ctx *c, cqt_ctx *q, const double *data, long L) {
   // the observation is replaced: not valid again before the transform is in
   c->have_X = false;
   c->cx_ready = false;
-  FASST_HIP(hipMemsetAsync(c->X.p, 0, c->X.n * sizeof(double2), c->stream));
+  FASST_TRY(c->X.zero(c->X.n, c->stream));
   if ((st = cqt_forward_pair(q, c->stream, data, L, c->X.p, c->Fp, plane))) return st;
   k_cx_from_X<<<2048, 256, 0, c->stream>>>(c->X.p, c->cx.p, plane);
   FASST_LAUNCH_CHECK();

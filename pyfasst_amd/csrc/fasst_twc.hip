@@ -376,15 +376,14 @@ int fasst_set_tw_constr(fasst_ctx *c, int j, int kind, const double *TW_all, con
   int st = twc_alloc(c);
   if (st) return st;
   const int K = c->K[j], KP = c->KP;
-  double *twall = c->twall.p + (size_t)j * KP * c->Tp;
-  double *d = c->twdp.p + (size_t)j * KP * KP;
-  FASST_HIP(hipMemsetAsync(twall, 0, (size_t)KP * c->Tp * sizeof(double), c->stream));
+  const DSpan<double> twall = c->twall.at((size_t)j * KP * c->Tp, (size_t)KP * c->Tp);
+  const DSpan<double> d = c->twdp.at((size_t)j * KP * KP, (size_t)KP * KP);
+  FASST_TRY(twall.zero(twall.n, c->stream));
   if (TW_all) {
-    FASST_HIP(hipMemcpy2DAsync(twall, c->Tp * sizeof(double), TW_all, c->T * sizeof(double),
-                               c->T * sizeof(double), K, hipMemcpyHostToDevice, c->stream));
+    FASST_TRY(twall.put_rows(TW_all, K, c->T, c->T, c->Tp, c->stream));
   } else {
-    k_twall_init<<<(c->T + 255) / 256, 256, 0, c->stream>>>(c->TW.p + (size_t)j * KP * c->Tp, twall,
-                                                           K, c->T, c->Tp);
+    k_twall_init<<<(c->T + 255) / 256, 256, 0, c->stream>>>(c->TW.p + (size_t)j * KP * c->Tp,
+                                                           twall.p, K, c->T, c->Tp);
     FASST_LAUNCH_CHECK();
   }
   // the prior: K state probabilities (GSMM) or K x K transitions (SHMM);
@@ -395,10 +394,9 @@ int fasst_set_tw_constr(fasst_ctx *c, int j, int kind, const double *TW_all, con
     def.assign((size_t)rows * K, 1. / (double)K);
     dp = def.data();
   }
-  FASST_HIP(hipMemsetAsync(d, 0, (size_t)KP * KP * sizeof(double), c->stream));
-  FASST_HIP(hipMemcpy2DAsync(d, KP * sizeof(double), dp, K * sizeof(double), K * sizeof(double),
-                             rows, hipMemcpyHostToDevice, c->stream));
-  FASST_HIP(hipMemsetAsync(c->twstate.p + (size_t)j * c->Tp, 0, c->Tp * sizeof(int), c->stream));
+  FASST_TRY(d.zero(d.n, c->stream));
+  FASST_TRY(d.put_rows(dp, rows, K, K, KP, c->stream));
+  FASST_TRY(c->twstate.at((size_t)j * c->Tp).zero(c->Tp, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   c->twc[j] = kind;
   c->twc_free[j] = dp_free ? 1 : 0;
@@ -414,16 +412,12 @@ int fasst_get_tw_constr(fasst_ctx *c, int j, double *TW_all, double *dp, int *st
   DeviceGuard g(c->device);
   const int K = c->K[j], KP = c->KP;
   if (TW_all)
-    FASST_HIP(hipMemcpy2DAsync(TW_all, c->T * sizeof(double), c->twall.p + (size_t)j * KP * c->Tp,
-                               c->Tp * sizeof(double), c->T * sizeof(double), K,
-                               hipMemcpyDeviceToHost, c->stream));
+    FASST_TRY(c->twall.at((size_t)j * KP * c->Tp, (size_t)KP * c->Tp)
+                  .get_rows(TW_all, K, c->T, c->T, c->Tp, c->stream));
   if (dp)
-    FASST_HIP(hipMemcpy2DAsync(dp, K * sizeof(double), c->twdp.p + (size_t)j * KP * KP,
-                               KP * sizeof(double), K * sizeof(double), c->twc[j] == 1 ? 1 : K,
-                               hipMemcpyDeviceToHost, c->stream));
-  if (state)
-    FASST_HIP(hipMemcpyAsync(state, c->twstate.p + (size_t)j * c->Tp, c->T * sizeof(int),
-                             hipMemcpyDeviceToHost, c->stream));
+    FASST_TRY(c->twdp.at((size_t)j * KP * KP, (size_t)KP * KP)
+                  .get_rows(dp, c->twc[j] == 1 ? 1 : K, K, K, KP, c->stream));
+  if (state) FASST_TRY(c->twstate.at((size_t)j * c->Tp, c->Tp).get(state, c->T, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }

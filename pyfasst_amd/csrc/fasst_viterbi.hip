@@ -548,13 +548,9 @@ int viterbi_tracking(int device, int n_states, int n_frames, const double *log_d
       (st = ante.alloc((size_t)N * Sp)) || (st = dpath.alloc(N)) ||
       (st = jump.alloc((size_t)nch * S)) || (st = hi_state.alloc(nch)))
     return st;
-  FASST_HIP(hipMemcpy2D(dD.p, (size_t)N * sizeof(double), log_density,
-                        (size_t)ld_density * sizeof(double), (size_t)N * sizeof(double), S,
-                        hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy2D(dT.p, (size_t)S * sizeof(double), log_transition,
-                        (size_t)ld_transition * sizeof(double), (size_t)S * sizeof(double), S,
-                        hipMemcpyHostToDevice));
-  FASST_HIP(hipMemcpy(dprior.p, log_prior, S * sizeof(double), hipMemcpyHostToDevice));
+  FASST_TRY(dD.at(0).put_rows(log_density, S, N, ld_density, N));
+  FASST_TRY(dT.at(0).put_rows(log_transition, S, S, ld_transition, S));
+  FASST_TRY(dprior.put(log_prior, S));
   Events tm;
   if ((st = tm.start(0))) return st;
   // frame-major densities [N][Sp], target-major transitions TT[s][s'] = T[s'][s]
@@ -624,7 +620,7 @@ int viterbi_tracking(int device, int n_states, int n_frames, const double *log_d
                                                     dim3(kVtPersistThreads), args, plds, 0);
     if (e == hipSuccess) {
       int aborted = 1;
-      FASST_HIP(hipMemcpy(&aborted, abort_word.p, sizeof(int), hipMemcpyDeviceToHost));
+      FASST_TRY(abort_word.get(&aborted, 1));
       if (!aborted) {
         g_vt_kind = 2;
         done = true;
@@ -636,7 +632,7 @@ int viterbi_tracking(int device, int n_states, int n_frames, const double *log_d
       }
       if (want_probe) {   // per-phase means of workgroup 0 over frames 2..4095, us
         std::vector<long long> h(8 * 4096);
-        FASST_HIP(hipMemcpy(h.data(), probe.p, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
+        FASST_TRY(probe.get(h.data(), h.size()));
         const int nf = std::min(N, 4096);
         double a[6] = {0, 0, 0, 0, 0, 0};
         for (int n = 2; n < nf; ++n) {
@@ -664,6 +660,7 @@ int viterbi_tracking(int device, int n_states, int n_frames, const double *log_d
                                  ante.p + (size_t)n * Sp, S);
     }
     FASST_LAUNCH_CHECK();
+    // (device to device: no DSpan)
     FASST_HIP(hipMemcpyAsync(clast.p, cum.p + ((N - 1) & 1) * Sp, S * sizeof(double),
                              hipMemcpyDeviceToDevice, 0));
   }
@@ -674,7 +671,7 @@ int viterbi_tracking(int device, int n_states, int n_frames, const double *log_d
   k_vt_fill<<<(nch + 63) / 64, 64>>>(ante.p, Sp, hi_state.p, N, dpath.p);
   FASST_LAUNCH_CHECK();
   if ((st = elapsed_ms(tm.e[0], tm.e[1], 0, &g_vt_ms))) return st;
-  FASST_HIP(hipMemcpy(path, dpath.p, (size_t)N * sizeof(long long), hipMemcpyDeviceToHost));
+  FASST_TRY(dpath.get(path, N));
   return FASST_OK;
 }
 

@@ -124,3 +124,196 @@ def run_cases(_lib):
     for n in (15, 257):
         out["wiener_gain_%d" % n] = call_wiener_gain(_lib, n, 30 + n)
     return out
+
+
+# ---- set / get round trips: offsets into a larger buffer, padded pitches ----
+# F = 5 (Fp = 16), T = 7 (Tp = 16), K = 3 (below every padded KP), two sources:
+# source 1's rows start at a non-zero offset, right behind source 0's.
+RT_F, RT_T, RT_K = 5, 7, 3
+
+
+def rt_engine(ranks=(2, 2), conv=(True, False)):
+    from pyfasst_amd.engine import Engine
+    e = Engine(RT_F, RT_T)
+    e.configure(list(ranks), [RT_K] * len(ranks), list(conv))
+    return e
+
+
+def rt_rand(seed, *shape):
+    return 0.5 + np.random.default_rng(seed).random(shape)
+
+
+def sfnmf_round_trip(_lib, F, N, Ks, seed):
+    """(what was set, what came back): W [F, K] and H [K, N] of the three
+    factors of a source/filter NMF context."""
+    h = ctypes.c_void_p()
+    st = _lib.lib.sfnmf_create(0, F, N, Ks[0], Ks[1], Ks[2], ctypes.byref(h))
+    assert st == _lib.FASST_OK, _lib.last_error()
+    try:
+        sent = []
+        for i, K in enumerate(Ks):
+            sent += [rt_rand(seed + 2 * i, F, K), rt_rand(seed + 2 * i + 1, K, N)]
+        st = _lib.lib.sfnmf_set_params(h, *[_lib.dptr(a) for a in sent])
+        assert st == _lib.FASST_OK, _lib.last_error()
+        back = [np.full(a.shape, np.nan) for a in sent]
+        st = _lib.lib.sfnmf_get_params(h, *[_lib.dptr(a) for a in back])
+        assert st == _lib.FASST_OK, _lib.last_error()
+        return sent, back
+    finally:
+        _lib.lib.sfnmf_destroy(h)
+
+
+# ---- compute entry points whose host side moved onto DSpan -------------------
+def call_viterbi(_lib, S, N, ld_d, ld_t, seed):
+    """viterbi_tracking with host leading dimensions above the row widths, so
+    both pitched uploads are narrower than their host pitch."""
+    rng = np.random.default_rng(seed)
+    dens = np.ascontiguousarray(rng.standard_normal((S, ld_d)))
+    trans = np.ascontiguousarray(np.log(rng.random((S, ld_t))))
+    prior = np.log(rng.random(S))
+    path = np.full(N, -1, dtype=np.int64)
+    st = _lib.lib.viterbi_tracking(0, S, N, _lib.dptr(dens), ld_d, _lib.dptr(prior),
+                                   _lib.dptr(trans), ld_t,
+                                   path.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)))
+    assert st == _lib.FASST_OK, _lib.last_error()
+    return path
+
+
+def call_nsgt_fft(_lib, n, sign, seed):
+    x = np.ascontiguousarray(_cplx(np.random.default_rng(seed), n))
+    out = np.full(n, np.nan + 0j)
+    st = _lib.lib.fasst_nsgt_fft(0, n, sign, _lib.dptr(x), _lib.dptr(out))
+    assert st == _lib.FASST_OK, _lib.last_error()
+    return out
+
+
+def digest(a):
+    """A large output as its SHA-256 (shape and dtype included): equal digests
+    are equal bits, and the fixture stays small."""
+    import hashlib
+    a = np.ascontiguousarray(a)
+    assert not np.isnan(a).any()
+    h = hashlib.sha256(("%s %s " % (a.dtype.str, a.shape)).encode() + a.tobytes())
+    return np.frombuffer(h.digest(), dtype=np.uint8).copy()
+
+
+def _keep(out, name, a):
+    a = np.ascontiguousarray(a)
+    if a.nbytes <= 2048:
+        out[name] = a
+    else:
+        out[name + "_sha256"] = digest(a)
+
+
+def cqt_cases(out):
+    """cqt24 on 101 samples, the smallest geometry of test_gpu_cqt_cells.py
+    (4 octaves, the last of 3 frames): the cells, their raster and the inverse
+    (perfRast = 0); the raster path forward and inverse (perfRast = 1) on
+    test_gpu_cqt.py's cqt12 signal."""
+    import cqt_cells_ref as C
+    from pyfasst_amd.tftransforms import minqt
+    kw = C.CASES["cqt24"][1]
+    x = C.signal("cqt24")
+    t = minqt.CQTransfo(**kw)
+    t.computeTransform(x)
+    for k, v in sorted(t.cellCQT.items(), key=lambda kv: str(kv[0])):
+        _keep(out, "cqt_cell_%s" % k, np.array(v))
+    _keep(out, "cqt_cells_raster", np.array(t.transfo))
+    _keep(out, "cqt_cells_inverse", t.invertTransform())
+    from helpers import CQT_CASES, load
+    r = minqt.CQTransfo(perfRast=1, **CQT_CASES[3][2])   # cqt12 of test_gpu_cqt.py
+    r.computeTransform(load("cqt")["x"])
+    X = np.array(r.transfo)
+    _keep(out, "cqt_raster_forward", X)
+    r.transfo = X
+    _keep(out, "cqt_raster_inverse", r.invertTransform())
+
+
+def filter_cases(out):
+    from pyfasst_amd.tftransforms.stft import filter_stft
+    rs = np.random.RandomState(92)
+    x = rs.randn(50, 2)
+    W = rs.randn(2, 2, 33) + 1j * rs.randn(2, 2, 33)
+    w, aw = _windows(64)
+    _keep(out, "filter_stft", filter_stft(x, W, analysisWindow=aw, synthWindow=w, hopsize=16.0,
+                                          nfft=64.0))
+
+
+def nmf_cases(_lib, out):
+    """One iteration of each context, then its getters.  F, N and the ranks
+    are odd and below every padded size."""
+    from pyfasst_amd.tools import nmf
+    import pyfasst_amd.SeparateLeadStereo.SIMM.SIMM as SIMM
+    F, N = 33, 17
+    rs = np.random.RandomState(93)
+    SXR, SXL = rs.gamma(0.8, 1.0, (F, N)), rs.gamma(0.8, 1.0, (F, N))
+    for K in (3, 16):   # 16: the fused kernels and their transposed copies
+        W, H = nmf._run(SXR, 0.5 + rs.rand(F, K), 0.5 + rs.rand(K, N), 1, True, True, None)
+        _keep(out, "nmf_K%d_W" % K, W)
+        _keep(out, "nmf_K%d_H" % K, H)
+    R = 3
+    res = SIMM._stereo_nmf_run(SXR, SXL, 0.5 + rs.rand(F, R), 0.5 + rs.rand(R, N), rs.rand(R), 1,
+                               1.0, True, _lib.default_device())
+    for name, a in zip(("bR", "bL", "HM", "WM", "err"), res):
+        _keep(out, "snmf_" + name, np.asarray(a, dtype=np.float64))
+    WF0, WG = rs.gamma(1.0, 1.0, (F, 5)), rs.gamma(1.0, 1.0, (F, 3))
+    np.random.seed(94)
+    res = SIMM.Stereo_SIMM(SXR, SXL, WF0, WG, numberOfFilters=1,
+                           numberOfAccompanimentSpectralShapes=1, numberOfIterations=1,
+                           computeError=True, verbose=False)
+    for i, a in enumerate(res):
+        _keep(out, "simm_stereo_%d" % i, np.asarray(a, dtype=np.float64))
+    np.random.seed(95)
+    res = SIMM.SIMM(SXR, WF0, WG, numberOfFilters=1, numberOfAccompanimentSpectralShapes=1,
+                    numberOfIterations=1, verbose=False)
+    for i, a in enumerate(res):
+        _keep(out, "simm_mono_%d" % i, np.asarray(a, dtype=np.float64))
+
+
+def nsgt_cases(out):
+    """NSGT forward and backward on host arrays of the prime length 101, real
+    (y is one double per sample) and complex (two per sample)."""
+    import warnings
+    from pyfasst_amd.tftransforms.nsgt import NSGT, OctScale
+    rs = np.random.RandomState(96)
+    for real in (True, False):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            t = NSGT(OctScale(500, 3500, 4), 8000, 101, real=real, matrixform=False)
+        x = rs.randn(101)
+        c = t.forward(x)
+        tag = "real" if real else "cplx"
+        _keep(out, "nsgt_%s_forward" % tag, np.concatenate([np.ravel(b) for b in c]))
+        _keep(out, "nsgt_%s_backward" % tag, np.asarray(t.backward(c)))
+
+
+def gemm_cases(_lib, out):
+    """The guarded-buffer harness: A one double past the allocation's base
+    (a_skew = 1), guard words on both sides of every payload."""
+    M, N, K, lda, ldb, ldc = 5, 6, 7, 6, 8, 9
+    rng = np.random.default_rng(97)
+    A = np.zeros((K, lda))
+    B = np.zeros((K, ldb))
+    A[:, :M] = rng.integers(-8, 9, (K, M))
+    B[:, :N] = rng.integers(-8, 9, (K, N))
+    C = np.full((M, ldc), -3.0)
+    arm = ctypes.c_int(-1)
+    st = _lib.lib.fasst_dgemm2_probe(0, M, N, K, _lib.dptr(A), lda, 1, _lib.dptr(B), ldb, 0,
+                                     _lib.dptr(C), ldc, 0, ctypes.byref(arm))
+    assert st == _lib.FASST_OK, _lib.last_error()
+    assert np.array_equal(C[:, :N], A[:, :M].T @ B[:, :N])   # small integers: exact
+    out["gemm_skew_C"] = C
+    out["gemm_skew_arm"] = np.array([arm.value])
+
+
+def run_compute_cases(_lib):
+    out = {"viterbi_3_5": call_viterbi(_lib, 3, 5, 8, 4, 90)}
+    for n in (7, 101):   # primes: the chirp-z path, tables uploaded per call
+        for sign in (-1, 1):
+            out["nsgt_fft_%d_%s" % (n, "fwd" if sign < 0 else "inv")] = call_nsgt_fft(_lib, n, sign, 91 + n)
+    cqt_cases(out)
+    filter_cases(out)
+    nmf_cases(_lib, out)
+    nsgt_cases(out)
+    gemm_cases(_lib, out)
+    return out
