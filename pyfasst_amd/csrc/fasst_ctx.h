@@ -117,7 +117,7 @@ struct fasst_ctx {
   // created; 2 (default): it also forms the next iteration's FWHt / hsum
   int ftail = 2;
   // the single-pass E-step's tile-packed operand images (layouts at
-  // k_cx_image / k_tw_image in fasst_em.hip).  eimg: bit 0 the Cx image, bit 1
+  // k_cx_image / k_tw_image in fasst_em_estep.hip).  eimg: bit 0 the Cx image, bit 1
   // the TW image (FASST_ESTEP_IMG = 0 | cx | tw | 1, read when the context is
   // created).  cxp [nft][ntt][512] is built from the planes by the first
   // iteration after an observation was written (cxp_valid, cleared by every

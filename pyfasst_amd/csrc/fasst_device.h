@@ -3,6 +3,7 @@
 // fixed summation order) lives here once, so a fix reaches every caller.
 #pragma once
 #include "fasst_common.h"
+#include "fasst_esched.h"
 
 namespace fasst {
 
@@ -134,6 +135,55 @@ template <int AUX>
 __device__ __forceinline__ double buf_ld(__amdgpu_buffer_rsrc_t r, unsigned vo, unsigned so) {
   const buf_u2 x = __builtin_amdgcn_raw_buffer_load_b64(r, (int)vo, (int)so, AUX);
   return __builtin_bit_cast(double, x);
+}
+
+// XCD-aware logical block: workgroups b, b + 8, ... of a launch share an XCD
+// (dispatch is round-robin over the 8 XCDs, for speed only, never
+// correctness); the bijective remap of cdna_hip_programming.md gives each XCD
+// a contiguous run of the logical (x fastest, z slowest) sequence, so the
+// blocks that re-read one operand slice (the E-step's TW chunk, the
+// contractions' W / (FW H)^T slices) meet in one 4 MB L2.  At C3 it takes
+// 9-14 % off the HBM fetch of the E-step and both contractions (rocprofv3
+// FETCH_SIZE, profiles/r4_bench.txt vs the row-major order) at equal time.
+__device__ __forceinline__ dim3 xcd_block() {
+  const int nx = gridDim.x, ny = gridDim.y, n = nx * ny * gridDim.z;
+  const int b = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
+  const int q = n / 8, r = n % 8, x = b % 8;
+  const int L = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
+  return dim3(L % nx, (L / nx) % ny, L / (nx * ny));
+}
+
+// max(x, y) as ONE v_max_f64: fmax() lowers to llvm.maxnum, whose operands
+// the backend first canonicalises (a second v_max_f64 each) unless it can
+// prove them canonical, which it cannot for MFMA results.  For the finite
+// operands it is used on the two forms agree.
+__device__ __forceinline__ double vmax_f64(double x, double y) {
+  double r;
+  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+  return r;
+}
+
+// One element of the TW image [ntt][J][KP / 8][64]: piece (tt, j, u), lane l
+// pairs the operands of the k-steps 2 u and 2 u + 1, TW[j][tq + 8 u][16 tt +
+// fl] and TW[j][tq + 8 u + 4][16 tt + fl]; `row(k)` is row k of source j at
+// frame 16 tt + fl
+template <class Row>
+__device__ __forceinline__ void tw_image_store(double2 *__restrict__ img, int tt, int j, int J,
+                                               int KP, int e, Row &&row) {
+  const int u = e >> 6, lane = e & 63, fl = lane & 15, tq = lane >> 4;
+  img[((size_t)tt * J + j) * (KP / 8) * 64 + e] = make_double2(row(tq + 8 * u, fl), row(tq + 8 * u + 4, fl));
+}
+
+// sum of the E-step's loglik partials [slot][bin tile]: the live entries
+// (slot < segments of the bin tile, fasst_esched.h) in index order, strided
+// over the 256 threads (a fixed order)
+__device__ __forceinline__ double ll_partial_sum(const double *__restrict__ llpart, const ESched es) {
+  double x = 0.0;
+  for (int i = threadIdx.x; i < es.nslot * es.nbt; i += 256) {
+    const int sl = i / es.nbt, bt = i - sl * es.nbt;
+    if (sl < es_segments(es, bt)) x += llpart[i];
+  }
+  return x;
 }
 
 }  // namespace fasst

@@ -14,16 +14,9 @@
 //   k_fb_update   FB *= (num/den)^omega, W_new = FB.FW
 //   k_tw_contract TW numerator/denominator over f (MFMA) + TW update (:1634-1727)
 //   k_renorm      renormalize_parameters          (:1980-2040)
-//
-// E-step restructuring (exact algebra, verified to 1e-15 against the
-// reference): with S = Sigma_x^-1, N = S Cx S - S and P = Cx S (2x2 per
-// (f,t)), the reference's R x R pair loop (:698-731) is
-//   hat_Rss[f][r1,r2] = a_r1^H (sum_t V_j1 V_j2 N) a_r2 / T + d_r1r2 mean_t V_r1
-//   hat_Rxs[f][c,r]   = sum_c' (sum_t V_j P)[c,c'] A_r,c' / T
-//   hat_Ws[r](f,t)    = | V_j^2 a_r^H N a_r + V_j |
-// because the mixing a_r is constant over t.  The t-reductions shrink from
-// R^2 complex products per (f,t) to J(J+1)/2 x 4 + 9J real FMAs.
-#include "fasst_ctx.h"
+// The E-step's kernels and launches are fasst_em_estep.hip's (interface:
+// fasst_em.h); the other phases are still in this unit.
+#include "fasst_em.h"
 #include "fasst_device.h"
 #include "fasst_twc.h"
 
@@ -41,32 +34,6 @@ void set_error(const char *fmt, ...) {
   vsnprintf(buf, sizeof(buf), fmt, ap);
   va_end(ap);
   g_err = buf;
-}
-
-// XCD-aware logical block: workgroups b, b + 8, ... of a launch share an XCD
-// (dispatch is round-robin over the 8 XCDs, for speed only, never
-// correctness); the bijective remap of cdna_hip_programming.md gives each XCD
-// a contiguous run of the logical (x fastest, z slowest) sequence, so the
-// blocks that re-read one operand slice (the E-step's TW chunk, the
-// contractions' W / (FW H)^T slices) meet in one 4 MB L2.  At C3 it takes
-// 9-14 % off the HBM fetch of the E-step and both contractions (rocprofv3
-// FETCH_SIZE, profiles/r4_bench.txt vs the row-major order) at equal time.
-__device__ __forceinline__ dim3 xcd_block() {
-  const int nx = gridDim.x, ny = gridDim.y, n = nx * ny * gridDim.z;
-  const int b = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
-  const int q = n / 8, r = n % 8, x = b % 8;
-  const int L = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-  return dim3(L % nx, (L / nx) % ny, L / (nx * ny));
-}
-
-// max(x, y) as ONE v_max_f64: fmax() lowers to llvm.maxnum, whose operands
-// the backend first canonicalises (a second v_max_f64 each) unless it can
-// prove them canonical, which it cannot for MFMA results.  For the finite
-// operands it is used on the two forms agree.
-__device__ __forceinline__ double vmax_f64(double x, double y) {
-  double r;
-  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
-  return r;
 }
 
 // ---------------------------------------------------------------- prep
@@ -212,1407 +179,6 @@ __global__ void k_inst_A(const double2 *__restrict__ Pinst, double2 *__restrict_
   }
 }
 
-// ------------------------------------------- E-step operand images (J <= 8)
-// k_estep_mx's lane (fl = lane & 15, tq = lane >> 4) of the wave on the
-// 16 x 16 tile (bin tile bt, frame tile tt) holds point i at (f = 16 bt + fl,
-// t = 16 tt + tq + 4 i).  The images store what each of its load instructions
-// needs as one contiguous KB, 16 bytes per lane.
-//
-// Cx image: record (bt, tt) = 8 pieces of 64 double2 at img + (bt ntt + tt)
-// 512; piece 2 i + h, lane l: (cx00, cx11) (h = 0) or (cxr, cxi) (h = 1) of
-// the lane's point i, padding included.  The records of one bin tile are
-// consecutive in tt.  Built once per observation (cx_image below).
-__global__ __launch_bounds__(256) void k_cx_image(const double *__restrict__ cx,
-                                                  double2 *__restrict__ img, int Fp, int ntt,
-                                                  size_t plane) {
-  const int tt = blockIdx.x, bt = blockIdx.y;
-  double2 *rec = img + ((size_t)bt * ntt + tt) * 512;
-  for (int e = threadIdx.x; e < 512; e += 256) {
-    const int piece = e >> 6, lane = e & 63, i = piece >> 1, fl = lane & 15, tq = lane >> 4;
-    const double *p = cx + (size_t)(16 * tt + tq + 4 * i) * Fp + 16 * bt + fl;
-    rec[e] = piece & 1 ? make_double2(p[2 * plane], p[3 * plane]) : make_double2(p[0], p[plane]);
-  }
-}
-
-// One element of the TW image [ntt][J][KP / 8][64]: piece (tt, j, u), lane l
-// pairs the operands of the k-steps 2 u and 2 u + 1, TW[j][tq + 8 u][16 tt +
-// fl] and TW[j][tq + 8 u + 4][16 tt + fl]; `row(k)` is row k of source j at
-// frame 16 tt + fl
-template <class Row>
-__device__ __forceinline__ void tw_image_store(double2 *__restrict__ img, int tt, int j, int J,
-                                               int KP, int e, Row &&row) {
-  const int u = e >> 6, lane = e & 63, fl = lane & 15, tq = lane >> 4;
-  img[((size_t)tt * J + j) * (KP / 8) * 64 + e] = make_double2(row(tq + 8 * u, fl), row(tq + 8 * u + 4, fl));
-}
-
-// the TW image from the planes: wherever TW was written without it (an
-// upload, the unfused tail, the first iteration of a batch)
-__global__ __launch_bounds__(256) void k_tw_image(const double *__restrict__ TW,
-                                                  double2 *__restrict__ img, int J, int KP, int Tp) {
-  const int tt = blockIdx.x, j = blockIdx.y;
-  const double *tw = TW + (size_t)j * KP * Tp + 16 * tt;
-  for (int e = threadIdx.x; e < (KP / 8) * 64; e += 256)
-    tw_image_store(img, tt, j, J, KP, e, [&](int k, int fl) { return tw[(size_t)k * Tp + fl]; });
-}
-
-// ---------------------------------------------------------------- E-step
-struct EArgs {
-  const double *cx00, *cx11, *cxr, *cxi;  // [Tp][Fp]
-  const double *TW;                       // [J][KP][Tp]
-  // tile-packed operand images of k_estep_mx (layouts at the pack kernels)
-  const double2 *cxp;                     // [nft][nttp] records of 512: Cx of one 16 x 16 tile
-  const double2 *twp;                     // [nttp][J][KP / 8][64]: the tile's TW operand pairs
-  const double *Wkf;                      // [J][KP][Fp]
-  const double2 *A;                       // [R][2][Fp]
-  const double *psd;                      // [Fp]
-  double *hatW;                           // [J][Tp][Fp]: rho = hat_W / max(V, eps)
-  double *part;                           // [slot][Fp][NACC]
-  double *llpart;                         // [slot][nft]
-  int F, T, Fp, Tp, KP, R, ntt, tpc, nft;
-  int nttp;          // frame tiles of the whole clip (the images' record stride)
-  int ybase, tbase;  // this launch's chunks start at partial ybase, frame tile tbase (ntt = end)
-  ESched es;         // the partials' layout (k_estep_mx: also its schedule; fasst_esched.h)
-  int roff[kMaxJ + 1];
-  const int *halt;
-};
-
-// Single-pass E-step with the per-bin t-reductions on the matrix cores.
-//
-// Every statistic of the E-step is a per-bin dot product over frames:
-//   cross  Q_j[c]      = sum_t V_j P_c        (P = Cx S, 8 real components)
-//   pairs  M_p[c]      = sum_t V_j1 V_j2 N_c  (N = S Cx S - S, 4 components)
-// For one bin these are tiny GEMMs, (J x T).(T x 8) and (NP x T).(T x 4).
-// v_mfma_f64_4x4x4_4b runs four independent 4x4x4 products per instruction,
-// one per block of 16 lanes (lane = 16 X + 4 b + Y: A[m=Y][k=X],
-// B[k=X][n=Y], D[m=X][n=Y] of block b; tools/probe_mfma4.hip), so with
-// block = bin and k = frame, ONE instruction contracts 4 frames of 4 bins
-// for a 4 x 4 block of statistics.  After each frame group, every lane drops
-// its point's operands (V, P, N and the pair products V_j1 V_j2) into a
-// per-wave LDS slab in the MFMA operand layout, and the wave issues
-// 4 bin groups x (2 + ceil(NP/4)) MFMAs.  The accumulators shrink from
-// 4 J(J+1)/2 + 8J doubles per lane (72 at J = 4, what forced the round-1
-// E-step into two launches) to 4 (2 + ceil(NP/4)) (20 at J = 4), so ONE pass
-// streams Cx once, forms V, Sigma_x and its inverse once per point, and keeps
-// two waves per SIMD; the 72 FMAs per point leave the VALU for the matrix
-// pipe (4x4x4_4b runs at 74.7 TF on this chip, profiles/r1_ubench_fp64.txt).
-
-// Reader-formed pair operands (RP, J >= 4): the slab holds V, P and N only,
-// and the reader forms the pair operands V_j1 V_j2 itself.  With the sources
-// padded to Q = 4 (J = 4) or 8 (J > 4), lane m of a 4-pair group reads the Q
-// rotated values W_e = V_{(m + e) mod Q} of its point, and the pairs are the
-// groups (base, d): pair m of a group is (base + m, base + m + d mod Q), its
-// operand W_base W_{(base + d) mod Q} -- static register indices.  Q = 8: the
-// 36 pairs are {0, 4} x {0..3} plus (0, 4); Q = 4: the 10 pairs are
-// (0, 0), (0, 1) and (0, 2) (rows m = 2, 3 of the last repeat rows 0, 1).
-// The writer's J (J + 1) / 2 products and their slab stores go (J = 8: 56 ->
-// 20 stores per point, J = 4: 26 -> 16), the reader's loads stay or drop
-// (J = 8: 14 -> 11 per bin group), and the slab shrinks.  Same-box A/B at
-// C3 (J = 4): E-step 0.373 vs 0.390 ms, iteration 1.040 vs 1.068 ms; J = 6 /
-// 8 (K = 32): 0.813 / 1.002 ms against 1.083 / 1.663 ms with writer-formed
-// pairs.
-// VR (J > 4): also the per-source pipelined V tile, one wave per SIMD (the
-// register file, not the LDS, bounds it: at two waves the kernel spills
-// 500+ bytes per lane to scratch) and the epilogue one bin group at a time.
-template <int J>
-struct MXShape {
-  static constexpr bool VR = J > 4;
-  static constexpr bool RP = J >= 4;
-  static constexpr int Q = J > 4 ? 8 : 4;       // RP: sources padded to Q
-  static constexpr int NP = J * (J + 1) / 2;
-  static constexpr int NPG = RP ? (Q == 8 ? 9 : 3) : (NP + 3) / 4;   // pair groups of 4
-  static constexpr int NVG = (J + 3) / 4;       // source groups of 4
-  static constexpr int SP = NVG, SN = NVG + 2, SV2 = NVG + 3;  // set offsets: P lo/hi, N, VV
-  static constexpr int NSET = NVG + 3 + (RP ? 0 : NPG);  // V groups | P lo | P hi | N | VV groups
-  static constexpr int GS = NSET * 64 + 1;      // doubles per bin group (+1: bank skew)
-  // VST (J > 4): the V sets of all four point rounds are written once per
-  // tile, right after the V tile ([round][bin group][NVG sets], VGS each),
-  // then P / N per round ([bin group][3 sets], PGS each)
-  static constexpr bool VST = VR;
-  static constexpr int VGS = NVG * 64 + 1, PGS = 3 * 64 + 1;
-  static constexpr int SLAB = VST ? 16 * VGS + 4 * PGS : 4 * GS;   // doubles per wave
-};
-// RP pair group h: (base, d)
-template <int Q>
-__host__ __device__ constexpr int rp_base(int h) { return Q == 4 || h == 8 ? 0 : 4 * (h & 1); }
-template <int Q>
-__host__ __device__ constexpr int rp_d(int h) { return Q == 4 ? h : (h == 8 ? 4 : h >> 1); }
-// canonical index (j1 <= j2, j1 major) of the pair lane m of group h
-// accumulates, or -1 (a padded source or a repeated pair)
-template <int J>
-__host__ __device__ constexpr int rp_pair(int h, int m) {
-  constexpr int Q = MXShape<J>::Q;
-  if (!MXShape<J>::RP) return 4 * h + m < MXShape<J>::NP ? 4 * h + m : -1;
-  const int j1 = rp_base<Q>(h) + m, j2 = (rp_base<Q>(h) + m + rp_d<Q>(h)) & (Q - 1);
-  if (j1 >= J || j2 >= J || (Q == 4 && rp_d<Q>(h) == 2 && m >= 2)) return -1;
-  const int lo = j1 < j2 ? j1 : j2, hi = j1 < j2 ? j2 : j1;
-  return lo * J - lo * (lo - 1) / 2 + (hi - lo);
-}
-// does RP pair group h hold a live pair
-template <int J>
-__host__ __device__ constexpr bool rp_live(int h) {
-  for (int m = 0; m < 4; ++m)
-    if (rp_pair<J>(h, m) >= 0) return true;
-  return false;
-}
-
-// the W tile sits in LDS unless it would push the block past 160 KB (J = 8,
-// K = 128); then the V tiles read their W operand from L2
-template <int J, int NKS>
-__host__ __device__ constexpr bool mx_w_in_lds() {
-  return (size_t)(4 + J * 4 * NKS * 16 + 4 * MXShape<J>::SLAB + J * 4 * 16) * sizeof(double) <=
-         160 * 1024;
-}
-template <int J, int NKS>
-static constexpr size_t estep_mx_smem() {
-  return (size_t)(4 + (mx_w_in_lds<J, NKS>() ? J * 4 * NKS * 16 : 0) + 4 * MXShape<J>::SLAB) *
-         sizeof(double);
-}
-
-// (the LDS slabs allow two blocks per CU, so the register budget is that of
-// two waves per SIMD: amdgpu_waves_per_eu tells the scheduler, which would
-// otherwise serialise the operand loads to fit three)
-// (more than 4 sources: one block per CU -- the slabs alone pass 80 KB -- so
-// one wave per SIMD and the full 512-register file)
-// (no-load-store-opt: the compiler otherwise pairs the slab / W-tile reads
-// into ds_read2_b64 / ds_read2st64_b64, which take 8 LDS cycles for the 4 of
-// two ds_read_b64 -- MI355X_MICROARCH.md §LDS -- and the LDS is this kernel's
-// busiest unit)
-// raw-buffer forms of the E-step's streaming accesses: wave-uniform
-// resource (SGPRs, formed on the scalar unit) + 32-bit per-lane offset, so
-// no 64-bit VALU address arithmetic per access (aux 2 = non-temporal)
-// (buf_rsrc / buf_ld of fasst_device.h; the store is the E-step's alone)
-template <int AUX>
-__device__ __forceinline__ void es_st(double v, __amdgpu_buffer_rsrc_t r, unsigned vo, unsigned so) {
-  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(buf_u2, v), r, (int)vo, (int)so, AUX);
-}
-
-// 16-byte raw-buffer load of an operand image (as buf_ld: wave-uniform
-// resource, per-lane byte offset vo, uniform byte offset so)
-typedef unsigned buf_u4 __attribute__((ext_vector_type(4)));
-typedef double buf_d2 __attribute__((ext_vector_type(2)));
-template <int AUX>
-__device__ __forceinline__ buf_d2 buf_ld2(__amdgpu_buffer_rsrc_t r, unsigned vo, unsigned so) {
-  const buf_u4 x = __builtin_amdgcn_raw_buffer_load_b128(r, (int)vo, (int)so, AUX);
-  return __builtin_bit_cast(buf_d2, x);
-}
-
-// Does the (J, NKS) instantiation preload every TW operand of a tile in
-// pairs of k-steps (the only form that reads the TW image)
-template <int J, int NKS>
-__host__ __device__ constexpr bool mx_tw_preload() {
-  return J <= 4 && J * NKS <= 32 && NKS % 2 == 0;
-}
-
-// CXI / TWI: Cx / the preloaded TW operands are read from the tile-packed
-// images a.cxp / a.twp (k_cx_image, k_tw_image) instead of the planes: one
-// contiguous KB per wave-instruction, 16 bytes per lane, half the loads.
-// The values and every arithmetic instruction are those of the plane form.
-// (J = 4 at K = 128: the 64 KB W tile leaves one block per CU, so one wave
-// per SIMD and the full register file for the pipelined V tile)
-template <int J, int NKS, int RKU, bool CXI = false, bool TWI = false>
-__global__ __launch_bounds__(256, (J > 4 || (J == 4 && NKS == 32)) ? 1 : 2)
-__attribute__((amdgpu_waves_per_eu(1, (J > 4 || (J == 4 && NKS == 32)) ? 1 : 2))) FASST_NO_LDS_PAIRING
-void k_estep_mx(const EArgs a) {
-  static_assert(!TWI || mx_tw_preload<J, NKS>(), "the TW image serves the preload path only");
-  HALT_GUARD(a.halt);
-  using S = MXShape<J>;
-  constexpr bool VR = S::VR, RP = S::RP;
-  constexpr int Q = S::Q;
-  constexpr int NP = S::NP, NPG = S::NPG, NVG = S::NVG;
-  constexpr int NACC = 4 * NP + 8 * J;
-  constexpr int KP = 4 * NKS;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  // per-source Sigma_x coefficients in a static array: the compiler can see
-  // that the slab stores never touch them and reuse each read within a tile
-  __shared__ double s_cj[J * 4 * 16];      // [J][4][16]
-  constexpr bool WL = mx_w_in_lds<J, NKS>();
-  double *s_ll = smem;                     // [4]
-  double *s_w = s_ll + 4;                  // [J][KP][16] W tile (if WL)
-  double *s_slab = s_w + (WL ? J * KP * 16 : 0);  // [4 waves][SLAB] operand slabs
-  double *s_red = s_w;                     // [4][NACC][16 | 4] (epilogue, aliases W + slabs)
-
-  // The block's work: segments, each a run of frame tiles [tb, te) of one
-  // 16-bin tile whose statistics go to partial `slot`.  Chunk grid: one
-  // segment, (bin tile, chunk) = the XCD-ordered block (x, y).  Balanced
-  // schedule (fasst_esched.h): the quad-steps [wu, wend) of the flattened
-  // (bin tile, quad-step) list, cut where the bin tile changes; the XCD order
-  // gives each XCD a contiguous run of the list.  All of it is wave-uniform.
-  const dim3 bi = xcd_block();   // chunk grid: x: 16-bin tile, y: frame chunk
-  // (chunk grid: the one segment)
-  int btile = bi.x, tb = a.tbase + bi.y * a.tpc, te = min(tb + a.tpc, a.ntt);
-  int slot = a.ybase + bi.y;
-  int left = 0;   // balanced: quad-steps of the range after this segment
-  if (a.es.bal) {
-    // the range's first segment: the only divisions, ahead of the segment loop
-    // (inside it their loop-invariant parts stayed live across the tile loop)
-    const int blk = bi.x, Q = a.es.Q;
-    const long long U = (long long)a.es.nbt * Q;
-    const int wu = (int)es_lo(blk, U, a.es.nb), wend = (int)es_lo(blk + 1, U, a.es.nb);
-    btile = wu / Q;
-    const int q0 = wu - btile * Q, nq = min(Q - q0, wend - wu);
-    tb = a.tbase + 4 * q0;
-    te = min(tb + 4 * nq, a.ntt);
-    slot = blk - es_first(btile, Q, a.es.nbt, a.es.nb);
-    left = wend - wu - nq;
-  }
-  // (pinned to SGPRs: the tile loop's bounds and the buffer resources derive from them)
-  btile = __builtin_amdgcn_readfirstlane(btile);
-  tb = __builtin_amdgcn_readfirstlane(tb);
-  te = __builtin_amdgcn_readfirstlane(te);
-  slot = __builtin_amdgcn_readfirstlane(slot);
-  left = __builtin_amdgcn_readfirstlane(left);
-  for (;;) {
-  // launder: every per-thread value (the prologue's, the tile loop's and the
-  // epilogue's addresses) is formed per segment from this thread index, as in
-  // a kernel of one segment: the compiler would otherwise hoist them out of
-  // the segment loop and keep them live across the tile loop, ~30 registers
-  int tidp = threadIdx.x;
-  asm volatile("" : "+v"(tidp));
-  const int tid = tidp, lane = tid & 63, wv = tid >> 6;
-  const int fl = lane & 15, tq = lane >> 4;
-  double *slab = s_slab + wv * S::SLAB;
-  const int f0 = btile * 16;
-  const int f = f0 + fl;
-
-  if (WL)
-    for (int idx = tidp; idx < J * KP * 16; idx += 256) {
-      const int ff = idx & 15, jk = idx >> 4;
-      s_w[idx] = a.Wkf[(size_t)jk * a.Fp + f0 + ff];
-    }
-  // operand slots no point writes (sources >= J, pairs >= NP) stay zero
-  for (int idx = tidp; idx < 4 * S::SLAB; idx += 256) s_slab[idx] = 0.0;
-  if (tidp < 16) {
-    const int ff = f0 + tidp;
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      double al = 0, be = 0, gr = 0, gi = 0;
-      for (int r = a.roff[j]; r < a.roff[j + 1]; ++r) {
-        const double2 a0 = a.A[(size_t)(2 * r) * a.Fp + ff];
-        const double2 a1 = a.A[(size_t)(2 * r + 1) * a.Fp + ff];
-        al += a0.x * a0.x + a0.y * a0.y;
-        be += a1.x * a1.x + a1.y * a1.y;
-        gr += a0.x * a1.x + a0.y * a1.y;  // Re a0 conj(a1)
-        gi += a0.y * a1.x - a0.x * a1.y;  // Im a0 conj(a1)
-      }
-      s_cj[(j * 4 + 0) * 16 + tidp] = al;
-      s_cj[(j * 4 + 1) * 16 + tidp] = be;
-      s_cj[(j * 4 + 2) * 16 + tidp] = gr;
-      s_cj[(j * 4 + 3) * 16 + tidp] = gi;
-    }
-  }
-  __syncthreads();
-
-  // CJR (J >= 4): the lane's Sigma_x coefficients in registers for the
-  // whole kernel (J = 8: 474 -> 240 LDS reads and 243 -> 84 waits per tile,
-  // E-step 1.00 -> 0.98 ms; J = 4: 0.372 -> 0.364 ms, same-box A/B)
-  constexpr bool CJR = J >= 4;
-  constexpr bool NF = J >= 4;
-  double cjr[CJR ? J : 1][4];
-  if constexpr (CJR)
-#pragma unroll
-    for (int j = 0; j < J; ++j)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) cjr[j][c] = s_cj[(j * 4 + c) * 16 + fl];
-  double inv_rk[J];
-#pragma unroll
-  for (int j = 0; j < J; ++j)
-    inv_rk[j] = RKU ? 1.0 / (double)RKU : 1.0 / (double)(a.roff[j + 1] - a.roff[j]);
-  const double psd = a.psd[f];
-  const bool fvalid = f < a.F;
-  // writer side: this lane's point goes to bin group g = fl / 4, block b = fl % 4, X = tq
-  double *wr = slab + (fl >> 2) * S::GS + 16 * tq + 4 * (fl & 3);
-  // reader side: operands of lane (X, b, Y) sit at [group][set][lane]
-  const double *rd = slab + lane;
-  auto slab_fence0 = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
-  // RP: W_e = V_{(m + e) mod Q} of the lane's point (m = Y) sits in set
-  // ((m + e) mod Q) / 4 at Y' = (m + e) mod 4 of the same (X, b)
-  const double *rdq = slab + (lane & ~3);
-  constexpr bool VST = S::VST;
-  // VST: this lane's V of round i at wrv + i 4 VGS (+ (j >> 2) 64 + (j & 3)),
-  // its P / N at wpn; the reader's V of round i, bin group g at
-  // rdq + (4 i + g) VGS, P / N at rpn + g PGS
-  double *wrv = slab + (fl >> 2) * S::VGS + 16 * tq + 4 * (fl & 3);
-  double *wpn = slab + 16 * S::VGS + (fl >> 2) * S::PGS + 16 * tq + 4 * (fl & 3);
-  const double *rpn = slab + 16 * S::VGS + lane;
-  int vro[Q];
-#pragma unroll
-  for (int e = 0; e < Q; ++e) {
-    const int j = ((lane & 3) + e) & (Q - 1);
-    vro[e] = (j >> 2) * 64 + (j & 3);
-  }
-
-  double xacc[4][NVG][2], pacc[4][NPG];  // D operands (4x4 blocks per bin group)
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-#pragma unroll
-    for (int vg = 0; vg < NVG; ++vg) xacc[g][vg][0] = xacc[g][vg][1] = 0.0;
-#pragma unroll
-    for (int h = 0; h < NPG; ++h) pacc[g][h] = 0.0;
-  }
-  double ll = 0.0, lm = 1.0, lev = 0.0, xmin = 1.0;
-
-  // SA: wave-uniform buffer resources (SGPRs, formed on the scalar unit) +
-  // 32-bit per-lane byte offsets instead of one 64-bit VALU address
-  // computation per access
-  constexpr bool SA = true;
-  int wvu = wv;
-  if constexpr (SA) wvu = __builtin_amdgcn_readfirstlane(wv);
-  const unsigned vo_tw = (unsigned)(tq * a.Tp + fl) * 8u;   // TW[j][k = tq + 4s][t0 + fl]
-  const unsigned vo_cx = (unsigned)(tq * a.Fp + f) * 8u;    // plane[t0 + tq + 4i][f]
-  [[maybe_unused]] const unsigned vo_img = (unsigned)lane * 16u;            // image piece[lane]
-  // Cx of frame tile tt (raw-buffer form; the flat form without SA)
-  auto load_cx = [&](int tt, double (&c)[4][4]) {
-    const int t0 = tt * 16;
-    if constexpr (CXI) {
-      // the tile's 8 KB record: piece 2 i + h holds (cx00, cx11) (h = 0) or
-      // (cxr, cxi) (h = 1) of the lane's point i
-      const __amdgpu_buffer_rsrc_t rc =
-          buf_rsrc((const double *)(a.cxp + ((size_t)btile * a.nttp + tt) * 512));
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const buf_d2 d = buf_ld2<2>(rc, vo_img, (unsigned)(2 * i) * 1024u);
-        const buf_d2 o = buf_ld2<2>(rc, vo_img, (unsigned)(2 * i + 1) * 1024u);
-        c[0][i] = d.x;
-        c[1][i] = d.y;
-        c[2][i] = o.x;
-        c[3][i] = o.y;
-      }
-      return;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if constexpr (SA) {
-        const size_t ro = (size_t)t0 * a.Fp;
-        const unsigned so = (unsigned)(4 * i * a.Fp) * 8u;
-        c[0][i] = buf_ld<2>(buf_rsrc(a.cx00 + ro), vo_cx, so);
-        c[1][i] = buf_ld<2>(buf_rsrc(a.cx11 + ro), vo_cx, so);
-        c[2][i] = buf_ld<2>(buf_rsrc(a.cxr + ro), vo_cx, so);
-        c[3][i] = buf_ld<2>(buf_rsrc(a.cxi + ro), vo_cx, so);
-      } else {
-        const size_t off = (size_t)(t0 + tq + 4 * i) * a.Fp + f;
-        c[0][i] = __builtin_nontemporal_load(a.cx00 + off);
-        c[1][i] = __builtin_nontemporal_load(a.cx11 + off);
-        c[2][i] = __builtin_nontemporal_load(a.cxr + off);
-        c[3][i] = __builtin_nontemporal_load(a.cxi + off);
-      }
-    }
-  };
-  // CXE (J > 4): the next tile's Cx loads are issued right after this
-  // tile's last point consumed its Cx (in the pipelined point loop), so they
-  // land during the last point's MFMAs and the next tile's V tile (J = 6 /
-  // 8: 0.790 / 0.961 -> 0.749 / 0.944 ms; at J = 4, two waves per SIMD,
-  // 0.361 -> 0.368 ms: not used there)
-  constexpr bool CXE = J > 4;
-  double cxv[4][4];
-  if (CXE && tb + wvu < te) load_cx(tb + wvu, cxv);
-  for (int tt = tb + wvu; tt < te; tt += 4) {
-    const int t0 = tt * 16;
-    int lofs = 0;  // launder: re-read the loop-invariant LDS data per tile
-    asm volatile("" : "+v"(lofs));
-    // all TW operands in flight before the first MFMA (the scheduler would
-    // otherwise pair each load with its MFMA and wait on every one); with more
-    // than 32 operands (J > 4 or K > 32 at J = 4) the sources beyond the first
-    // 32 operands load next to their own MFMAs
-    // (VR: none up front -- the V loop below pipelines them source by source)
-    // CP: more operands than that (J <= 4 at K >= 64): the V tiles as one
-    // pipeline of 8-MFMA chunks over (source, k), each chunk's TW operands
-    // issued two chunks ahead -- the per-source inline loads left each
-    // source's load latency exposed (J = 4, K = 128: 2.70 ms).  (The same
-    // pipeline for the VR loop with W from L2, J > 4 at K = 128, crashes
-    // ROCm 7.2's compiler at distance 2 and spills 0.4-1.8 KB per lane at 1.)
-    constexpr bool CP = !VR && J * NKS > 32;
-    constexpr int JA = (VR || CP) ? 1 : (J * NKS <= 32) ? J : (32 / NKS > 0 ? 32 / NKS : 1);
-    double twv[JA][NKS];
-    if constexpr (TWI) {
-      // the tile's TW image: piece (j, u) holds the operands of the k-steps
-      // s = 2 u (.x) and 2 u + 1 (.y) of source j
-      static_assert(JA == J, "every source preloaded");
-      const __amdgpu_buffer_rsrc_t rt =
-          buf_rsrc((const double *)(a.twp + (size_t)tt * (J * (NKS / 2) * 64)));
-#pragma unroll
-      for (int j = 0; j < J; ++j)
-#pragma unroll
-        for (int u = 0; u < NKS / 2; ++u) {
-          const buf_d2 h = buf_ld2<0>(rt, vo_img, (unsigned)(j * (NKS / 2) + u) * 1024u);
-          twv[j][2 * u] = h.x;
-          twv[j][2 * u + 1] = h.y;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < ((CP || TWI) ? 0 : JA); ++j) {
-      const double *tw = a.TW + ((size_t)j * KP + tq) * a.Tp + t0 + fl;
-#pragma unroll
-      for (int s = 0; s < NKS; ++s)
-        twv[j][s] = SA ? buf_ld<0>(buf_rsrc(a.TW + t0), vo_tw, (unsigned)((j * KP + 4 * s) * a.Tp) * 8u)
-                       : tw[(size_t)(4 * s) * a.Tp];
-    }
-    if constexpr (!CXE) load_cx(tt, cxv);  // this tile's Cx (in flight with the TW operands)
-    __builtin_amdgcn_sched_barrier(0);
-    d4 v[J];
-    if constexpr (CP) {
-      constexpr int CH = 8, CPS = NKS / CH, NCH = J * CPS, PD = 2;   // chunks, prefetch distance
-      static_assert(NKS % CH == 0, "k chunks of 8");
-      double ta[PD + 1][CH], wa[PD + 1][WL ? 1 : CH];
-      auto ld = [&](int u, int sl) {
-        const int j = u / CPS, s0 = (u % CPS) * CH;
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-          const int s = s0 + c;
-          ta[sl][c] = buf_ld<0>(buf_rsrc(a.TW + t0), vo_tw, (unsigned)((j * KP + 4 * s) * a.Tp) * 8u);
-          if constexpr (!WL)
-            wa[sl][c] = a.Wkf[lofs + ((size_t)j * KP + tq + 4 * s) * a.Fp + f];
-        }
-      };
-#pragma unroll
-      for (int u = 0; u < PD; ++u) ld(u, u);
-#pragma unroll
-      for (int u = 0; u < NCH; ++u) {
-        if (u + PD < NCH) ld(u + PD, (u + PD) % (PD + 1));
-        __builtin_amdgcn_sched_barrier(0);
-        const int j = u / CPS, s0 = (u % CPS) * CH, sl = u % (PD + 1);
-        if (s0 == 0) v[j] = d4{0.0, 0.0, 0.0, 0.0};
-        const double *sw = s_w + lofs + (j * KP + tq) * 16 + fl;
-#pragma unroll
-        for (int c = 0; c < CH; ++c)
-          v[j] = mfma4(ta[sl][c], WL ? sw[4 * (s0 + c) * 16] : wa[sl][WL ? 0 : c], v[j]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    } else if constexpr (VR && !(WL || NKS <= 16)) {
-      // J > 4 at K = 128 (W from L2): a runtime loop over the sources, each
-      // source's V tile a 4-chunk pipeline of 8 MFMAs with the next chunk's TW
-      // and W operands in flight (the last chunk prefetches source j + 1's
-      // first), written to the VST slab as soon as it is formed -- the fully
-      // unrolled form crashes or spills (CP above); the inline loads left one
-      // L2 round trip per source exposed (J = 8, K = 128: 6.85 ms)
-      slab_fence0();   // the previous tile's last reads before these writes
-      constexpr int CH = 8, CPS = NKS / CH;
-      double ta[2][CH], wa[2][CH];
-      auto ld = [&](int j, int s0, int sl) {
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-          ta[sl][c] = buf_ld<0>(buf_rsrc(a.TW + t0), vo_tw, (unsigned)((j * KP + 4 * (s0 + c)) * a.Tp) * 8u);
-          wa[sl][c] = a.Wkf[lofs + ((size_t)j * KP + tq + 4 * (s0 + c)) * a.Fp + f];
-        }
-      };
-      ld(0, 0, 0);
-#pragma unroll 1
-      for (int j = 0; j < J; ++j) {
-        d4 vj = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int c = 0; c < CPS; ++c) {
-          const int sl = c & 1;
-          if (c + 1 < CPS)
-            ld(j, (c + 1) * CH, sl ^ 1);
-          else if (j + 1 < J)
-            ld(j + 1, 0, sl ^ 1);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int cc = 0; cc < CH; ++cc) vj = mfma4(ta[sl][cc], wa[sl][cc], vj);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) wrv[i * 4 * S::VGS + (j >> 2) * 64 + (j & 3)] = vj[i];
-      }
-    } else if constexpr (VR) {
-      // source j + 1's TW operands in flight while source j's MFMAs run; the
-      // barriers keep the scheduler from hoisting every source's loads (at
-      // K = 64 / 128 they alone would fill the register file)
-      // (W from L2 at K = 128, J = 8: no prefetch, or the operands alone spill)
-      constexpr bool PFS = WL || NKS <= 16;
-      double tn[NKS];
-#pragma unroll
-      for (int s = 0; s < NKS; ++s) tn[s] = twv[0][s];
-#pragma unroll
-      for (int j = 0; j < J; ++j) {
-        double tc[NKS];
-#pragma unroll
-        for (int s = 0; s < NKS; ++s)
-          tc[s] = PFS || j == 0 ? tn[s]
-                               : buf_ld<0>(buf_rsrc(a.TW + t0), vo_tw, (unsigned)((j * KP + 4 * s) * a.Tp) * 8u);
-        if (PFS && j + 1 < J) {
-#pragma unroll
-          for (int s = 0; s < NKS; ++s)
-            tn[s] = buf_ld<0>(buf_rsrc(a.TW + t0), vo_tw, (unsigned)(((j + 1) * KP + 4 * s) * a.Tp) * 8u);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        v[j] = d4{0.0, 0.0, 0.0, 0.0};
-        const double *sw = s_w + lofs + (j * KP + tq) * 16 + fl;
-        const double *gw = a.Wkf + lofs + ((size_t)j * KP + tq) * a.Fp + f;
-#pragma unroll
-        for (int s = 0; s < NKS; ++s)
-          v[j] = mfma4(tc[s], WL ? sw[4 * s * 16] : gw[(size_t)(4 * s) * a.Fp], v[j]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < ((VR || CP) ? 0 : J); ++j) {
-      v[j] = d4{0.0, 0.0, 0.0, 0.0};
-      const double *sw = s_w + lofs + (j * KP + tq) * 16 + fl;
-      const double *gw = a.Wkf + lofs + ((size_t)j * KP + tq) * a.Fp + f;
-      const double *tw = a.TW + ((size_t)j * KP + tq) * a.Tp + t0 + fl;
-#pragma unroll
-      for (int s = 0; s < NKS; ++s)
-        v[j] = mfma4(j < JA ? twv[j < JA ? j : 0][s] : tw[(size_t)(4 * s) * a.Tp],
-                     WL ? sw[4 * s * 16] : gw[(size_t)(4 * s) * a.Fp], v[j]);
-    }
-    if constexpr (VST && (WL || NKS <= 16)) {   // (else written by the loop above)
-      slab_fence0();   // the previous tile's last reads before these writes
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < J; ++j) wrv[i * 4 * S::VGS + (j >> 2) * 64 + (j & 3)] = v[j][i];
-    }
-    const double *cj = s_cj + lofs + fl;
-    // the lane's Sigma_x coefficients: LDS (re-read per tile) or, with
-    // CJR, the registers loaded once per kernel
-    auto cjv = [&](int j, int c) { return CJR ? cjr[j][c] : cj[(j * 4 + c) * 16]; };
-    // point i of the lane's four (frame t0 + tq + 4 i): Sigma_x, its guarded
-    // inverse, loglik, P = Cx S, N = S Cx S - S, and rho stored; no LDS
-    auto pt_valu = [&](int i, double (&P)[8], double (&N)[4]) {
-      const int t = t0 + tq + 4 * i;
-      const double x00 = cxv[0][i], x11 = cxv[1][i], xr = cxv[2][i], xi = cxv[3][i];
-      double V[J];
-#pragma unroll
-      for (int j = 0; j < J; ++j) V[j] = VST ? wrv[i * 4 * S::VGS + (j >> 2) * 64 + (j & 3)] : v[j][i];
-      // Sigma_x = sum_r V_r a_r a_r^H + PSD I   (compute_suff_stat :613-652)
-      double d0 = psd, d1 = psd, ore = 0.0, oim = 0.0;
-#pragma unroll
-      for (int j = 0; j < J; ++j) {
-        d0 += cjv(j, 0) * V[j];
-        d1 += cjv(j, 1) * V[j];
-        ore += cjv(j, 2) * V[j];
-        oim += cjv(j, 3) * V[j];
-      }
-      // inv_herm_mat_2d (signalTools.py:177-194)
-      double det = d0 * d1 - (ore * ore + oim * oim);
-      const double dg = det + kEps;
-      const double sg = dg > 0.0 ? 1.0 : (dg < 0.0 ? -1.0 : 0.0);
-      det = sg * fmax(fabs(det), kEps);
-      const double rdet = rcp_nr(det);
-      const double i0 = d1 * rdet, i1 = d0 * rdet, ior = -ore * rdet, ioi = -oim * rdet;
-      if (fvalid && t < a.T) {
-        // log(det pi) as mantissa product x 2^exponent (v_frexp_*: 0, inf and
-        // NaN pass through the mantissa, so log(lm) gives -inf / inf / NaN as
-        // log() would; a negative det, which the guard only lets through for
-        // a Sigma_x that is not positive semi-definite, is flagged in xmin)
-        const double x = det * M_PI;
-        lev += (double)__builtin_amdgcn_frexp_exp(x);
-        lm *= __builtin_amdgcn_frexp_mant(x);
-        xmin = fmin(xmin, x);
-        ll += i0 * x00 + i1 * x11 + 2.0 * (ior * xr + ioi * xi);
-      }
-      // P = Cx S, N = S Cx S - S = P^H S - S
-      P[0] = x00 * i0 + xr * ior + xi * ioi;   // p00r
-      P[1] = xi * ior - xr * ioi;              // p00i
-      P[2] = x00 * ior + xr * i1;              // p01r
-      P[3] = x00 * ioi + xi * i1;              // p01i
-      P[4] = xr * i0 + x11 * ior;              // p10r
-      P[5] = -xi * i0 - x11 * ioi;             // p10i
-      P[6] = xr * ior + xi * ioi + x11 * i1;   // p11r
-      P[7] = xr * ioi - xi * ior;              // p11i
-      N[0] = P[0] * i0 + (P[4] * ior - P[5] * ioi) - i0;          // n00
-      N[1] = (P[2] * ior + P[3] * ioi) + P[6] * i1 - i1;          // n11
-      N[2] = P[0] * ior + P[1] * ioi + P[4] * i1 - ior;           // n01r
-      N[3] = P[0] * ioi - P[1] * ior - P[5] * i1 - ioi;           // n01i
-      // hat_W[j] = mean over the ranks of j of |V^2 a_r^H N a_r + V| (:727-729,
-      // :413-414) in the rank-merged form |V^2 (sum_r a_r^H N a_r) / rk + V|
-      // (each rank's term is a posterior second moment, >= 0: the two forms
-      // differ by rounding), with sum_r a_r^H N a_r = tr(N sum_r a_r a_r^H) from
-      // the Sigma_x coefficients; stored as rho = (hat_W / vm^2) vm,
-      // vm = max(V, eps): the FB ratio of update_spectral_components
-      // (:1521-1575, N1), formed where V is at hand
-      // Since V >= 0, rho = |V^2 q + V| / max(V, eps) = |V q + 1| min(V / eps, 1)
-      // (q = a^H N a / rk): no reciprocal (the two forms differ by rounding)
-      // NF: the factors 2 (the off-diagonal pair) and 1 / rk (a uniform rank)
-      // folded into N once per point instead of once per source
-      double Nf[4];
-      {
-        const double ir = RKU ? 1.0 / (double)RKU : 1.0;
-        Nf[0] = N[0] * ir;
-        Nf[1] = N[1] * ir;
-        Nf[2] = N[2] * (2.0 * ir);
-        Nf[3] = N[3] * (2.0 * ir);
-      }
-#pragma unroll
-      for (int j = 0; j < J; ++j) {
-        const double Vj = V[j];
-        double q;
-        if constexpr (NF) {
-          q = cjv(j, 0) * Nf[0] + cjv(j, 1) * Nf[1] + cjv(j, 2) * Nf[2] + cjv(j, 3) * Nf[3];
-          if constexpr (RKU == 0) q *= inv_rk[j];
-        } else {
-          const double qa = (cjv(j, 0) * N[0] + cjv(j, 1) * N[1]) +
-                            2.0 * (cjv(j, 2) * N[2] + cjv(j, 3) * N[3]);
-          q = RKU == 1 ? qa : qa * inv_rk[j];
-        }
-        const double val = fabs(fma(Vj, q, 1.0)) * fmin(Vj * (1.0 / kEps), 1.0);
-        if constexpr (SA)
-          es_st<2>(val, buf_rsrc(a.hatW + ((size_t)j * a.Tp + t0) * a.Fp), vo_cx,
-                               (unsigned)(4 * i * a.Fp) * 8u);
-        else
-          __builtin_nontemporal_store(val, a.hatW + ((size_t)j * a.Tp + t) * a.Fp + f);
-      }
-    };
-    // point i's MFMA operands -> the wave's slab (reader layout)
-    auto pt_write = [&](int i, const double (&P)[8], const double (&N)[4]) {
-      if constexpr (VST) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          wpn[0 * 64 + c] = P[c];
-          wpn[1 * 64 + c] = P[4 + c];
-          wpn[2 * 64 + c] = N[c];
-        }
-        return;
-      }
-      double V[J];
-#pragma unroll
-      for (int j = 0; j < J; ++j) V[j] = v[j][i];
-#pragma unroll
-      for (int j = 0; j < J; ++j) wr[(j >> 2) * 64 + (j & 3)] = V[j];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        wr[(S::SP + 0) * 64 + c] = P[c];
-        wr[(S::SP + 1) * 64 + c] = P[4 + c];
-        wr[S::SN * 64 + c] = N[c];
-      }
-      if constexpr (!RP) {
-        int p = 0;
-#pragma unroll
-        for (int j1 = 0; j1 < J; ++j1)
-#pragma unroll
-          for (int j2 = j1; j2 < J; ++j2, ++p)
-            wr[(S::SV2 + (p >> 2)) * 64 + (p & 3)] = V[j1] * V[j2];
-      }
-    };
-    // SWP (J >= 4): the next point's VALU work sits between this point's slab
-    // reads and its MFMAs (J = 4 with the reader-formed pairs: 0.370 -> 0.367
-    // ms alone, 0.373 -> 0.3625 with CJR; with the writer-formed pairs it was
-    // neutral; at J > 4 the unpipelined form also tripped ROCm 7.2's
-    // AGPR-copy rewrite pass)
-    constexpr bool SWP = J >= 4;
-
-    auto slab_fence = [&]() {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    // the slab's operands of the 4 bin groups in flight at once, then the
-    // MFMAs (read -> wait -> MFMA one at a time left the LDS latency exposed);
-    // with SWP the next point's VALU work sits between the reads and the
-    // MFMAs (its slab writes after them)
-    auto mfma_pass = [&](int i, auto between) {
-      if constexpr (VST) {
-        // the bin groups in two halves (half the operands live)
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-          double w[2][Q], pn[2][3];
-#pragma unroll
-          for (int g2 = 0; g2 < 2; ++g2) {
-            const int g = 2 * hh + g2;
-#pragma unroll
-            for (int e = 0; e < Q; ++e) w[g2][e] = rdq[(4 * i + g) * S::VGS + vro[e]];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) pn[g2][q] = rpn[g * S::PGS + q * 64];
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          if (hh == 0) {
-            between();
-            __builtin_amdgcn_sched_barrier(0);
-          }
-#pragma unroll
-          for (int g2 = 0; g2 < 2; ++g2) {
-            const int g = 2 * hh + g2;
-#pragma unroll
-            for (int vg = 0; vg < NVG; ++vg) {
-              xacc[g][vg][0] = mfma44(w[g2][4 * vg], pn[g2][0], xacc[g][vg][0]);
-              xacc[g][vg][1] = mfma44(w[g2][4 * vg], pn[g2][1], xacc[g][vg][1]);
-            }
-#pragma unroll
-            for (int h = 0; h < NPG; ++h)
-              if (rp_live<J>(h))
-                pacc[g][h] = mfma44(w[g2][rp_base<Q>(h)] * w[g2][(rp_base<Q>(h) + rp_d<Q>(h)) & (Q - 1)],
-                                    pn[g2][2], pacc[g][h]);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        return;
-      }
-      if constexpr (RP) {
-        // rotated sources W_e, then P lo / hi and N, of the 4 bin groups
-        double w[4][Q], pn[4][3];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-#pragma unroll
-          for (int e = 0; e < Q; ++e) w[g][e] = rdq[g * S::GS + vro[e]];
-#pragma unroll
-          for (int q = 0; q < 3; ++q) pn[g][q] = rd[g * S::GS + (S::SP + q) * 64];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (SWP) {
-          between();
-          __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-#pragma unroll
-          for (int vg = 0; vg < NVG; ++vg) {
-            xacc[g][vg][0] = mfma44(w[g][4 * vg], pn[g][0], xacc[g][vg][0]);
-            xacc[g][vg][1] = mfma44(w[g][4 * vg], pn[g][1], xacc[g][vg][1]);
-          }
-#pragma unroll
-          for (int h = 0; h < NPG; ++h)
-            if (rp_live<J>(h))
-              pacc[g][h] = mfma44(w[g][rp_base<Q>(h)] * w[g][(rp_base<Q>(h) + rp_d<Q>(h)) & (Q - 1)],
-                                  pn[g][2], pacc[g][h]);
-        }
-        return;
-      }
-      double opd[4][S::NSET];
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int q = 0; q < S::NSET; ++q) opd[g][q] = rd[g * S::GS + q * 64];
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (SWP) {
-        between();
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-#pragma unroll
-        for (int vg = 0; vg < NVG; ++vg) {
-          xacc[g][vg][0] = mfma44(opd[g][vg], opd[g][S::SP], xacc[g][vg][0]);
-          xacc[g][vg][1] = mfma44(opd[g][vg], opd[g][S::SP + 1], xacc[g][vg][1]);
-        }
-#pragma unroll
-        for (int h = 0; h < NPG; ++h)
-          pacc[g][h] = mfma44(opd[g][S::SV2 + h], opd[g][S::SN], pacc[g][h]);
-      }
-    };
-    if constexpr (SWP) {
-      double Pc[8], Nc[4];
-      pt_valu(0, Pc, Nc);
-      pt_write(0, Pc, Nc);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        slab_fence();   // point i's slab writes land before the cross-lane reads
-        double Pn[8], Nn[4];
-        mfma_pass(i, [&]() {
-          if (i < 3) pt_valu(i + 1, Pn, Nn);
-          if (CXE && i == 2 && tt + 4 < te) load_cx(tt + 4, cxv);
-        });
-        slab_fence();   // point i + 1's writes must not overtake point i's reads
-        if (i < 3) pt_write(i + 1, Pn, Nn);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        double P[8], N[4];
-        pt_valu(i, P, N);
-        pt_write(i, P, N);
-        slab_fence();   // the slab writes land before the cross-lane reads
-        mfma_pass(i, []() {});
-        slab_fence();   // the next point's writes must not overtake these reads
-      }
-    }
-    // keep lm in [0.5, 1): at most 4 factors >= 0.5 were multiplied in
-    lev += (double)__builtin_amdgcn_frexp_exp(lm);
-    lm = __builtin_amdgcn_frexp_mant(lm);
-  }
-  ll += (log(lm) + lev * M_LN2) + (xmin < 0.0 ? NAN : 0.0);
-
-  // epilogue: lane (X = m, b, Y = n) holds, per bin group g, the 4x4 blocks
-  // D[m][n] of bin f0 + 4g + b: cross (j = m, c = 4h + n), pairs (p = 4h + m, c = n)
-  // (VR: pair m of group (base, d); the four waves' sums go through LDS one
-  // bin group at a time, [4][NACC][4], to fit the smaller slab allocation)
-#pragma unroll
-  for (int mm = 1; mm < 64; mm <<= 1) ll += __shfl_xor(ll, mm, 64);
-  int tide = tid;   // (launder: see tidp)
-  asm volatile("" : "+v"(tide));
-  const int lanee = tide & 63, wve = tide >> 6;
-  if constexpr (VR) {
-    static_assert(4 * NACC * 4 <= 4 * S::SLAB, "VR epilogue fits the slabs");
-    const int m = lanee >> 4, bb = (lanee >> 2) & 3, n = lanee & 3;
-    double *red = s_slab;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      __syncthreads();  // (g = 0: the slabs' last reads; else the previous group's sums)
-#pragma unroll
-      for (int vg = 0; vg < NVG; ++vg) {
-        const int j = 4 * vg + m;
-        if (j < J) {
-          red[((wve * NACC) + 4 * NP + 8 * j + n) * 4 + bb] = xacc[g][vg][0];
-          red[((wve * NACC) + 4 * NP + 8 * j + 4 + n) * 4 + bb] = xacc[g][vg][1];
-        }
-      }
-#pragma unroll
-      for (int h = 0; h < NPG; ++h) {
-        const int p = rp_pair<J>(h, m);
-        if (p >= 0) red[((wve * NACC) + 4 * p + n) * 4 + bb] = pacc[g][h];
-      }
-      __syncthreads();
-      for (int idx = tide; idx < NACC * 4; idx += 256) {
-        const int ac = idx >> 2, ff = idx & 3;
-        const double x = red[(0 * NACC + ac) * 4 + ff] + red[(1 * NACC + ac) * 4 + ff] +
-                         red[(2 * NACC + ac) * 4 + ff] + red[(3 * NACC + ac) * 4 + ff];
-        a.part[((size_t)slot * a.Fp + f0 + 4 * g + ff) * NACC + ac] = x;
-      }
-    }
-    if (lanee == 0) s_ll[wve] = ll;
-    __syncthreads();
-    if (tide == 0)
-      a.llpart[slot * a.nft + btile] = ((s_ll[0] + s_ll[1]) + s_ll[2]) + s_ll[3];
-  } else {
-  __syncthreads();  // s_red aliases the W tile and the slabs
-  double *red = s_red + wve * NACC * 16;
-  {
-    const int m = lanee >> 4, bb = (lanee >> 2) & 3, n = lanee & 3;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int bin = 4 * g + bb;
-#pragma unroll
-      for (int vg = 0; vg < NVG; ++vg) {
-        const int j = 4 * vg + m;
-        if (j < J) {
-          red[(4 * NP + 8 * j + n) * 16 + bin] = xacc[g][vg][0];
-          red[(4 * NP + 8 * j + 4 + n) * 16 + bin] = xacc[g][vg][1];
-        }
-      }
-#pragma unroll
-      for (int h = 0; h < NPG; ++h) {
-        const int p = rp_pair<J>(h, m);
-        if (p >= 0) red[(4 * p + n) * 16 + bin] = pacc[g][h];
-      }
-    }
-  }
-  if (lanee == 0) s_ll[wve] = ll;
-  __syncthreads();
-  for (int idx = tide; idx < NACC * 16; idx += 256) {
-    const int ac = idx >> 4, ff = idx & 15;
-    const double x = s_red[(0 * NACC + ac) * 16 + ff] + s_red[(1 * NACC + ac) * 16 + ff] +
-                     s_red[(2 * NACC + ac) * 16 + ff] + s_red[(3 * NACC + ac) * 16 + ff];
-    a.part[((size_t)slot * a.Fp + f0 + ff) * NACC + ac] = x;
-  }
-  if (tide == 0)
-    a.llpart[slot * a.nft + btile] = ((s_ll[0] + s_ll[1]) + s_ll[2]) + s_ll[3];
-  }
-  // the next segment's prologue rewrites the W tile, the slabs and s_cj that
-  // this epilogue (s_red / red alias them) and this segment's tiles read
-  __syncthreads();
-  if (left <= 0) break;
-  // the next bin tile from its first quad-step: this block is the first to
-  // meet it, so the segment is the bin tile's slot 0
-  const int nq = min(a.es.Q, left);
-  ++btile;
-  slot = 0;
-  tb = a.tbase;
-  te = min(tb + 4 * nq, a.ntt);
-  left -= nq;
-  }  // segments
-}
-
-// ---------------------------------------------------------------- E-step, J > 8
-// More than 8 sources (up to kMaxJ): the statistics no longer fit the
-// single-pass kernel's registers (J (J + 1) / 2 pair and 8 J cross sums per
-// bin), so the E-step runs in two passes over a scratch copy of its point
-// quantities.  k_egen_point: one wave per 16 x 16 (bin, frame) tile, V_j on
-// 16x16x4 MFMA (the k_estep_mx / k_wiener tile), then per point Sigma_x, its
-// guarded inverse, the loglik term, P = Cx S, N = S Cx S - S and rho, with V_j,
-// N and P written to frame-major scratch planes.  k_egen_stats: one block per
-// (16-bin tile, frame chunk) sums the pair statistics V_j1 V_j2 N_c and the
-// cross statistics V_j P_c over its frames (tiles staged in LDS) into the
-// k_estep_mx partial layout, so k_mix reads it unchanged.
-struct GArgs {
-  double *V;     // [J][Tp][Fp]
-  double *NP;    // [12][Tp][Fp]: N0..N3, P0..P7
-  double *lw;    // [ntt][nft] per-wave loglik partials
-  int J;
-};
-
-// V_j of the tile: per source, its NKS TW / W operand pairs in chunks of CH,
-// every chunk's loads issued one chunk ahead of its MFMAs (two static register
-// buffers; the unrolled (source, chunk) sequence fixes which), so a wave waits
-// one memory round trip per chunk instead of one per MFMA.  The loads are
-// unconditional (a chunk past source J - 1 re-reads its last), so every path
-// reaches each wait with the same loads outstanding.
-template <int NKS>
-__global__ __launch_bounds__(64) void k_egen_point(const EArgs a, const GArgs g) {
-  HALT_GUARD(a.halt);
-  constexpr int CH = NKS < 8 ? NKS : 8, NCH = NKS / CH, NST = kMaxJ * NCH;
-  const int lane = threadIdx.x, fl = lane & 15, tq = lane >> 4;
-  const int tt = blockIdx.x, ft = blockIdx.y, t0 = tt * 16, f0 = ft * 16, f = f0 + fl;
-  const int J = g.J;
-  __shared__ double s_c[kMaxJ][4][16];   // Sigma_x coefficients of the tile's bins
-  __shared__ double s_irk[kMaxJ];
-  double ta[2][CH], wa[2][CH];
-  auto load = [&](int buf, int st) {
-    const int j = min(st / NCH, J - 1), s0 = (st % NCH) * CH;
-    const double *tw = a.TW + ((size_t)j * a.KP + tq + 4 * s0) * a.Tp + t0 + fl;
-    const double *wk = a.Wkf + ((size_t)j * a.KP + tq + 4 * s0) * a.Fp + f;
-#pragma unroll
-    for (int u = 0; u < CH; ++u) {
-      ta[buf][u] = tw[(size_t)(4 * u) * a.Tp];
-      wa[buf][u] = wk[(size_t)(4 * u) * a.Fp];
-    }
-  };
-  load(0, 0);
-  // lane (fl, tq): the coefficients of sources tq, tq + 4, ... of bin fl
-  for (int j = tq; j < J; j += 4) {
-    double al = 0, be = 0, gr = 0, gi = 0;
-    for (int r = a.roff[j]; r < a.roff[j + 1]; ++r) {
-      const double2 a0 = a.A[(size_t)(2 * r) * a.Fp + f];
-      const double2 a1 = a.A[(size_t)(2 * r + 1) * a.Fp + f];
-      al += a0.x * a0.x + a0.y * a0.y;
-      be += a1.x * a1.x + a1.y * a1.y;
-      gr += a0.x * a1.x + a0.y * a1.y;
-      gi += a0.y * a1.x - a0.x * a1.y;
-    }
-    s_c[j][0][fl] = al;
-    s_c[j][1][fl] = be;
-    s_c[j][2][fl] = gr;
-    s_c[j][3][fl] = gi;
-  }
-  if (lane < J) s_irk[lane] = 1.0 / (double)(a.roff[lane + 1] - a.roff[lane]);
-  d4 v[kMaxJ];
-#pragma unroll
-  for (int j = 0; j < kMaxJ; ++j) v[j] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int st = 0; st < NST; ++st) {
-    const int j = st / NCH, cur = st & 1;
-    if (j >= J) break;   // (wave-uniform)
-    if (st + 1 < NST) load(cur ^ 1, st + 1);
-    asm volatile("" ::: "memory");   // (keeps the prefetch here, not sunk past the next break)
-#pragma unroll
-    for (int u = 0; u < CH; ++u) v[j] = mfma4(ta[cur][u], wa[cur][u], v[j]);
-  }
-  __syncthreads();
-  const size_t plane = (size_t)a.Tp * a.Fp;
-  const double psd = a.psd[f];
-  double ll = 0.0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int t = t0 + tq + 4 * i;
-    const size_t o = (size_t)t * a.Fp + f;
-    const double x00 = a.cx00[o], x11 = a.cx11[o], xr = a.cxr[o], xi = a.cxi[o];
-    double d0 = psd, d1 = psd, ore = 0.0, oim = 0.0;
-#pragma unroll
-    for (int j = 0; j < kMaxJ; ++j)
-      if (j < J) {
-        d0 += s_c[j][0][fl] * v[j][i];
-        d1 += s_c[j][1][fl] * v[j][i];
-        ore += s_c[j][2][fl] * v[j][i];
-        oim += s_c[j][3][fl] * v[j][i];
-      }
-    // inv_herm_mat_2d (signalTools.py:177-194)
-    double det = d0 * d1 - (ore * ore + oim * oim);
-    const double dg = det + kEps;
-    det = (dg > 0.0 ? 1.0 : (dg < 0.0 ? -1.0 : 0.0)) * fmax(fabs(det), kEps);
-    const double rdet = rcp_nr(det);
-    const double i0 = d1 * rdet, i1 = d0 * rdet, ior = -ore * rdet, ioi = -oim * rdet;
-    if (f < a.F && t < a.T) ll += log(det * M_PI) + (i0 * x00 + i1 * x11 + 2.0 * (ior * xr + ioi * xi));
-    double P[8], N[4];
-    P[0] = x00 * i0 + xr * ior + xi * ioi;
-    P[1] = xi * ior - xr * ioi;
-    P[2] = x00 * ior + xr * i1;
-    P[3] = x00 * ioi + xi * i1;
-    P[4] = xr * i0 + x11 * ior;
-    P[5] = -xi * i0 - x11 * ioi;
-    P[6] = xr * ior + xi * ioi + x11 * i1;
-    P[7] = xr * ioi - xi * ior;
-    N[0] = P[0] * i0 + (P[4] * ior - P[5] * ioi) - i0;
-    N[1] = (P[2] * ior + P[3] * ioi) + P[6] * i1 - i1;
-    N[2] = P[0] * ior + P[1] * ioi + P[4] * i1 - ior;
-    N[3] = P[0] * ioi - P[1] * ior - P[5] * i1 - ioi;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) g.NP[c * plane + o] = N[c];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) g.NP[(4 + c) * plane + o] = P[c];
-#pragma unroll
-    for (int j = 0; j < kMaxJ; ++j)
-      if (j < J) {
-        const double Vj = v[j][i];
-        g.V[j * plane + o] = Vj;
-        // rho = |V^2 q + V| / max(V, eps) = |V q + 1| min(V / eps, 1), q the
-        // rank-merged quadratic form (as k_estep_mx)
-        const double q = ((s_c[j][0][fl] * N[0] + s_c[j][1][fl] * N[1]) +
-                          2.0 * (s_c[j][2][fl] * N[2] + s_c[j][3][fl] * N[3])) * s_irk[j];
-        a.hatW[j * plane + o] = fabs(fma(Vj, q, 1.0)) * fmin(Vj * (1.0 / kEps), 1.0);
-      }
-  }
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) ll += __shfl_xor(ll, m, 64);
-  if (lane == 0) g.lw[(size_t)tt * a.nft + ft] = ll;
-}
-
-// The statistics as 16x16x4 FP64 MFMAs per bin, frames as the k dimension:
-// with A[m = j1][k = t] = V_j1(t) and B[k = t][n = j2] = V_j2(t) N_c(t),
-// D[j1][j2] accumulates the pair sums of component c for all (j1, j2) at
-// once (the j1 > j2 half is discarded), and B[k = t][n = c] = P_c(t) gives
-// the cross sums D[j][c].  Lane (fl, tq) supplies the A and B operands of
-// row/column fl and frame tq from one LDS read of V_fl(t).  Block = 8 waves
-// on one (16-bin tile, frame chunk); wave wv owns bins 2 wv, 2 wv + 1 (five
-// 16x16 accumulators each).  A frame tile's J + 12 planes are staged point-
-// major in LDS ([16 frames][16 bins][RS], RS = (J + 12) | 1 so the 16 rows a
-// wave reads land on distinct banks), the next tile's values already in
-// flight in registers while the current one is summed.  (Was VALU pair FMAs
-// over the same staged tile at 5.48 ms for J = 16 at C3's size;
-// profiles/r6_struct_J16K32_sum.txt.)
-constexpr int kEgsThreads = 512;
-constexpr int kEgsRows = (kMaxJ + 12) | 1;
-__global__ __launch_bounds__(kEgsThreads) void k_egen_stats(const EArgs a, const GArgs g) {
-  HALT_GUARD(a.halt);
-  const int J = g.J, NP = J * (J + 1) / 2, NACC = 4 * NP + 8 * J;
-  const int tid = threadIdx.x, lane = tid & 63, fl = lane & 15, tq = lane >> 4;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ft = blockIdx.x, f0 = ft * 16, y = blockIdx.y;
-  const int nr = J + 12, RS = nr | 1;
-  extern __shared__ __attribute__((aligned(16))) double s_t[];   // [16 frames][16 bins][RS]
-  d4 acc[2][5];
-#pragma unroll
-  for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-    for (int c = 0; c < 5; ++c) acc[bi][c] = d4{0.0, 0.0, 0.0, 0.0};
-  const size_t plane = (size_t)a.Tp * a.Fp;
-  const int tb = a.tbase + y * a.tpc, te = min(tb + a.tpc, a.ntt);
-  // staging: thread tid carries point e = tid & 255 of rows r = 2 k + (tid >> 8)
-  // (wave-uniform: each row's plane is a scalar base, the point a 32-bit offset)
-  const int e = tid & 255, rh = __builtin_amdgcn_readfirstlane(tid >> 8), etl = e >> 4, efl = e & 15;
-  constexpr int kPre = (kMaxJ + 12 + 1) / 2;
-  double pre[2][kPre];   // two tiles in flight
-  // Loads and stores unconditional (rows past nr repeat the last; a tile
-  // past the chunk re-reads its last and is never staged), so every path
-  // reaches the loop head with the same two batches outstanding and the
-  // older one is waited for alone.
-  auto load = [&](double(&p)[kPre], int tt) {
-    const unsigned o = (unsigned)((min(tt, te - 1) * 16 + etl) * a.Fp + f0 + efl);
-#pragma unroll
-    for (int k = 0; k < kPre; ++k) {
-      const int r = min(2 * k + rh, nr - 1);
-      const double *base = r < J ? g.V + r * plane : g.NP + (r - J) * plane;
-      p[k] = __builtin_nontemporal_load(base + o);
-    }
-  };
-  auto stage = [&](const double(&p)[kPre]) {
-    __syncthreads();   // (the previous tile's reads)
-#pragma unroll
-    for (int k = 0; k < kPre; ++k) s_t[e * RS + min(2 * k + rh, nr - 1)] = p[k];
-    __syncthreads();
-  };
-  // MFMA operands: lane (fl, tq) reads V_fl (fl < J), N_0..3 and P_fl (fl <
-  // 8) of its point; out-of-range lanes read a valid slot and select zero
-  const int vcol = min(fl, J - 1), xcol = J + 4 + (fl & 7);
-  const bool vok = fl < J, xok = fl < 8;
-  auto sum_tile = [&]() {
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi) {
-      const int b = 2 * wv + bi;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const double *pt = s_t + ((4 * q + tq) * 16 + b) * RS;   // point (frame 4 q + tq, bin b)
-        const double vr = pt[vcol], pr = pt[xcol];
-        const double n0 = pt[J], n1 = pt[J + 1], n2 = pt[J + 2], n3 = pt[J + 3];
-        const double v = vok ? vr : 0.0, px = xok ? pr : 0.0;
-        acc[bi][0] = mfma4(v, v * n0, acc[bi][0]);
-        acc[bi][1] = mfma4(v, v * n1, acc[bi][1]);
-        acc[bi][2] = mfma4(v, v * n2, acc[bi][2]);
-        acc[bi][3] = mfma4(v, v * n3, acc[bi][3]);
-        acc[bi][4] = mfma4(v, px, acc[bi][4]);
-      }
-    }
-  };
-  if (tb < te) {
-    load(pre[0], tb);
-    load(pre[1], tb + 1);
-    for (int tt = tb; tt < te; tt += 2) {
-      stage(pre[0]);
-      load(pre[0], tt + 2);
-      sum_tile();
-      if (tt + 1 < te) {   // (block-uniform)
-        stage(pre[1]);
-        sum_tile();
-      }
-      load(pre[1], tt + 3);
-    }
-  }
-  // lane (fl, tq), register i: D[tq + 4 i][fl]
-#pragma unroll
-  for (int bi = 0; bi < 2; ++bi) {
-    double *out = a.part + ((size_t)(a.ybase + y) * a.Fp + f0 + 2 * wv + bi) * NACC;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int j1 = tq + 4 * i, j2 = fl;
-      if (j1 <= j2 && j2 < J) {
-        const int p = j1 * J - j1 * (j1 - 1) / 2 + j2 - j1;   // canonical index of (j1, j2)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) out[4 * p + c] = acc[bi][c][i];
-      }
-      if (j1 < J && fl < 8) out[4 * NP + 8 * j1 + fl] = acc[bi][4][i];
-    }
-  }
-  if (tid == 0) {   // the chunk's loglik, its tiles in order
-    double l = 0.0;
-    for (int tt = tb; tt < te; ++tt) l += g.lw[(size_t)tt * a.nft + ft];
-    a.llpart[(a.ybase + y) * a.nft + ft] = l;
-  }
-}
-
-// Fused many-source E-step (J > 8, KP <= 32): k_egen_point's point pass and
-// k_egen_stats' statistics in one block per (16-bin tile, frame chunk), V, N
-// and P never leaving the LDS slab (the two-pass form writes and re-reads
-// 28 planes, 4.6 GB at J = 16 and C3's size, and its point pass is bound by
-// those writes; profiles/r6_ab_egen_point.txt).  Per frame tile, three phases
-// between barriers:
-//   V      wave wv forms V of sources 2 wv, 2 wv + 1 on 16x16x4 MFMA (its W
-//          operands held in registers for the chunk, the next tile's TW
-//          operands loaded while the current tile is summed) into the slab;
-//   point  thread pair (2 e, 2 e + 1) owns point e: Sigma_x summed over the
-//          even / odd sources and combined across the pair, then both form
-//          the guarded inverse, P and N (the pair's halves write N and P to
-//          the slab) and rho of their own sources to global;
-//   stats  as k_egen_stats, from the slab.
-template <int NKS>
-__global__ __launch_bounds__(kEgsThreads) void k_egen_fused(const EArgs a, const GArgs g) {
-  HALT_GUARD(a.halt);
-  const int J = g.J, NP = J * (J + 1) / 2, NACC = 4 * NP + 8 * J;
-  const int tid = threadIdx.x, lane = tid & 63, fl = lane & 15, tq = lane >> 4;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ft = blockIdx.x, f0 = ft * 16, y = blockIdx.y;
-  const int nr = J + 12, RS = nr | 1;
-  const int tb = a.tbase + y * a.tpc, te = min(tb + a.tpc, a.ntt);
-  const size_t plane = (size_t)a.Tp * a.Fp;
-  extern __shared__ __attribute__((aligned(16))) double s_t[];   // [256 points][RS], then W
-  double *s_w = s_t + 256 * RS;           // [J][KP][16 bins]: the tile's W operands
-  // Sigma_x coefficients per (source, component, bin), the source stride 80
-  // doubles (= 16 mod 32 banks) so a half-wave's 16 bins x even / odd
-  // sources fall on 32 distinct banks
-  __shared__ double s_cfb[kMaxJ][80];
-  auto cf = [&](int b, int j, int c) -> double & { return s_cfb[j][16 * c + b]; };
-  __shared__ double s_irk[kMaxJ];
-  __shared__ double s_ll[kEgsThreads / 64];
-  if (tid < 16 * J) {
-    const int j = tid >> 4, b = tid & 15, f = f0 + b;
-    double al = 0, be = 0, gr = 0, gi = 0;
-    for (int r = a.roff[j]; r < a.roff[j + 1]; ++r) {
-      const double2 a0 = a.A[(size_t)(2 * r) * a.Fp + f];
-      const double2 a1 = a.A[(size_t)(2 * r + 1) * a.Fp + f];
-      al += a0.x * a0.x + a0.y * a0.y;
-      be += a1.x * a1.x + a1.y * a1.y;
-      gr += a0.x * a1.x + a0.y * a1.y;
-      gi += a0.y * a1.x - a0.x * a1.y;
-    }
-    cf(b, j, 0) = al;
-    cf(b, j, 1) = be;
-    cf(b, j, 2) = gr;
-    cf(b, j, 3) = gi;
-  }
-  if (tid < J) s_irk[tid] = 1.0 / (double)(a.roff[tid + 1] - a.roff[tid]);
-  constexpr int KP = 4 * NKS;
-  for (int idx = tid; idx < J * KP * 16; idx += kEgsThreads)
-    s_w[idx] = a.Wkf[(size_t)(idx >> 4) * a.Fp + f0 + (idx & 15)];
-  // V phase: sources ja, ja + 1 of this wave (clamped operands past J - 1)
-  const int ja = 2 * wv, jA = min(ja, J - 1), jB = min(ja + 1, J - 1);
-  const double *wA = s_w + (jA * KP + tq) * 16 + fl, *wB = s_w + (jB * KP + tq) * 16 + fl;
-  double tr[2][NKS];
-  auto load_tw = [&](int tt) {
-    const int t = min(tt, te - 1) * 16 + fl;
-    const double *tA = a.TW + ((size_t)jA * a.KP + tq) * a.Tp + t;
-    const double *tB = a.TW + ((size_t)jB * a.KP + tq) * a.Tp + t;
-#pragma unroll
-    for (int s = 0; s < NKS; ++s) {
-      tr[0][s] = tA[(size_t)(4 * s) * a.Tp];
-      tr[1][s] = tB[(size_t)(4 * s) * a.Tp];
-    }
-  };
-  // point phase: point e = (frame tl, bin b), half h (even / odd sources)
-  const int e = tid >> 1, h = tid & 1, tl = e >> 4, b = e & 15, f = f0 + b;
-  const double psd = a.psd[f];
-  double cx[4];
-  auto load_cx = [&](int tt) {
-    const size_t o = (size_t)(min(tt, te - 1) * 16 + tl) * a.Fp + f;
-    cx[0] = a.cx00[o];
-    cx[1] = a.cx11[o];
-    cx[2] = a.cxr[o];
-    cx[3] = a.cxi[o];
-  };
-  // statistics phase: v_mfma_f64_4x4x4_4b with block = bin (lane = 16 X +
-  // 4 b + Y: A[m=Y][k=X], B[k=X][n=Y], D[m=X][n=Y] of block b), k = frame.
-  // Wave wv owns bin quad bq = wv / 2 (bins 4 bq + b) and half hf = wv % 2:
-  // the pair blocks (j1 block jb1 <= j2 block jb2, 4 sources each) of
-  // components 2 hf, 2 hf + 1 and the cross blocks of sources 8 hf .. 8 hf + 7
-  // -- 24 one-double accumulators, upper-triangle blocks only (40% fewer
-  // matrix cycles than all 16 x 16 pairs on 16x16x4)
-  const int X = lane >> 4, Yl = lane & 3, bq = wv >> 1, hf = wv & 1;
-  const int sbin = 4 * bq + ((lane >> 2) & 3);
-  double accp[10][2], accx[2][2];
-#pragma unroll
-  for (int pb = 0; pb < 10; ++pb) accp[pb][0] = accp[pb][1] = 0.0;
-#pragma unroll
-  for (int u = 0; u < 2; ++u) accx[u][0] = accx[u][1] = 0.0;
-  double ll = 0.0;
-  if (tb < te) {
-    load_tw(tb);
-    load_cx(tb);
-  }
-  for (int tt = tb; tt < te; ++tt) {
-    __syncthreads();   // (the slab's previous readers; at the first tile, s_cf)
-    {
-      d4 vA = d4{0.0, 0.0, 0.0, 0.0}, vB = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int s = 0; s < NKS; ++s) {
-        vA = mfma4(tr[0][s], wA[64 * s], vA);
-        vB = mfma4(tr[1][s], wB[64 * s], vB);
-      }
-      load_tw(tt + 1);
-      if (ja < J)   // (wave-uniform)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s_t[((tq + 4 * i) * 16 + fl) * RS + ja] = vA[i];
-      if (ja + 1 < J)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s_t[((tq + 4 * i) * 16 + fl) * RS + ja + 1] = vB[i];
-    }
-    __syncthreads();
-    {
-      double *pt = s_t + e * RS;
-      double d0 = 0.0, d1 = 0.0, ore = 0.0, oim = 0.0, vk[kMaxJ / 2];
-#pragma unroll
-      for (int m = 0; m < kMaxJ / 2; ++m) {
-        const int j = 2 * m + h, jc = min(j, J - 1);
-        vk[m] = pt[jc];   // (kept for rho below)
-        const double vj = j < J ? vk[m] : 0.0;
-        d0 = fma(cf(b, jc, 0), vj, d0);
-        d1 = fma(cf(b, jc, 1), vj, d1);
-        ore = fma(cf(b, jc, 2), vj, ore);
-        oim = fma(cf(b, jc, 3), vj, oim);
-      }
-      d0 = psd + (d0 + __shfl_xor(d0, 1, 64));
-      d1 = psd + (d1 + __shfl_xor(d1, 1, 64));
-      ore += __shfl_xor(ore, 1, 64);
-      oim += __shfl_xor(oim, 1, 64);
-      const double x00 = cx[0], x11 = cx[1], xr = cx[2], xi = cx[3];
-      load_cx(tt + 1);
-      // inv_herm_mat_2d (signalTools.py:177-194)
-      double det = d0 * d1 - (ore * ore + oim * oim);
-      const double dg = det + kEps;
-      det = (dg > 0.0 ? 1.0 : (dg < 0.0 ? -1.0 : 0.0)) * fmax(fabs(det), kEps);
-      const double rdet = rcp_nr(det);
-      const double i0 = d1 * rdet, i1 = d0 * rdet, ior = -ore * rdet, ioi = -oim * rdet;
-      const int t = tt * 16 + tl;
-      if (h == 0 && f < a.F && t < a.T)
-        ll += log(det * M_PI) + (i0 * x00 + i1 * x11 + 2.0 * (ior * xr + ioi * xi));
-      double P[8], N[4];
-      P[0] = x00 * i0 + xr * ior + xi * ioi;
-      P[1] = xi * ior - xr * ioi;
-      P[2] = x00 * ior + xr * i1;
-      P[3] = x00 * ioi + xi * i1;
-      P[4] = xr * i0 + x11 * ior;
-      P[5] = -xi * i0 - x11 * ioi;
-      P[6] = xr * ior + xi * ioi + x11 * i1;
-      P[7] = xr * ioi - xi * ior;
-      N[0] = P[0] * i0 + (P[4] * ior - P[5] * ioi) - i0;
-      N[1] = (P[2] * ior + P[3] * ioi) + P[6] * i1 - i1;
-      N[2] = P[0] * ior + P[1] * ioi + P[4] * i1 - ior;
-      N[3] = P[0] * ioi - P[1] * ior - P[5] * i1 - ioi;
-      if (h == 0) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) pt[J + c] = N[c];
-      } else {
-#pragma unroll
-        for (int c = 0; c < 8; ++c) pt[J + 4 + c] = P[c];
-      }
-      const size_t o = (size_t)t * a.Fp + f;
-      // (sources past J - 1 clamp to J - 1 and store the very value its
-      // owner stores -- both halves hold bit-identical N -- so the stores
-      // need no lane-divergent branch)
-#pragma unroll
-      for (int m = 0; m < kMaxJ / 2; ++m) {
-        const int j = min(2 * m + h, J - 1);
-        // rho = |V q + 1| min(V / eps, 1), q the rank-merged quadratic form
-        const double q = ((cf(b, j, 0) * N[0] + cf(b, j, 1) * N[1]) +
-                          2.0 * (cf(b, j, 2) * N[2] + cf(b, j, 3) * N[3])) * s_irk[j];
-        const double vj = vk[m];   // (= pt[j]: the same clamped source)
-        __builtin_nontemporal_store(fabs(fma(vj, q, 1.0)) * fmin(vj * (1.0 / kEps), 1.0),
-                                    a.hatW + j * plane + o);
-      }
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int g = 0; g < 4; ++g) {
-      const double *pt = s_t + ((4 * g + X) * 16 + sbin) * RS;   // point (frame 4 g + X, bin sbin)
-      double va[4], bn[4][2], px[2];
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb) {
-        const int jj = 4 * jb + Yl;
-        const double v = pt[min(jj, J - 1)];
-        va[jb] = jj < J ? v : 0.0;
-      }
-      const double nc0 = pt[J + 2 * hf], nc1 = pt[J + 2 * hf + 1];
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb) {
-        bn[jb][0] = va[jb] * nc0;
-        bn[jb][1] = va[jb] * nc1;
-      }
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb) px[cb] = pt[J + 4 + 4 * cb + Yl];
-      // (the ten blocks spelled out: constant register indices)
-#define EGF_PB(pb, j1b, j2b)                                              \
-  if (4 * (j2b) < J) {   /* (wave-uniform) */                             \
-    accp[pb][0] = mfma44(va[j1b], bn[j2b][0], accp[pb][0]);              \
-    accp[pb][1] = mfma44(va[j1b], bn[j2b][1], accp[pb][1]);              \
-  }
-      EGF_PB(0, 0, 0) EGF_PB(1, 0, 1) EGF_PB(2, 0, 2) EGF_PB(3, 0, 3) EGF_PB(4, 1, 1)
-      EGF_PB(5, 1, 2) EGF_PB(6, 1, 3) EGF_PB(7, 2, 2) EGF_PB(8, 2, 3) EGF_PB(9, 3, 3)
-#undef EGF_PB
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        if (4 * (2 * hf + u) >= J) continue;   // (wave-uniform)
-        // (its own LDS read: selecting va[2 hf + u] became a scratch access)
-        const int jj = 4 * (2 * hf + u) + Yl;
-        const double vr = pt[min(jj, J - 1)], vs = jj < J ? vr : 0.0;
-        accx[u][0] = mfma44(vs, px[0], accx[u][0]);
-        accx[u][1] = mfma44(vs, px[1], accx[u][1]);
-      }
-    }
-  }
-  // lane (X, b, Y) holds D[X][Y] of its bin: pair (4 jb1 + X, 4 jb2 + Y),
-  // cross (source 4 jb + X, component 4 cb + Y)
-  {
-    double *out = a.part + ((size_t)(a.ybase + y) * a.Fp + f0 + sbin) * NACC;
-#pragma unroll
-    for (int pb = 0; pb < 10; ++pb) {
-      const int jb1 = pb < 4 ? 0 : pb < 7 ? 1 : pb < 9 ? 2 : 3;
-      const int jb2 = pb < 4 ? pb : pb < 7 ? pb - 3 : pb < 9 ? pb - 5 : 3;
-      const int j1 = 4 * jb1 + X, j2 = 4 * jb2 + Yl;
-      if (j1 <= j2 && j2 < J) {
-        const int p = j1 * J - j1 * (j1 - 1) / 2 + j2 - j1;   // canonical index of (j1, j2)
-        out[4 * p + 2 * hf] = accp[pb][0];
-        out[4 * p + 2 * hf + 1] = accp[pb][1];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int j = 4 * (2 * hf + u) + X;
-      if (j < J) {
-        out[4 * NP + 8 * j + Yl] = accx[u][0];
-        out[4 * NP + 8 * j + 4 + Yl] = accx[u][1];
-      }
-    }
-  }
-  // the chunk's loglik: lanes in order within a wave, then waves in order
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) ll += __shfl_xor(ll, m, 64);
-  if (lane == 0) s_ll[wv] = ll;
-  __syncthreads();
-  if (tid == 0) {
-    double l = 0.0;
-    for (int w = 0; w < kEgsThreads / 64; ++w) l += s_ll[w];
-    a.llpart[(a.ybase + y) * a.nft + ft] = l;
-  }
-}
-
 // sum_t TW[j][k][t] (for mean_t V_j = W_j . sum_t H_j, the hat_Rss diagonal term)
 __global__ void k_tw_rowsum(const double *__restrict__ TW, double *__restrict__ hsum, int T,
                             int Tp, const int *halt) {
@@ -1628,32 +194,6 @@ __global__ void k_tw_rowsum(const double *__restrict__ TW, double *__restrict__ 
     __syncthreads();
   }
   if (threadIdx.x == 0) hsum[blockIdx.x] = s[0];
-}
-
-// sum of the E-step's loglik partials [slot][bin tile]: the live entries
-// (slot < segments of the bin tile, fasst_esched.h) in index order, strided
-// over the 256 threads (a fixed order)
-__device__ __forceinline__ double ll_partial_sum(const double *__restrict__ llpart, const ESched es) {
-  double x = 0.0;
-  for (int i = threadIdx.x; i < es.nslot * es.nbt; i += 256) {
-    const int sl = i / es.nbt, bt = i - sl * es.nbt;
-    if (sl < es_segments(es, bt)) x += llpart[i];
-  }
-  return x;
-}
-
-__global__ void k_loglik(const double *__restrict__ llpart, const ESched es, double *__restrict__ out,
-                         double inv_FT, const int *halt) {
-  HALT_GUARD(halt);
-  __shared__ double s[256];
-  const double x = ll_partial_sum(llpart, es);
-  s[threadIdx.x] = x;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = -(s[0] * inv_FT);
 }
 
 // sum_{c < n} p[c * stride] in index order (bit-identical to the plain loop)
@@ -3680,9 +2220,6 @@ __global__ __launch_bounds__(256) void k_tb_renorm(const TBRArgs a) {
 }
 
 // ---------------------------------------------------------------- host side
-enum KernelId {
-  KW = 0, KFWH, KINSTA, KESTEP, KLL, KMIX, KMIXI, KFBC, KFBU, KTWC, KREN, KTWU, KFWU, KROWS, KRTAIL, KTWD, KTWV
-};
 static const char *kKernelNames[fasst_ctx::kNK] = {
     "k_w_from_fb", "k_fwh_t", "k_inst_A", "k_estep", "k_loglik", "k_mix",
     "k_mix_inst", "k_fb_contract", "k_fb_update", "k_tw_contract", "k_renorm", "k_tw_update",
@@ -3691,17 +2228,6 @@ static const char *kKernelNames[fasst_ctx::kNK] = {
     "k_sf_other", "k_sf_hatw", "k_sf_energy", "k_sf_bary", "k_sf_sparsify",
     "k_sfw_scale", "k_sfw_dgemm2", "k_sfw_update", "k_sfw_renorm"};
 
-// per-kernel timing: an event pair around the launch on the stream it runs on
-// (s = nullptr: the main stream), slot = the iteration's place in the ring
-static inline void prof_begin(fasst_ctx *c, int id, hipStream_t s = nullptr) {
-  if (c->prof) {
-    (void)hipEventRecord(c->ev0[id][c->pslot], s ? s : c->stream);
-    c->used[id][c->pslot] = 1;
-  }
-}
-static inline void prof_end(fasst_ctx *c, int id, hipStream_t s = nullptr) {
-  if (c->prof) (void)hipEventRecord(c->ev1[id][c->pslot], s ? s : c->stream);
-}
 // after a device sync: fold the recorded event pairs into the averages
 static void prof_collect(fasst_ctx *c) {
   if (!c->prof) return;
@@ -3717,16 +2243,66 @@ static void prof_collect(fasst_ctx *c) {
     }
 }
 
-// the E-step's default schedule and the fewest quad-steps a balanced block
-// takes by default (fasst_configure)
-constexpr bool kEsBalancedDefault = true;
-constexpr int kEsMinUnits = 10;
-// k_tw_contract_lds's schedule when FASST_TWC_SCHED is unset
-constexpr bool kTwcBalancedDefault = true;
-static int estep_occupancy(const fasst_ctx *c);
-static bool estep_cxi(const fasst_ctx *c);
-static int contract_occupancy(const fasst_ctx *c);
-static int twl_occupancy(const fasst_ctx *c, bool bal, int *units, int *group_tiles);
+// The spectral update's template arms, chosen from the model in one place:
+// `f` receives NKC = KP / 16 as a std::integral_constant<int, 1 | 2 | 4 | 8>
+// (launches and occupancy queries alike), and LAM as a std::bool_constant.
+template <class F>
+static void nkc_dispatch(const fasst_ctx *c, F &&f) {
+  switch (c->KP / 16) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;   // KP = 128
+  }
+}
+
+template <class F>
+static void lam_dispatch(const fasst_ctx *c, F &&f) {
+  if (c->lambda > 0.0)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+
+// frame tiles per wave of the TW contraction: KP = 128 keeps one (its
+// numerator / denominator tiles alone fill 128 VGPRs)
+template <int NKC>
+constexpr int tpw_for() { return NKC > 4 ? 1 : kTPW; }
+
+// k_tw_contract_lds's shape: 8 waves per block, one frame tile per wave, two
+// LDS stages (C3 same-box A/B, k_tw_contract 0.395 ms: NW x TPW x NS = 8 x 1 x
+// 2 0.378, 4 x 2 x 2 0.379, 4 x 1 x 3 0.396, 4 x 2 x 3 0.437 ms; the other
+// shapes and the register-operand k_tw_contract of rounds 1-4 were deleted
+// after the A/B)
+template <int NKC>
+using TwlShape = TwlCfg<NKC, 8, 1, 2>;
+
+// resident k_tw_contract_lds blocks per CU (bal: of its balanced form), its
+// frame-tile groups (units) and the frame tiles of one
+static int twl_occupancy(const fasst_ctx *c, bool bal, int *units, int *group_tiles) {
+  int n = 0;
+  nkc_dispatch(c, [&](auto k) {
+    using CF = TwlShape<decltype(k)::value>;
+    const void *fn = bal ? (const void *)k_tw_contract_lds<CF, true> : (const void *)k_tw_contract_lds<CF>;
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF::smem);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, CF::NT, CF::smem) != hipSuccess) n = 1;
+    *group_tiles = CF::NW_ * CF::TPW_;
+    *units = (c->ntt + *group_tiles - 1) / *group_tiles;
+  });
+  return std::max(1, n);
+}
+
+// resident k_fb_contract waves per CU
+static int contract_occupancy(const fasst_ctx *c) {
+  int n = 1;
+  hipError_t e = hipSuccess;
+  nkc_dispatch(c, [&](auto k) {
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fb_contract<decltype(k)::value, kFPW>,
+                                                     64, 0);
+  });
+  return e == hipSuccess ? std::max(1, n) : 1;
+}
+
 // bins per block of the FW update's f-contraction (k_fw_reduce holds three
 // [fpc][KP] tiles in LDS: 96 KB at KP = 128 with 32 bins)
 static int fw_fpc(const fasst_ctx *c) { return c->KP > 64 ? 32 : kFwFpc; }
@@ -3757,7 +2333,7 @@ static int best_split(long unit, long cap, int max_split) {
 // default, raised once per model configuration to the most any structure asks
 // of them (not per iteration: the sizes depend only on the model shape, and
 // a ceiling above a launch's own size costs nothing)
-static int set_lds_limits() {
+static int spectral_lds_limits() {
   struct L {
     const void *f;
     size_t bytes;
@@ -3765,17 +2341,23 @@ static int set_lds_limits() {
   const L lim[] = {
       {(const void *)k_fw_reduce, (size_t)3 * 32 * kMaxKP * sizeof(double)},
       {(const void *)k_fwh_t<true>, (size_t)(16 + 64) * kMaxKP * sizeof(double)},
-      {(const void *)k_egen_stats, (size_t)kEgsRows * 256 * sizeof(double)},
-      {(const void *)k_egen_fused<4>, (size_t)(kEgsRows * 256 + kMaxJ * 16 * 16) * sizeof(double)},
-      {(const void *)k_egen_fused<8>, (size_t)(kEgsRows * 256 + kMaxJ * 32 * 16) * sizeof(double)},
-      {(const void *)k_mix<(4 * (kMaxJ * (kMaxJ + 1) / 2) + 8 * kMaxJ + 63) / 64, (kMaxR * kMaxR + 63) / 64>,
-       mix_smem(kMaxJ, kMaxR, kMaxKP, 4 * (kMaxJ * (kMaxJ + 1) / 2) + 8 * kMaxJ)},
   };
   for (const L &l : lim)
     if (hipFuncSetAttribute(l.f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.bytes) != hipSuccess) {
       set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu) failed", l.bytes);
       return FASST_ERR_DEVICE;
     }
+  return FASST_OK;
+}
+
+static int mix_lds_limits() {
+  constexpr int nacc = 4 * (kMaxJ * (kMaxJ + 1) / 2) + 8 * kMaxJ;
+  const size_t bytes = mix_smem(kMaxJ, kMaxR, kMaxKP, nacc);
+  if (hipFuncSetAttribute((const void *)k_mix<(nacc + 63) / 64, (kMaxR * kMaxR + 63) / 64>,
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+    set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu) failed", bytes);
+    return FASST_ERR_DEVICE;
+  }
   return FASST_OK;
 }
 
@@ -3799,7 +2381,9 @@ int configure_model(fasst_ctx *c, int J, const int *rank, const int *K, const in
               kMaxKP);
     return FASST_ERR_UNSUPPORTED;
   }
-  if (int st = set_lds_limits()) return st;
+  if (int st = spectral_lds_limits()) return st;
+  if (int st = estep_lds_limits()) return st;
+  if (int st = mix_lds_limits()) return st;
   c->J = J;
   c->R = R;
   c->convm = 0;
@@ -4114,38 +2698,6 @@ static Step step_of(const fasst_ctx *c, int b = -1, int only_j = -1) {
 // initialised, every field that follows from the context (buffers, shapes,
 // chunking, halt) and from the step set here.  What a caller adds is named at
 // each builder; a pointer left out stays null.
-
-static EArgs e_args(const fasst_ctx *c, const double *psd_dev) {
-  EArgs e{};
-  const size_t plane = (size_t)c->Tp * c->Fp;
-  e.cx00 = c->cx.p;
-  e.cx11 = c->cx.p + plane;
-  e.cxr = c->cx.p + 2 * plane;
-  e.cxi = c->cx.p + 3 * plane;
-  e.TW = c->TW.p;
-  e.cxp = c->cxp.p;
-  e.twp = c->twp.p;
-  e.nttp = c->ntt;
-  e.Wkf = c->Wkf.p;
-  e.A = c->A.p;
-  e.psd = psd_dev;
-  e.hatW = c->hatW.p;
-  e.halt = c->halt;
-  e.part = c->epart.p;
-  e.llpart = c->llpart.p;
-  e.F = c->F;
-  e.T = c->T;
-  e.Fp = c->Fp;
-  e.Tp = c->Tp;
-  e.KP = c->KP;
-  e.R = c->R;
-  e.ntt = c->ntt;
-  e.tpc = c->tpc_e;
-  e.nft = c->nft;
-  e.es = c->esched;
-  for (int j = 0; j <= kMaxJ; ++j) e.roff[j] = j <= c->J ? c->roff[j] : c->R;
-  return e;
-}
 
 // the caller adds the planes rnum / rden / rtw / rcp / rpow / roth and `first`
 static MPArgs mp_args(const fasst_ctx *c, const Step &s) {
@@ -4522,175 +3074,6 @@ static int launch_tail_side(fasst_ctx *c) {
   return FASST_OK;
 }
 
-// E-step instantiation chosen from the model structure; `f` receives an
-// ETag carrying the template parameters (used for launches and occupancy).
-template <int J_, int NKS_, int RKU_, bool CXI_, bool TWI_>
-struct ETag {
-  static constexpr int J = J_, NKS = NKS_, RKU = RKU_;
-  static constexpr bool CXI = CXI_, TWI = TWI_;
-};
-
-// does the model's single-pass E-step read the Cx / the TW image (the
-// context's FASST_ESTEP_IMG choice; the TW image on the preload path only)
-// (J = 7 at K = 128 keeps the planes: with the 16-byte loads that one
-// instantiation, already at the whole register file, spills 12 bytes per lane)
-static bool estep_cxi(const fasst_ctx *c) {
-  return c->J <= 8 && (c->eimg & 1) && !(c->J == 7 && c->KP == 128);
-}
-static bool estep_twi(const fasst_ctx *c) {
-  return c->J <= 4 && (c->eimg & 2) && c->J * (c->KP / 4) <= 32;
-}
-
-template <int J, int NKS, int RKU, class F>
-static void estep_dispatch_img(const fasst_ctx *c, F &&f) {
-  const bool cxi = estep_cxi(c);
-  if constexpr (J == 7 && NKS == 32) {   // (never with the Cx image: estep_cxi)
-    f(ETag<J, NKS, RKU, false, false>{});
-  } else {
-    if constexpr (mx_tw_preload<J, NKS>())
-      if (estep_twi(c)) {
-        if (cxi)
-          f(ETag<J, NKS, RKU, true, true>{});
-        else
-          f(ETag<J, NKS, RKU, false, true>{});
-        return;
-      }
-    if (cxi)
-      f(ETag<J, NKS, RKU, true, false>{});
-    else
-      f(ETag<J, NKS, RKU, false, false>{});
-  }
-}
-
-template <int J, int NKS, class F>
-static void estep_dispatch_r(const fasst_ctx *c, F &&f) {
-  bool all1 = true, all2 = true;
-  for (int j = 0; j < J; ++j) {
-    all1 &= c->rank[j] == 1;
-    all2 &= c->rank[j] == 2;
-  }
-  if (all1)
-    estep_dispatch_img<J, NKS, 1>(c, f);
-  else if (all2)
-    estep_dispatch_img<J, NKS, 2>(c, f);
-  else
-    estep_dispatch_img<J, NKS, 0>(c, f);
-}
-
-template <int J, class F>
-static void estep_dispatch_j(const fasst_ctx *c, F &&f) {
-  switch (c->KP) {
-    case 16: estep_dispatch_r<J, 4>(c, f); break;
-    case 32: estep_dispatch_r<J, 8>(c, f); break;
-    case 64: estep_dispatch_r<J, 16>(c, f); break;
-    default: estep_dispatch_img<J, 32, 0>(c, f); break;   // K up to 128: general ranks only
-  }
-}
-
-template <class F>
-static void estep_dispatch(const fasst_ctx *c, F &&f) {
-  switch (c->J) {
-    case 1: estep_dispatch_j<1>(c, f); break;
-    case 2: estep_dispatch_j<2>(c, f); break;
-    case 3: estep_dispatch_j<3>(c, f); break;
-    case 4: estep_dispatch_j<4>(c, f); break;
-    case 5: estep_dispatch_j<5>(c, f); break;
-    case 6: estep_dispatch_j<6>(c, f); break;
-    case 7: estep_dispatch_j<7>(c, f); break;
-    default: estep_dispatch_j<8>(c, f); break;
-  }
-}
-
-// The operand images of the coming k_estep_mx launch (fasst_ctx.h): the Cx
-// image rebuilt if an observation was written since it was packed, the TW
-// image packed from TW unless the previous iteration's fused k_tw_update
-// wrote it (tw_fresh: gem_iteration's prep_ready, which every batch start and
-// every path around the fused tail clears)
-static int estep_images(fasst_ctx *c, bool tw_fresh) {
-  if (estep_cxi(c) && !(c->cxp_valid && c->cxp.p)) {
-    const size_t n = (size_t)c->nft * c->ntt * 512;
-    if (c->cxp.n != n)
-      if (int st = c->cxp.alloc_uninit(n)) return st;
-    k_cx_image<<<dim3(c->ntt, c->nft), 256, 0, c->stream>>>(c->cx.p, c->cxp.p, c->Fp, c->ntt,
-                                                            (size_t)c->Tp * c->Fp);
-    FASST_LAUNCH_CHECK();
-    c->cxp_valid = true;
-  }
-  if (estep_twi(c)) {
-    const size_t n = (size_t)c->ntt * c->J * (c->KP / 8) * 64;
-    if (c->twp.n != n) {
-      if (int st = c->twp.alloc_uninit(n)) return st;
-      tw_fresh = false;
-    }
-    if (!tw_fresh) {
-      k_tw_image<<<dim3(c->ntt, c->J), 256, 0, c->stream>>>(c->TW.p, c->twp.p, c->J, c->KP, c->Tp);
-      FASST_LAUNCH_CHECK();
-    }
-  }
-  return FASST_OK;
-}
-
-static void launch_estep(fasst_ctx *c, const EArgs &e, int ny) {
-  estep_dispatch(c, [&](auto tag) {
-    using T = decltype(tag);
-    prof_begin(c, KESTEP);
-    const dim3 g = e.es.bal ? dim3(e.es.nb) : dim3(c->nft, ny);
-    k_estep_mx<T::J, T::NKS, T::RKU, T::CXI, T::TWI><<<g, 256, estep_mx_smem<T::J, T::NKS>(), c->stream>>>(e);
-    prof_end(c, KESTEP);
-  });
-}
-
-// resident E-step blocks per CU
-static int estep_occupancy(const fasst_ctx *c) {
-  int occ = 1;
-  estep_dispatch(c, [&](auto tag) {
-    using T = decltype(tag);
-    constexpr size_t smem = estep_mx_smem<T::J, T::NKS>();
-    (void)hipFuncSetAttribute((const void *)k_estep_mx<T::J, T::NKS, T::RKU, T::CXI, T::TWI>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_estep_mx<T::J, T::NKS, T::RKU, T::CXI, T::TWI>, 256,
-                                                     smem) != hipSuccess)
-      n = 1;
-    occ = std::max(1, n);
-  });
-  return occ;
-}
-
-// The spectral update's template arms, chosen from the model in one place:
-// `f` receives NKC = KP / 16 as a std::integral_constant<int, 1 | 2 | 4 | 8>
-// (launches and occupancy queries alike), and LAM as a std::bool_constant.
-template <class F>
-static void nkc_dispatch(const fasst_ctx *c, F &&f) {
-  switch (c->KP / 16) {
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    default: f(std::integral_constant<int, 8>{}); break;   // KP = 128
-  }
-}
-
-template <class F>
-static void lam_dispatch(const fasst_ctx *c, F &&f) {
-  if (c->lambda > 0.0)
-    f(std::true_type{});
-  else
-    f(std::false_type{});
-}
-
-// frame tiles per wave of the TW contraction: KP = 128 keeps one (its
-// numerator / denominator tiles alone fill 128 VGPRs)
-template <int NKC>
-constexpr int tpw_for() { return NKC > 4 ? 1 : kTPW; }
-
-// k_tw_contract_lds's shape: 8 waves per block, one frame tile per wave, two
-// LDS stages (C3 same-box A/B, k_tw_contract 0.395 ms: NW x TPW x NS = 8 x 1 x
-// 2 0.378, 4 x 2 x 2 0.379, 4 x 1 x 3 0.396, 4 x 2 x 3 0.437 ms; the other
-// shapes and the register-operand k_tw_contract of rounds 1-4 were deleted
-// after the A/B)
-template <int NKC>
-using TwlShape = TwlCfg<NKC, 8, 1, 2>;
-
 // The launches of the spectral update.  `timed`: with the per-kernel timing
 // events (spectral_update's launches record them, multi_step's none).
 
@@ -4793,39 +3176,13 @@ static int launch_fw_update(fasst_ctx *c, const FWArgs &w, bool blk, bool timed)
         k_fw_contract<NKC, true, decltype(l)::value><<<gc, 64, 0, c->stream>>>(w);
       });
   });
-  const size_t lds = (size_t)3 * w.fpc * c->KP * sizeof(double);   // (ceiling: set_lds_limits)
+  const size_t lds = (size_t)3 * w.fpc * c->KP * sizeof(double);   // (ceiling: spectral_lds_limits)
   k_fw_reduce<<<dim3(w.nfc, c->J), 256, lds, c->stream>>>(w);
   k_fw_final<<<c->J, 256, 0, c->stream>>>(w);
   launch_w(c, c->Wkf_new.p, c->Wfk_new.p, c->stream);
   if (timed) prof_end(c, KFWU);
   FASST_LAUNCH_CHECK();
   return FASST_OK;
-}
-
-// resident k_tw_contract_lds blocks per CU (bal: of its balanced form), its
-// frame-tile groups (units) and the frame tiles of one
-static int twl_occupancy(const fasst_ctx *c, bool bal, int *units, int *group_tiles) {
-  int n = 0;
-  nkc_dispatch(c, [&](auto k) {
-    using CF = TwlShape<decltype(k)::value>;
-    const void *fn = bal ? (const void *)k_tw_contract_lds<CF, true> : (const void *)k_tw_contract_lds<CF>;
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF::smem);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, CF::NT, CF::smem) != hipSuccess) n = 1;
-    *group_tiles = CF::NW_ * CF::TPW_;
-    *units = (c->ntt + *group_tiles - 1) / *group_tiles;
-  });
-  return std::max(1, n);
-}
-
-// resident k_fb_contract waves per CU
-static int contract_occupancy(const fasst_ctx *c) {
-  int n = 1;
-  hipError_t e = hipSuccess;
-  nkc_dispatch(c, [&](auto k) {
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fb_contract<decltype(k)::value, kFPW>,
-                                                     64, 0);
-  });
-  return e == hipSuccess ? std::max(1, n) : 1;
 }
 
 // source j's TW step is the discrete-state one (fasst_set_tw_constr)
@@ -4952,7 +3309,7 @@ static int launch_spectral_prep(fasst_ctx *c, bool fork) {
   bool any_fw = false;
   for (int j = 0; j < J; ++j) any_fw |= c->fw_free[j] != 0;
   // (KP > 64: 16-row FW chunk + TW tile, 80 KB of LDS, two blocks per CU;
-  // ceiling set by set_lds_limits)
+  // ceiling set by spectral_lds_limits)
   (c->KP > 64 ? k_fwh_t<true> : k_fwh_t<false>)<<<dim3((c->Tp + 63) / 64, J), 256,
             c->KP > 64 ? (16 + 64) * c->KP * sizeof(double) : fw_lds(c, c->KP * 64),
             side>>>(c->FW.p, c->TW.p, c->FWHt.p, any_fw ? c->TWt.p : nullptr, J, c->Tp, c->KP,
@@ -5031,6 +3388,22 @@ __global__ void k_rho_from_hatw(const double *__restrict__ hw, const double *__r
   rho[((size_t)j * Tp + t) * Fp + f] = hw[((size_t)j * F + f) * T + t] / fmax(v, kEps);
 }
 
+// the fused tail's last launch (k_renorm_tail: the loglik and, with prep, the
+// next iteration's TW row sums), after the side stream's ev_rows
+static int launch_renorm_tail(fasst_ctx *c, double *ll_dev, int iter, bool prep) {
+  FASST_HIP(hipStreamWaitEvent(c->stream, c->ev_rows, 0));
+  RArgs r = renorm_args(c);
+  r.ll_out = ll_dev;
+  r.hpart = prep ? c->hpart.p : nullptr;
+  r.hsum = c->hsum.p;
+  r.J = c->J;
+  prof_begin(c, KRTAIL);
+  k_renorm_tail<<<1 + (prep ? (c->J * c->KP + 3) / 4 : 0), 256, 0, c->stream>>>(r, iter);
+  prof_end(c, KRTAIL);
+  FASST_LAUNCH_CHECK();
+  return FASST_OK;
+}
+
 // One GEM iteration, all launches asynchronous on c->stream.
 static int gem_iteration(fasst_ctx *c, const double *psd_dev, double *ll_dev, double omega,
                          int iter) {
@@ -5059,46 +3432,10 @@ static int gem_iteration(fasst_ctx *c, const double *psd_dev, double *ll_dev, do
   if (!w_ready && (st = launch_w_old(c))) return st;
   st = build_inst_A(c);
   if (st) return st;
-  const EArgs e = e_args(c, psd_dev);
-  if (J > 8 && c->KP <= 32) {   // the fused many-source E-step
-    GArgs gg{};
-    gg.J = J;
-    const size_t lds = (size_t)(((J + 12) | 1) * 256 + J * c->KP * 16) * sizeof(double);   // (ceiling: set_lds_limits)
-    prof_begin(c, KESTEP);
-    if (c->KP == 16)
-      k_egen_fused<4><<<dim3(c->nft, c->nchunk_e), kEgsThreads, lds, c->stream>>>(e, gg);
-    else
-      k_egen_fused<8><<<dim3(c->nft, c->nchunk_e), kEgsThreads, lds, c->stream>>>(e, gg);
-    prof_end(c, KESTEP);
-  } else if (J > 8) {   // the two-pass E-step (k_egen_point / k_egen_stats)
-    GArgs gg{};
-    gg.V = c->vgen.p;
-    gg.NP = c->npgen.p;
-    gg.lw = c->lgen.p;
-    gg.J = J;
-    prof_begin(c, KESTEP);
-    nkc_dispatch(c, [&](auto n) {
-      constexpr int NKC = decltype(n)::value;
-      if constexpr (NKC >= 4)   // this path has KP > 32: the fused branch above took the rest
-        k_egen_point<4 * NKC><<<dim3(c->ntt, c->nft), 64, 0, c->stream>>>(e, gg);
-    });
-    const size_t lds = (size_t)((J + 12) | 1) * 256 * sizeof(double);   // (ceiling: set_lds_limits)
-    k_egen_stats<<<dim3(c->nft, c->nchunk_e), kEgsThreads, lds, c->stream>>>(e, gg);
-    prof_end(c, KESTEP);
-  } else {
-    if ((st = estep_images(c, prep_ready))) return st;
-    launch_estep(c, e_args(c, psd_dev), c->nchunk_e);
-  }
-  FASST_LAUNCH_CHECK();
+  if ((st = launch_estep_phase(c, psd_dev, prep_ready))) return st;
   if (!prep_ready) FASST_HIP(hipStreamWaitEvent(c->stream, c->ev_join, 0));  // hsum, FWHt below
   const bool ft = fast_tail(c);
-  if (!ft) {   // (fused tail: summed by k_renorm_tail)
-    prof_begin(c, KLL);
-    k_loglik<<<1, 256, 0, c->stream>>>(c->llpart.p, c->esched, ll_dev,
-                                       1.0 / ((double)c->F * (double)c->T), c->halt);
-    prof_end(c, KLL);
-    FASST_LAUNCH_CHECK();
-  }
+  if (!ft && (st = launch_loglik(c, ll_dev))) return st;   // (fused tail: summed by k_renorm_tail)
   // mixing update (update_mix_matrix, :766-889).  (On the side stream beside
   // the TW contraction instead, after the FB update: k_mix stretched to 0.18
   // ms and took 23 us from the TW contraction and 14 us from the FB
@@ -5106,17 +3443,8 @@ static int gem_iteration(fasst_ctx *c, const double *psd_dev, double *ll_dev, do
   if ((st = launch_mix(c, c->stream))) return st;
   if ((st = spectral_update(c, omega, ft))) return st;
   if (!ft) return launch_renorm(c, iter);
-  FASST_HIP(hipStreamWaitEvent(c->stream, c->ev_rows, 0));
-  RArgs r = renorm_args(c);
-  r.ll_out = ll_dev;
   const bool prep = c->ftail >= 2 && c->KP <= 64;   // (spectral_update's k_tw_update formed FWHt)
-  r.hpart = prep ? c->hpart.p : nullptr;
-  r.hsum = c->hsum.p;
-  r.J = J;
-  prof_begin(c, KRTAIL);
-  k_renorm_tail<<<1 + (prep ? (J * c->KP + 3) / 4 : 0), 256, 0, c->stream>>>(r, iter);
-  prof_end(c, KRTAIL);
-  FASST_LAUNCH_CHECK();
+  if ((st = launch_renorm_tail(c, ll_dev, iter, prep))) return st;
   std::swap(c->Wkf.p, c->Wkf_next.p);
   c->w_ready = 1;
   c->prep_ready = prep;

@@ -47,7 +47,7 @@ __global__ void k_source_powers(const double *__restrict__ Wkf, const double *__
 //   pair  PS[p][c] = sum_t V_r1 V_r2 N_c   (p = (r1 <= r2), c: n00 n11 n01r n01i)
 //   cross CS[r][c] = sum_t V_r P_c          (c: P00 P01 P10 P11, re / im)
 //   sV[r] = sum_t V_r
-// and hat_Rss / hat_Rxs follow per bin (see the header of fasst_em.hip).
+// and hat_Rss / hat_Rxs follow per bin (see the header of fasst_em_estep.hip).
 constexpr int kSsTile = 256;
 constexpr int kSsMaxOut = 4 * (kStepMaxR * (kStepMaxR + 1) / 2) + 8 * kStepMaxR + kStepMaxR;
 struct SSArgs {

@@ -1,4 +1,4 @@
-"""The single-pass E-step's tile-packed operand images (fasst_em.hip:
+"""The single-pass E-step's tile-packed operand images (fasst_em_estep.hip:
 k_cx_image, k_tw_image, the image store of the fused k_tw_update, and the
 CXI / TWI forms of k_estep_mx), selected by FASST_ESTEP_IMG = 0 | cx | tw | 1
 when a context is created.

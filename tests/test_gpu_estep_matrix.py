@@ -31,9 +31,10 @@ NCHUNK = 3
 def estep_instance(J, K, ranks):
     """The E-step kernel instantiation fasst_run launches for J sources of at
     most K NMF columns each with these spatial ranks.  Restates
-    pyfasst_amd/csrc/fasst_em.hip:
+    pyfasst_amd/csrc/fasst_em.hip (configure_model) and fasst_em_estep.hip:
       configure_model   KP = K padded to 16 / 32 / 64 / 128 (NKS = KP / 4);
-      gem_iteration     J > 8 with KP <= 32 -> k_egen_fused<NKS>,
+      launch_estep_phase
+                        J > 8 with KP <= 32 -> k_egen_fused<NKS>,
                         J > 8 otherwise -> k_egen_point<NKS> + k_egen_stats,
                         else launch_estep -> k_estep_mx<J, NKS, RKU>;
       estep_dispatch_r / _j
