@@ -4,7 +4,7 @@ Drop-in for pyfasst.audioModel (audioModel.py:66-2508): same class names,
 constructor keyword arguments, `spat_comps` / `spec_comps` / `noise` dicts
 and public methods.  Between calls the NumPy dicts are the source of truth;
 `estim_param_a_post_model()` uploads them once, runs every GEM iteration on
-the GPU (pyfasst_amd/csrc/fasst_em.hip, fasst_em_estep.hip) and downloads the result;
+the GPU (pyfasst_amd/csrc/fasst_em.hip and its phase units fasst_em_*.hip) and downloads the result;
 `separate_spat_comps()` computes the Wiener images and iSTFTs on the GPU.
 
 There is no CPU fallback: structures outside the HIP path raise

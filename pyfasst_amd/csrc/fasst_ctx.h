@@ -59,7 +59,7 @@ struct fasst_ctx {
   int bfw[fasst::kMaxJ][fasst::kMaxBlk] = {{0}};
   // time blobs (fasst_set_tb): block b of source j with tbl[j][b] = L > 0 has
   // H = TW.TB; its factor TW (block rows x L) and TB (L x Tp) live in
-  // tb[j][b] (layout tb_layout in fasst_em.hip) and the block's rows of TW
+  // tb[j][b] (layout tb_layout in fasst_device.h) and the block's rows of TW
   // hold H; btb[j][b]: TB free.  Any time blob routes through the multi path
   fasst::DBuf<double> tb[fasst::kMaxJ][fasst::kMaxBlk];
   int tbl[fasst::kMaxJ][fasst::kMaxBlk] = {{0}}, btb[fasst::kMaxJ][fasst::kMaxBlk] = {{0}};

@@ -186,4 +186,26 @@ __device__ __forceinline__ double ll_partial_sum(const double *__restrict__ llpa
   return x;
 }
 
+// The slot buffer tb[j][b] of a spectral component with time blobs (H = TW TB,
+// fasst_em_spectral.hip): its factor TW ("TWs", kbw block rows x L), TB
+// (L x Tp) and the TW step's numerator / denominator
+struct TBLayout {
+  size_t tws, tb, num, den, n;   // offsets (doubles) in the slot buffer, total
+};
+__host__ __device__ inline TBLayout tb_layout(int kbw, int L, int Tp) {
+  TBLayout o;
+  o.tws = 0;
+  o.tb = (size_t)kbw * L;
+  o.num = o.tb + (size_t)L * Tp;
+  o.den = o.num + (size_t)kbw * L;
+  o.n = o.den + (size_t)kbw * L;
+  return o;
+}
+
+// the time-blob kernels' halt test (iter: TBArgs::iter / TBRArgs::iter)
+__device__ inline bool tb_halted(const int *halt, const int *flags, int iter) {
+  if (!halt || !*(volatile const int *)halt) return false;
+  return iter < 0 || *(volatile const int *)(flags + kFlagIter) < iter;
+}
+
 }  // namespace fasst

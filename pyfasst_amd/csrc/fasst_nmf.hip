@@ -79,7 +79,7 @@ __global__ void k_nmf_h(double *__restrict__ H, const double *__restrict__ num,
 // is recomputed tile by tile on the MFMA pipe and never stored, the ratios
 // X = SX / max(hat^2, eps), Y = 1 / max(hat, eps) stay in registers, and the
 // accumulator-as-operand layout of 16x16x4 feeds them straight into the
-// contraction (as the FASST FB / TW contractions, fasst_em.hip).
+// contraction (as the FASST FB / TW contractions, fasst_em_spectral.hip).
 //
 // Register layouts are chosen so that every operand a lane needs is a run of
 // consecutive doubles (16-byte loads, 20 per 16 x 32 tile instead of 40

@@ -2,7 +2,7 @@
 // GEM path.  V_j = prod_i P_{j,i}, P_{j,i} = (FB_i.FW_i).TW_i, every power an
 // F x T plane (comp_spat_comp_power, audioModel.py:430-498; the multi-factor
 // branches of update_spectral_components :1469-1727 and renormalize_parameters
-// :1980-2040).  Kept beside the single-factor kernels of fasst_em.hip: a model
+// :1980-2040).  Kept beside the single-factor kernels of fasst_em_*.hip: a model
 // without a two-factor component never reaches this file.
 //
 // Per GEM iteration (sf_iteration):

@@ -3,9 +3,9 @@ was one translation unit (tests/golden/em_split.npz, written by
 make_golden_em_split.py on that library): FB, FW, TW, the mixing parameters
 and the per-iteration log-likelihoods of ten models, one per launch path of
 the E-step, mixing, spectral and renormalisation phases
-(tests/em_split_cases.py), whichever unit (fasst_em.hip, fasst_em_estep.hip,
-later ones) a phase lives in.  The kernels are the same machine code, so the
-tolerance is 0: any difference is a launch shape, an argument, a stream or
+(tests/em_split_cases.py), whichever unit (fasst_em_estep.hip,
+fasst_em_mix.hip, fasst_em_spectral.hip, fasst_em_renorm.hip) a phase lives
+in.  The kernels are the same machine code, so the tolerance is 0: any difference is a launch shape, an argument, a stream or
 event order, or an LDS ceiling that did not survive the move.
 
 The fixture depends on the device's CU count through configure_model's

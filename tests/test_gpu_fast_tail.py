@@ -1,6 +1,7 @@
-"""The fused renormalisation tail (fasst_em.hip: k_fb_update statistics,
-k_renorm_scales / _rows on the side stream, TW rescale inside k_tw_update,
-k_renorm_tail; renormalize_parameters, audioModel.py:1980-2040) against the
+"""The fused renormalisation tail (fasst_em_spectral.hip: k_fb_update
+statistics, TW rescale inside k_tw_update; fasst_em_renorm.hip:
+k_renorm_scales / _rows on the side stream, k_renorm_tail;
+renormalize_parameters, audioModel.py:1980-2040) against the
 unfused kernels (FASST_FAST_TAIL=0, read when a context is created) and the
 oracle, on the structures it covers: one spectral component per source,
 fixed FW, no time blobs.  Both fused modes are run: FASST_FAST_TAIL=1 (the

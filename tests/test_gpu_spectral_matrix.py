@@ -56,7 +56,8 @@ ELSEWHERE = [
 
 def spectral_arms(K, several=False, lam=False, blobs=False, free_tb=False, free_fw=False):
     """The instantiations of the four kernels one GEM iteration launches for
-    sources of at most K NMF columns.  Restates pyfasst_amd/csrc/fasst_em.hip:
+    sources of at most K NMF columns.  Restates pyfasst_amd/csrc/fasst_em.hip
+    (configure_model, update_multi) and fasst_em_spectral.hip (the rest):
       configure_model   KP = K padded to 16 / 32 / 64 / 128, NKC = KP / 16;
       update_multi      BLK (the multi-block path, multi_spectral /
                         multi_step) when some source has several spectral
