@@ -88,6 +88,24 @@ struct DeviceGuard {
   }
 };
 
+// A non-blocking stream of the current device owned by a call's scope: drained
+// and destroyed with it, so every return after create() leaves nothing queued.
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(const Stream &) = delete;
+  Stream &operator=(const Stream &) = delete;
+  int create() {
+    FASST_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    return FASST_OK;
+  }
+  ~Stream() {
+    if (!s) return;
+    (void)hipStreamSynchronize(s);
+    (void)hipStreamDestroy(s);
+  }
+};
+
 // Up to three HIP events owned by a call's scope or by a context and destroyed
 // with it, so no error return after create() can leak them.
 struct Events {

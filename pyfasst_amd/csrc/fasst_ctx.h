@@ -152,6 +152,9 @@ int configure_model(fasst_ctx *c, int J, const int *rank, const int *K, const in
 int build_inst_A(fasst_ctx *c);
 int launch_w_old(fasst_ctx *c);  // Wkf = FB.FW
 void sf_release(fasst_ctx *c);   // drop the two-factor model (fasst_sf.hip)
+// what a separation call needs of the observation (fasst_tf.hip): a resident
+// transform, and for nfft > 0 one of nfft / 2 + 1 == F bins; else FASST_ERR_SHAPE
+int need_stft_model(const fasst_ctx *c, const char *fn, int nfft = 0);
 // inv_herm_mat_2d on device arrays (k_inv_herm, fasst_tf.hip)
 int launch_inv_herm(int n, const double *d, const double2 *off, double *id, double2 *ioff,
                     double *det, hipStream_t stream);

@@ -67,18 +67,40 @@ static inline int ilog2(int n) {
   return (1 << l) == n ? l : -1;
 }
 
-// Host-side launchers of the fasst_tf.hip kernels for the other translation
-// units (HIP kernels do not link across TUs without -fgpu-rdc).
-// [nm][F][T] (host order) <-> [nm][Tp][Fp] (frame-major, bins contiguous)
+// Host side of the fasst_tf.hip kernels for the other translation units (HIP
+// kernels do not link across TUs without -fgpu-rdc).  A separation call is an
+// image producer followed by one of the sinks below or cqt_inverse_batch.
+// [nm][F][T] (host order) -> [nm][Tp][Fp] (frame-major, bins contiguous)
 int tf_launch_ft_to_tf(hipStream_t s, const double2 *src, double2 *dst, int F, int T, int Fp,
                        int Tp, int nm);
-int tf_launch_tf_to_ft(hipStream_t s, const double2 *src, double2 *dst, int F, int T, int Fp,
-                       int Tp, int nm);
-// iSTFT of one frame-major image (rows of `ld` bins, T frames) into y[len_out]
-// (tftransforms/stft.py:71-131); frames is [T][wlen] scratch, tw the +1
-// twiddles of nfft.
-int tf_launch_istft(hipStream_t s, const double2 *S, int ld, int T, const double *win,
-                    const double *awin, const double2 *tw, int wlen, int nfft, int hop,
-                    double *frames, double *y, int len_out);
+
+// iSTFT of frame-major images (T rows of `ld` bins) into len_out() samples each
+// (tftransforms/stft.py:71-131).  init refuses a bad geometry before it
+// allocates, and owns what the images share: the windows (analysis_window
+// nullptr: the window), the +1 twiddles of nfft and the [T][wlen] frames.
+struct IstftSink {
+  int init(hipStream_t s, const double *window, const double *analysis_window, int wlen, int nfft,
+           int hop, int T, bool simm = false);   // simm: fasst_istft_simm's overlap-add
+  int len_out() const { return hop * (T - 1) + wlen - (simm ? 0 : wlen / 2); }
+  int run(const double2 *S, int ld, double *y_dev);
+  // the image g0 X0 + g1 X1 (X [2] planes `plane` apart), formed as a frame is loaded
+  int run_gain(const double2 *X, size_t plane, int ld, const double2 *g0, const double2 *g1,
+               double *y_dev);
+
+  hipStream_t s = nullptr;
+  int wlen = 0, nfft = 0, hop = 0, T = 0;
+  bool simm = false;
+  std::vector<double2> tw;   // outlives its asynchronous upload
+  DBuf<double> dw, daw, dframes;
+  DBuf<double2> dtw;
+  int ola(double *y_dev);
+};
+
+// `nimg` images `plane` apart through the sink into y_host [nimg][len_out()];
+// n [Tp][Fp] planes into S_host [n][F][T].  Both drain the stream.
+int images_to_waveforms(IstftSink &sink, const double2 *S, size_t plane, int ld, int nimg,
+                        double *y_host);
+int images_to_host(hipStream_t s, const double2 *dS, int n, int F, int T, int Fp, int Tp,
+                   double *S_host);
 
 }  // namespace fasst

@@ -860,17 +860,12 @@ int nmf_wiener_images(int device, int F, int N, int K, const double *W, const do
                       const int *comp_source, const double *psd, const double *X, double *S) {
   if (!S) return FASST_ERR_SHAPE;
   DeviceGuard g(device);
-  hipStream_t s = nullptr;
-  FASST_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   WienerDev d;
-  int st = wiener_images_dev(s, F, N, K, W, H, J, comp_source, psd, X, d);
-  DBuf<double2> hS;
-  if (!st) st = hS.alloc((size_t)J * F * N);
-  if (!st) st = tf_launch_tf_to_ft(s, d.S.p, hS.p, F, N, d.Fp, d.Np, J);
-  if (!st) st = hS.get(S, hS.n, s);
-  if (hipStreamSynchronize(s) != hipSuccess && !st) st = FASST_ERR_DEVICE;
-  (void)hipStreamDestroy(s);
-  return st;
+  Stream s;
+  int st;
+  if ((st = s.create()) || (st = wiener_images_dev(s.s, F, N, K, W, H, J, comp_source, psd, X, d)))
+    return st;
+  return images_to_host(s.s, d.S.p, J, F, N, d.Fp, d.Np, S);
 }
 
 int nmf_wiener_waveforms(int device, int F, int N, int K, const double *W, const double *H, int J,
@@ -882,27 +877,15 @@ int nmf_wiener_waveforms(int device, int F, int N, int K, const double *W, const
     return FASST_ERR_SHAPE;
   }
   DeviceGuard g(device);
-  hipStream_t s = nullptr;
-  FASST_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   WienerDev d;
-  int st = wiener_images_dev(s, F, N, K, W, H, J, comp_source, psd, X, d);
-  const int len_out = hop * (N - 1) + wlen - wlen / 2;  // istft (stft.py:108-129)
-  DBuf<double> dw, daw, frames, dy;
-  DBuf<double2> dtw;
-  if (!st && ((st = dw.alloc(wlen)) || (st = daw.alloc(wlen)) || (st = dtw.alloc(nfft / 2)) ||
-              (st = frames.alloc((size_t)N * wlen)) || (st = dy.alloc((size_t)J * len_out)))) {
-  }
-  auto tw = twiddles(nfft, +1);
-  if (!st) st = dw.put(window, wlen, s);
-  if (!st) st = daw.put(analysis_window ? analysis_window : window, wlen, s);
-  if (!st) st = dtw.put(tw.data(), tw.size(), s);
-  for (int n = 0; n < J && !st; ++n)
-    st = tf_launch_istft(s, d.S.p + (size_t)n * d.Np * d.Fp, d.Fp, N, dw.p, daw.p, dtw.p, wlen,
-                         nfft, hop, frames.p, dy.p + (size_t)n * len_out, len_out);
-  if (!st) st = dy.get(y, dy.n, s);
-  if (hipStreamSynchronize(s) != hipSuccess && !st) st = FASST_ERR_DEVICE;
-  (void)hipStreamDestroy(s);
-  return st;
+  IstftSink sink;
+  Stream s;
+  int st;
+  // (the producer first: it checks N, which sizes the sink's frames)
+  if ((st = s.create()) || (st = wiener_images_dev(s.s, F, N, K, W, H, J, comp_source, psd, X, d)) ||
+      (st = sink.init(s.s, window, analysis_window, wlen, nfft, hop, N)))
+    return st;
+  return images_to_waveforms(sink, d.S.p, (size_t)d.Np * d.Fp, d.Fp, J, y);
 }
 
 int nmf_get_params(nmf_ctx *c, double *W, double *H) {

@@ -823,6 +823,26 @@ static int sf_check_sources(fasst_ctx *c, int nsrc, const int *src_of) {
   return FASST_OK;
 }
 
+// The image producer of the two-factor model's separation calls: the Wiener
+// images of the nsrc sources in p.S, queued on c->stream; frame-major [Tp][Fp]
+// planes (zero in the padding) for a device sink, else the caller's dense
+// [F][T] order.  The caller keeps p until the stream has drained.
+struct SfPlanes {
+  DBuf<double> dpsd;
+  DBuf<double2> S;
+};
+
+static int sf_planes(fasst_ctx *c, const double *psd, int nsrc, const int *src_of, bool frame_major,
+                     SfPlanes &p) {
+  const size_t splane = frame_major ? (size_t)c->Tp * c->Fp : (size_t)c->F * c->T;
+  int st;
+  if ((st = frame_major ? p.S.alloc(nsrc * 2 * splane) : p.S.alloc_uninit(nsrc * 2 * splane)) ||
+      (st = p.dpsd.upload(psd, c->F, c->stream)) || (st = sf_all_powers(c)))
+    return st;
+  return frame_major ? sf_launch_wiener(c, p.dpsd.p, nsrc, src_of, p.S.p, splane, 1, (size_t)c->Fp)
+                     : sf_launch_wiener(c, p.dpsd.p, nsrc, src_of, p.S.p, splane, (size_t)c->T, 1);
+}
+
 }  // namespace fasst
 
 using namespace fasst;
@@ -1143,20 +1163,13 @@ int fasst_sf_wiener_images(fasst_ctx *c, const double *psd, int nsrc, const int 
   int st = need_sf(c, 0);
   if (st) return st;
   if (!psd || !S) return FASST_ERR_SHAPE;
-  if ((st = sf_check_sources(c, nsrc, src_of))) return st;
-  if (!c->have_X) {
-    set_error("fasst_sf_wiener_images: no STFT available (set_audio / set_stft)");
-    return FASST_ERR_SHAPE;
-  }
-  DeviceGuard g(c->device);
-  const size_t FT = (size_t)c->F * c->T;
-  DBuf<double> dpsd;
-  DBuf<double2> dS;
-  if ((st = dpsd.upload(psd, c->F, c->stream)) || (st = dS.alloc_uninit((size_t)nsrc * 2 * FT)))
+  if ((st = sf_check_sources(c, nsrc, src_of)) || (st = need_stft_model(c, "fasst_sf_wiener_images")))
     return st;
-  if ((st = sf_all_powers(c))) return st;
-  if ((st = sf_launch_wiener(c, dpsd.p, nsrc, src_of, dS.p, FT, (size_t)c->T, 1))) return st;
-  FASST_TRY(dS.get(S, dS.n, c->stream));
+  DeviceGuard g(c->device);
+  SfPlanes p;
+  if ((st = sf_planes(c, psd, nsrc, src_of, false, p))) return st;
+  // the kernel wrote the host layout through its strides: no transpose
+  FASST_TRY(p.S.get(S, p.S.n, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
   return FASST_OK;
 }
@@ -1167,40 +1180,16 @@ int fasst_sf_separate_waveforms(fasst_ctx *c, const double *psd, int nsrc, const
   int st = need_sf(c, 0);
   if (st) return st;
   if (!psd || !window || !y) return FASST_ERR_SHAPE;
-  if ((st = sf_check_sources(c, nsrc, src_of))) return st;
-  if (nfft < 2 || nfft / 2 + 1 != c->F || wlen < 2 || wlen > nfft || hop < 1) {
-    set_error("fasst_sf_separate_waveforms: nfft=%d wlen=%d hop=%d for F=%d", nfft, wlen, hop, c->F);
-    return FASST_ERR_SHAPE;
-  }
-  if (!c->have_X) {
-    set_error("fasst_sf_separate_waveforms: no STFT available (set_audio / set_stft)");
-    return FASST_ERR_SHAPE;
-  }
-  DeviceGuard g(c->device);
-  const int T = c->T;
-  const size_t plane = (size_t)c->Tp * c->Fp;
-  const int len_out = hop * (T - 1) + wlen - wlen / 2;
-  DBuf<double> dpsd, dw, daw, dframes, dy;
-  DBuf<double2> dS, dtw;
-  if ((st = dpsd.alloc_uninit(c->F)) || (st = dS.alloc((size_t)nsrc * 2 * plane)) || (st = dw.alloc(wlen)) ||
-      (st = daw.alloc(wlen)) || (st = dtw.alloc(nfft / 2)) || (st = dframes.alloc((size_t)T * wlen)) ||
-      (st = dy.alloc((size_t)nsrc * 2 * len_out)))
+  if ((st = sf_check_sources(c, nsrc, src_of)) ||
+      (st = need_stft_model(c, "fasst_sf_separate_waveforms", nfft)))
     return st;
-  auto tw = twiddles(nfft, +1);
-  FASST_TRY(dpsd.put(psd, c->F, c->stream));
-  FASST_TRY(dw.put(window, wlen, c->stream));
-  FASST_TRY(daw.put(analysis_window ? analysis_window : window, wlen, c->stream));
-  FASST_TRY(dtw.put(tw.data(), tw.size(), c->stream));
-  if ((st = sf_all_powers(c))) return st;
-  // images frame-major [Tp][Fp], the layout the device iSTFT reads
-  if ((st = sf_launch_wiener(c, dpsd.p, nsrc, src_of, dS.p, plane, 1, (size_t)c->Fp))) return st;
-  for (int q = 0; q < 2 * nsrc; ++q)
-    if ((st = tf_launch_istft(c->stream, dS.p + (size_t)q * plane, c->Fp, T, dw.p, daw.p, dtw.p, wlen, nfft,
-                              hop, dframes.p, dy.p + (size_t)q * len_out, len_out)))
-      return st;
-  FASST_TRY(dy.get(y, dy.n, c->stream));
-  FASST_HIP(hipStreamSynchronize(c->stream));
-  return FASST_OK;
+  DeviceGuard g(c->device);
+  IstftSink sink;
+  SfPlanes p;
+  if ((st = sink.init(c->stream, window, analysis_window, wlen, nfft, hop, c->T)) ||
+      (st = sf_planes(c, psd, nsrc, src_of, true, p)))
+    return st;
+  return images_to_waveforms(sink, p.S.p, (size_t)c->Tp * c->Fp, c->Fp, 2 * nsrc, y);
 }
 
 // fasst_sf_separate_waveforms for a model on a CQT / MinQT (include/fasst_cqt.h):
@@ -1210,24 +1199,16 @@ int fasst_sf_separate_waveforms_cqt(fasst_ctx *c, cqt_ctx *q, const double *psd,
   int st = need_sf(c, 0);
   if (st) return st;
   if (!q || !psd || !y) return FASST_ERR_SHAPE;
-  if ((st = sf_check_sources(c, nsrc, src_of))) return st;
-  if ((st = cqt_match_model(q, L, c->device, c->F, c->T, "fasst_sf_separate_waveforms_cqt")))
+  if ((st = sf_check_sources(c, nsrc, src_of)) ||
+      (st = cqt_match_model(q, L, c->device, c->F, c->T, "fasst_sf_separate_waveforms_cqt")) ||
+      (st = need_stft_model(c, "fasst_sf_separate_waveforms_cqt")))
     return st;
-  if (!c->have_X) {
-    set_error("fasst_sf_separate_waveforms_cqt: no transform resident (set_audio_cqt / set_stft)");
-    return FASST_ERR_SHAPE;
-  }
   DeviceGuard g(c->device);
-  const size_t plane = (size_t)c->Tp * c->Fp;
-  DBuf<double> dpsd;
-  DBuf<double2> dS;
-  if ((st = dS.alloc((size_t)nsrc * 2 * plane)) || (st = dpsd.upload(psd, c->F, c->stream)))
-    return st;
-  if ((st = sf_all_powers(c))) return st;
-  if ((st = sf_launch_wiener(c, dpsd.p, nsrc, src_of, dS.p, plane, 1, (size_t)c->Fp))) return st;
+  SfPlanes p;
+  if ((st = sf_planes(c, psd, nsrc, src_of, true, p))) return st;
   CqtImages im;
-  im.S = dS.p;
-  im.plane = plane;
+  im.S = p.S.p;
+  im.plane = (size_t)c->Tp * c->Fp;
   im.ld = c->Fp;
   return cqt_inverse_batch(q, c->stream, im, 2 * nsrc, L, y);
 }

@@ -722,63 +722,106 @@ int tf_launch_ft_to_tf(hipStream_t s, const double2 *src, double2 *dst, int F, i
   return FASST_OK;
 }
 
-int tf_launch_tf_to_ft(hipStream_t s, const double2 *src, double2 *dst, int F, int T, int Fp,
-                       int Tp, int nm) {
-  k_tf_to_ft<<<dim3((Tp + 15) / 16, (Fp + 15) / 16, nm), 256, 0, s>>>(src, dst, F, T, Fp, Tp);
+int IstftSink::init(hipStream_t stream, const double *window, const double *analysis_window,
+                    int wlen_, int nfft_, int hop_, int T_, bool simm_) {
+  FASST_TRY(check_fft(nfft_, wlen_, hop_));
+  FASST_TRY(fft_smem(nfft_));
+  s = stream, wlen = wlen_, nfft = nfft_, hop = hop_, T = T_, simm = simm_;
+  tw = twiddles(nfft, +1);
+  FASST_TRY(dw.upload(window, wlen, s));
+  FASST_TRY(daw.upload(analysis_window ? analysis_window : window, wlen, s));
+  FASST_TRY(dtw.upload(tw.data(), tw.size(), s));
+  return dframes.alloc_uninit((size_t)T * wlen);   // k_istft_*frames writes all of it
+}
+
+// k_ola / k_ola_simm write every sample of y_dev[len_out()]
+int IstftSink::ola(double *y_dev) {
+  const int n = len_out();
+  if (simm)
+    k_ola_simm<<<(n + 255) / 256, 256, 0, s>>>(dframes.p, T, wlen, hop, dw.p, daw.p, y_dev, n);
+  else
+    k_ola<<<(n + 255) / 256, 256, 0, s>>>(dframes.p, T, wlen, hop, dw.p, daw.p, y_dev, n);
   FASST_LAUNCH_CHECK();
   return FASST_OK;
 }
 
-int tf_launch_istft(hipStream_t s, const double2 *S, int ld, int T, const double *win,
-                    const double *awin, const double2 *tw, int wlen, int nfft, int hop,
-                    double *frames, double *y, int len_out) {
-  int st = check_fft(nfft, wlen, hop);
-  if (st) return st;
-  if ((st = fft_smem(nfft))) return st;
-  k_istft_frames<<<T, 256, nfft * sizeof(double2), s>>>(S, ld, win, wlen, tw, nfft, ilog2(nfft),
-                                                        frames);
+int IstftSink::run(const double2 *S, int ld, double *y_dev) {
+  k_istft_frames<<<T, 256, nfft * sizeof(double2), s>>>(S, ld, dw.p, wlen, dtw.p, nfft,
+                                                        ilog2(nfft), dframes.p);
   FASST_LAUNCH_CHECK();
-  k_ola<<<(len_out + 255) / 256, 256, 0, s>>>(frames, T, wlen, hop, win, awin, y, len_out);
+  return ola(y_dev);
+}
+
+int IstftSink::run_gain(const double2 *X, size_t plane, int ld, const double2 *g0,
+                        const double2 *g1, double *y_dev) {
+  k_istft_gain_frames<<<T, 256, nfft * sizeof(double2), s>>>(X, plane, ld, g0, g1, dw.p, wlen,
+                                                             dtw.p, nfft, ilog2(nfft), dframes.p);
   FASST_LAUNCH_CHECK();
+  return ola(y_dev);
+}
+
+// each image's frames are rows of its plane: iSTFT straight from HBM
+// (k_istft_frames takes the row stride), only waveforms leave the card
+int images_to_waveforms(IstftSink &sink, const double2 *S, size_t plane, int ld, int nimg,
+                        double *y_host) {
+  const size_t n = sink.len_out();
+  DBuf<double> dy;
+  FASST_TRY(dy.alloc_uninit(nimg * n));
+  for (int q = 0; q < nimg; ++q) FASST_TRY(sink.run(S + q * plane, ld, dy.p + q * n));
+  FASST_TRY(dy.get(y_host, dy.n, sink.s));
+  FASST_HIP(hipStreamSynchronize(sink.s));
+  return FASST_OK;
+}
+
+int images_to_host(hipStream_t s, const double2 *dS, int n, int F, int T, int Fp, int Tp,
+                   double *S_host) {
+  DBuf<double2> hS;   // k_tf_to_ft writes all of it
+  FASST_TRY(hS.alloc_uninit((size_t)n * F * T));
+  k_tf_to_ft<<<dim3((Tp + 15) / 16, (Fp + 15) / 16, n), 256, 0, s>>>(dS, hS.p, F, T, Fp, Tp);
+  FASST_LAUNCH_CHECK();
+  FASST_TRY(hS.get(S_host, hS.n, s));
+  FASST_HIP(hipStreamSynchronize(s));
+  return FASST_OK;
+}
+
+int need_stft_model(const fasst_ctx *c, const char *fn, int nfft) {
+  if (nfft > 0 && nfft / 2 + 1 != c->F) {
+    set_error("%s: nfft=%d gives %d bins, the model has F=%d", fn, nfft, nfft / 2 + 1, c->F);
+    return FASST_ERR_SHAPE;
+  }
+  if (!c->have_X) {
+    set_error("%s: no transform resident (set_audio / set_audio_cqt / set_stft)", fn);
+    return FASST_ERR_SHAPE;
+  }
   return FASST_OK;
 }
 
 // fasst_istft, and fasst_istft_simm (simm): the latter keeps the first half
 // window, refuses an output shorter than two windows (its edge copy) and
-// overlap-adds with k_ola_simm
+// overlap-adds with k_ola_simm.  On the null stream.
 static int istft_host(bool simm, int device, const double *X, int n_frames, const double *window,
                       const double *analysis_window, int wlen, int nfft, int hop, double *y) {
-  int st = check_fft(nfft, wlen, hop);
-  if (st) return st;
   if (n_frames < 1 || !X || !y) return FASST_ERR_SHAPE;
   const int F = nfft / 2 + 1, T = n_frames;
-  const int len_out = hop * (T - 1) + wlen - (simm ? 0 : wlen / 2);
+  DeviceGuard g(device);
+  IstftSink sink;
+  int st = sink.init(nullptr, window, analysis_window, wlen, nfft, hop, T, simm);
+  if (st) return st;
+  const int len_out = sink.len_out();
   if (simm && len_out < 2 * wlen) {
     set_error("istft: %d samples < two windows (%d); the reference's edge copy fails", len_out,
               wlen);
     return FASST_ERR_SHAPE;
   }
-  DeviceGuard g(device);
-  if ((st = fft_smem(nfft))) return st;
-  DBuf<double> dw, daw, dframes, dy;
-  DBuf<double2> dtw, dX, dXt;
-  auto tw = twiddles(nfft, +1);
-  if ((st = dXt.alloc((size_t)T * F)) || (st = dframes.alloc((size_t)T * wlen)) ||
-      (st = dy.alloc(len_out)) || (st = dw.upload(window, wlen)) ||
-      (st = daw.upload(analysis_window ? analysis_window : window, wlen)) ||
-      (st = dtw.upload(tw.data(), tw.size())) || (st = dX.upload(X, (size_t)T * F)))
+  DBuf<double> dy;
+  DBuf<double2> dX, dXt;
+  if ((st = dXt.alloc((size_t)T * F)) || (st = dy.alloc_uninit(len_out)) ||
+      (st = dX.upload(X, (size_t)T * F)))
     return st;
   // [F][T] -> [T][F]
   k_ft_to_tf<<<dim3((T + 15) / 16, (F + 15) / 16, 1), 256>>>(dX.p, dXt.p, F, T, F, T);
   FASST_LAUNCH_CHECK();
-  k_istft_frames<<<T, 256, nfft * sizeof(double2)>>>(dXt.p, F, dw.p, wlen, dtw.p, nfft,
-                                                     ilog2(nfft), dframes.p);
-  FASST_LAUNCH_CHECK();
-  if (simm)
-    k_ola_simm<<<(len_out + 255) / 256, 256>>>(dframes.p, T, wlen, hop, dw.p, daw.p, dy.p, len_out);
-  else
-    k_ola<<<(len_out + 255) / 256, 256>>>(dframes.p, T, wlen, hop, dw.p, daw.p, dy.p, len_out);
-  FASST_LAUNCH_CHECK();
+  if ((st = sink.run(dXt.p, F, dy.p))) return st;
   FASST_HIP(hipDeviceSynchronize());
   return dy.get(y, len_out);
 }
@@ -924,6 +967,33 @@ static int upload_stft(fasst_ctx *c, const double *X) {
   c->have_X = true;
   return FASST_OK;
 }
+
+// The image producer of this model's separation calls: the Wiener images of
+// the separation sources, NS * 2 frame-major [Tp][Fp] planes in S, queued on
+// c->stream.  The caller keeps the buffers until the stream has drained.
+struct WienerPlanes {
+  DBuf<double> dpsd, coef;
+  DBuf<int> droff;
+  DBuf<double2> S;
+  int NS = 0;
+};
+
+static int wiener_planes(fasst_ctx *c, const double *psd, WienerPlanes &w) {
+  const int J = c->J;
+  w.NS = c->nsrc > 0 ? c->nsrc : J;
+  int st;
+  if ((st = w.dpsd.alloc(c->Fp)) || (st = w.coef.alloc((size_t)J * 4 * c->Fp)) ||
+      (st = w.droff.alloc(kMaxJ + 1)) || (st = w.S.alloc((size_t)w.NS * 2 * c->Tp * c->Fp)))
+    return st;
+  if ((st = w.dpsd.put(psd, c->F, c->stream)) || (st = w.droff.put(c->roff, J + 1, c->stream)))
+    return st;
+  // W = FB.FW and the per-bin mixing for 'inst'
+  if ((st = build_inst_A(c)) || (st = launch_w_old(c))) return st;
+  k_mixcoef<<<(c->Fp + 255) / 256, 256, 0, c->stream>>>(c->A.p, w.coef.p, J, w.droff.p, c->F,
+                                                        c->Fp);
+  FASST_LAUNCH_CHECK();
+  return launch_wiener(c, w.coef.p, w.dpsd.p, w.S.p);
+}
 }  // namespace fasst
 
 extern "C" {
@@ -991,32 +1061,10 @@ int fasst_wiener_images(fasst_ctx *c, const double *psd, const double *X, double
   int st;
   DeviceGuard g(c->device);  // before upload_stft: X and its staging live on c->device
   if (X && (st = upload_stft(c, X))) return st;
-  if (!c->have_X) {
-    set_error("fasst_wiener_images: no STFT available (set_audio / set_stft / X argument)");
-    return FASST_ERR_SHAPE;
-  }
-  const int J = c->J, NS = c->nsrc > 0 ? c->nsrc : J;
-  DBuf<double> dpsd, coef;
-  DBuf<int> droff;
-  DBuf<double2> dS, hS;
-  const size_t plane = (size_t)c->Tp * c->Fp;
-  if ((st = dpsd.alloc(c->Fp)) || (st = coef.alloc((size_t)J * 4 * c->Fp)) ||
-      (st = droff.alloc(kMaxJ + 1)) || (st = dS.alloc((size_t)NS * 2 * plane)) ||
-      (st = hS.alloc((size_t)NS * 2 * c->F * c->T)))
-    return st;
-  if ((st = dpsd.put(psd, c->F, c->stream)) || (st = droff.put(c->roff, J + 1, c->stream)))
-    return st;
-  // W = FB.FW and the per-bin mixing for 'inst'
-  if ((st = build_inst_A(c))) return st;
-  if ((st = launch_w_old(c))) return st;
-  k_mixcoef<<<(c->Fp + 255) / 256, 256, 0, c->stream>>>(c->A.p, coef.p, J, droff.p, c->F, c->Fp);
-  FASST_LAUNCH_CHECK();
-  if ((st = launch_wiener(c, coef.p, dpsd.p, dS.p))) return st;
-  k_tf_to_ft<<<dim3(c->ntt, c->nft, NS * 2), 256, 0, c->stream>>>(dS.p, hS.p, c->F, c->T, c->Fp, c->Tp);
-  FASST_LAUNCH_CHECK();
-  FASST_TRY(hS.get(S, hS.n, c->stream));
-  FASST_HIP(hipStreamSynchronize(c->stream));
-  return FASST_OK;
+  if ((st = need_stft_model(c, "fasst_wiener_images"))) return st;
+  WienerPlanes w;
+  if ((st = wiener_planes(c, psd, w))) return st;
+  return images_to_host(c->stream, w.S.p, w.NS * 2, c->F, c->T, c->Fp, c->Tp, S);
 }
 
 int fasst_separate_waveforms(fasst_ctx *c, const double *psd, const double *window,
@@ -1026,53 +1074,15 @@ int fasst_separate_waveforms(fasst_ctx *c, const double *psd, const double *wind
     set_error("fasst_separate_waveforms: context not configured");
     return FASST_ERR_SHAPE;
   }
-  int st = check_fft(nfft, wlen, hop);
+  int st = need_stft_model(c, "fasst_separate_waveforms", nfft);
   if (st) return st;
-  if (nfft / 2 + 1 != c->F) {
-    set_error("fasst_separate_waveforms: nfft=%d gives %d bins, the model has F=%d", nfft,
-              nfft / 2 + 1, c->F);
-    return FASST_ERR_SHAPE;
-  }
-  if (!c->have_X) {
-    set_error("fasst_separate_waveforms: no STFT available (set_audio / set_stft)");
-    return FASST_ERR_SHAPE;
-  }
   DeviceGuard g(c->device);
-  if ((st = fft_smem(nfft))) return st;
-  const int J = c->J, T = c->T, NS = c->nsrc > 0 ? c->nsrc : J;
-  const size_t plane = (size_t)c->Tp * c->Fp;
-  const int len_out = hop * (T - 1) + wlen - wlen / 2;  // istft (stft.py:108-129)
-  DBuf<double> dpsd, coef, dw, daw, dframes, dy;
-  DBuf<int> droff;
-  DBuf<double2> dS, dtw;
-  if ((st = dpsd.alloc(c->Fp)) || (st = coef.alloc((size_t)J * 4 * c->Fp)) ||
-      (st = droff.alloc(kMaxJ + 1)) || (st = dS.alloc((size_t)NS * 2 * plane)) ||
-      (st = dframes.alloc((size_t)T * wlen)) || (st = dy.alloc((size_t)NS * 2 * len_out)))
+  IstftSink sink;
+  WienerPlanes w;
+  if ((st = sink.init(c->stream, window, analysis_window, wlen, nfft, hop, c->T)) ||
+      (st = wiener_planes(c, psd, w)))
     return st;
-  auto tw = twiddles(nfft, +1);
-  if ((st = dpsd.put(psd, c->F, c->stream)) || (st = droff.put(c->roff, J + 1, c->stream)) ||
-      (st = dw.upload(window, wlen, c->stream)) ||
-      (st = daw.upload(analysis_window ? analysis_window : window, wlen, c->stream)) ||
-      (st = dtw.upload(tw.data(), tw.size(), c->stream)))
-    return st;
-  if ((st = build_inst_A(c))) return st;
-  if ((st = launch_w_old(c))) return st;
-  k_mixcoef<<<(c->Fp + 255) / 256, 256, 0, c->stream>>>(c->A.p, coef.p, J, droff.p, c->F, c->Fp);
-  FASST_LAUNCH_CHECK();
-  if ((st = launch_wiener(c, coef.p, dpsd.p, dS.p))) return st;
-  // each image's frames are rows of its [Tp][Fp] plane: iSTFT straight from
-  // HBM (k_istft_frames takes the row stride), only waveforms leave the card
-  for (int q = 0; q < 2 * NS; ++q) {
-    k_istft_frames<<<T, 256, nfft * sizeof(double2), c->stream>>>(
-        dS.p + (size_t)q * plane, c->Fp, dw.p, wlen, dtw.p, nfft, ilog2(nfft), dframes.p);
-    FASST_LAUNCH_CHECK();
-    k_ola<<<(len_out + 255) / 256, 256, 0, c->stream>>>(dframes.p, T, wlen, hop, dw.p, daw.p,
-                                                        dy.p + (size_t)q * len_out, len_out);
-    FASST_LAUNCH_CHECK();
-  }
-  FASST_TRY(dy.get(y, dy.n, c->stream));
-  FASST_HIP(hipStreamSynchronize(c->stream));
-  return FASST_OK;
+  return images_to_waveforms(sink, w.S.p, (size_t)c->Tp * c->Fp, c->Fp, w.NS * 2, y);
 }
 
 }  // extern "C"
@@ -1121,25 +1131,16 @@ int fasst_spatial_filter_images(fasst_ctx *c, double *S) {
   int st = need_conv_model(c, "fasst_spatial_filter_images");
   if (st) return st;
   if (!S) return FASST_ERR_SHAPE;
-  if (!c->have_X) {
-    set_error("fasst_spatial_filter_images: no STFT available (set_audio / set_stft)");
-    return FASST_ERR_SHAPE;
-  }
+  if ((st = need_stft_model(c, "fasst_spatial_filter_images"))) return st;
   DeviceGuard g(c->device);
   const int J = c->J;
   const size_t plane = (size_t)c->Tp * c->Fp;
   DBuf<int> droff;
-  DBuf<double2> G, dS, hS;
-  if ((st = spatial_gains(c, droff, G)) || (st = dS.alloc((size_t)J * 2 * plane)) ||
-      (st = hS.alloc((size_t)J * 2 * c->F * c->T)))
-    return st;
+  DBuf<double2> G, dS;
+  if ((st = spatial_gains(c, droff, G)) || (st = dS.alloc((size_t)J * 2 * plane))) return st;
   k_spatial_images<<<2048, 256, 0, c->stream>>>(c->X.p, G.p, J, c->Fp, plane, dS.p);
   FASST_LAUNCH_CHECK();
-  k_tf_to_ft<<<dim3(c->ntt, c->nft, J * 2), 256, 0, c->stream>>>(dS.p, hS.p, c->F, c->T, c->Fp, c->Tp);
-  FASST_LAUNCH_CHECK();
-  FASST_TRY(hS.get(S, hS.n, c->stream));
-  FASST_HIP(hipStreamSynchronize(c->stream));
-  return FASST_OK;
+  return images_to_host(c->stream, dS.p, J * 2, c->F, c->T, c->Fp, c->Tp, S);
 }
 
 int fasst_spatial_filter_waveforms(fasst_ctx *c, const double *window,
@@ -1148,42 +1149,22 @@ int fasst_spatial_filter_waveforms(fasst_ctx *c, const double *window,
   int st = need_conv_model(c, "fasst_spatial_filter_waveforms");
   if (st) return st;
   if (!window || !y) return FASST_ERR_SHAPE;
-  if ((st = check_fft(nfft, wlen, hop))) return st;
-  if (nfft / 2 + 1 != c->F) {
-    set_error("fasst_spatial_filter_waveforms: nfft=%d gives %d bins, the model has F=%d", nfft,
-              nfft / 2 + 1, c->F);
-    return FASST_ERR_SHAPE;
-  }
-  if (!c->have_X) {
-    set_error("fasst_spatial_filter_waveforms: no STFT available (set_audio / set_stft)");
-    return FASST_ERR_SHAPE;
-  }
+  if ((st = need_stft_model(c, "fasst_spatial_filter_waveforms", nfft))) return st;
   DeviceGuard g(c->device);
-  if ((st = fft_smem(nfft))) return st;
-  const int J = c->J, T = c->T;
-  const size_t plane = (size_t)c->Tp * c->Fp;
-  const int len_out = hop * (T - 1) + wlen - wlen / 2;  // istft (stft.py:108-129)
-  DBuf<double> dw, daw, dframes, dy;
+  IstftSink sink;
+  DBuf<double> dy;
   DBuf<int> droff;
-  DBuf<double2> G, dtw;
-  auto tw = twiddles(nfft, +1);
-  if ((st = dframes.alloc_uninit((size_t)T * wlen)) ||
-      (st = dy.alloc_uninit((size_t)J * 2 * len_out)) ||
-      (st = dw.upload(window, wlen, c->stream)) ||
-      (st = daw.upload(analysis_window ? analysis_window : window, wlen, c->stream)) ||
-      (st = dtw.upload(tw.data(), tw.size(), c->stream)))
+  DBuf<double2> G;
+  if ((st = sink.init(c->stream, window, analysis_window, wlen, nfft, hop, c->T)) ||
+      (st = dy.alloc_uninit((size_t)c->J * 2 * sink.len_out())) ||
+      (st = spatial_gains(c, droff, G)))
     return st;
-  if ((st = spatial_gains(c, droff, G))) return st;
   // image q = (n, channel): its frames are g0 X0 + g1 X1 of the resident X
   // rows, formed in the iSTFT's LDS buffer; only waveforms are written
-  for (int q = 0; q < 2 * J; ++q) {
+  for (int q = 0; q < 2 * c->J; ++q) {
     const double2 *g0 = G.p + (size_t)(2 * q) * c->Fp;
-    k_istft_gain_frames<<<T, 256, nfft * sizeof(double2), c->stream>>>(
-        c->X.p, plane, c->Fp, g0, g0 + c->Fp, dw.p, wlen, dtw.p, nfft, ilog2(nfft), dframes.p);
-    FASST_LAUNCH_CHECK();
-    k_ola<<<(len_out + 255) / 256, 256, 0, c->stream>>>(dframes.p, T, wlen, hop, dw.p, daw.p,
-                                                        dy.p + (size_t)q * len_out, len_out);
-    FASST_LAUNCH_CHECK();
+    FASST_TRY(sink.run_gain(c->X.p, (size_t)c->Tp * c->Fp, c->Fp, g0, g0 + c->Fp,
+                            dy.p + (size_t)q * sink.len_out()));
   }
   FASST_TRY(dy.get(y, dy.n, c->stream));
   FASST_HIP(hipStreamSynchronize(c->stream));
@@ -1276,33 +1257,17 @@ int fasst_separate_waveforms_cqt(fasst_ctx *c, cqt_ctx *q, const double *psd, lo
   }
   int st = cqt_match_model(q, L, c->device, c->F, c->T, "fasst_separate_waveforms_cqt");
   if (st) return st;
-  if (!c->have_X) {
-    set_error("fasst_separate_waveforms_cqt: no transform resident (set_audio_cqt / set_stft)");
-    return FASST_ERR_SHAPE;
-  }
+  if ((st = need_stft_model(c, "fasst_separate_waveforms_cqt"))) return st;
   DeviceGuard g(c->device);
-  const int J = c->J, NS = c->nsrc > 0 ? c->nsrc : J;
-  const size_t plane = (size_t)c->Tp * c->Fp;
-  DBuf<double> dpsd, coef;
-  DBuf<int> droff;
-  DBuf<double2> dS;
-  if ((st = dpsd.alloc(c->Fp)) || (st = coef.alloc((size_t)J * 4 * c->Fp)) ||
-      (st = droff.alloc(kMaxJ + 1)) || (st = dS.alloc((size_t)NS * 2 * plane)))
-    return st;
-  if ((st = dpsd.put(psd, c->F, c->stream)) || (st = droff.put(c->roff, J + 1, c->stream)))
-    return st;
-  if ((st = build_inst_A(c))) return st;
-  if ((st = launch_w_old(c))) return st;
-  k_mixcoef<<<(c->Fp + 255) / 256, 256, 0, c->stream>>>(c->A.p, coef.p, J, droff.p, c->F, c->Fp);
-  FASST_LAUNCH_CHECK();
-  if ((st = launch_wiener(c, coef.p, dpsd.p, dS.p))) return st;
+  WienerPlanes w;
+  if ((st = wiener_planes(c, psd, w))) return st;
   // image q = (source, channel) is a [Tp][Fp] plane: the frame-major raster the
   // inverse reads, with the model's row pitch; all 2 NS go through one chain
   CqtImages im;
-  im.S = dS.p;
-  im.plane = plane;
+  im.S = w.S.p;
+  im.plane = (size_t)c->Tp * c->Fp;
   im.ld = c->Fp;
-  return cqt_inverse_batch(q, c->stream, im, 2 * NS, L, y);
+  return cqt_inverse_batch(q, c->stream, im, 2 * w.NS, L, y);
 }
 
 int fasst_spatial_filter_waveforms_cqt(fasst_ctx *c, cqt_ctx *q, long L, double *y) {
@@ -1311,10 +1276,7 @@ int fasst_spatial_filter_waveforms_cqt(fasst_ctx *c, cqt_ctx *q, long L, double 
   if (!q || !y) return FASST_ERR_SHAPE;
   if ((st = cqt_match_model(q, L, c->device, c->F, c->T, "fasst_spatial_filter_waveforms_cqt")))
     return st;
-  if (!c->have_X) {
-    set_error("fasst_spatial_filter_waveforms_cqt: no transform resident (set_audio_cqt / set_stft)");
-    return FASST_ERR_SHAPE;
-  }
+  if ((st = need_stft_model(c, "fasst_spatial_filter_waveforms_cqt"))) return st;
   DeviceGuard g(c->device);
   DBuf<int> droff;
   DBuf<double2> G;
