@@ -1,7 +1,7 @@
 /*
  * fasst_nsgt.h -- C ABI of the non-stationary Gabor transform (libfasst_hip.so):
- * the reference's tftransforms/nsgt (nsgtf.py, nsigtf.py), non-sliced, and the
- * FFT of any length it stands on.
+ * the reference's tftransforms/nsgt (nsgtf.py, nsigtf.py), whole-signal and
+ * sliced (slicq.py), and the FFT of any length it stands on.
  *
  * Conventions: fasst_hip.h (status codes, the last-error text, complex128 as
  * interleaved doubles).  All arithmetic is FP64.  The overlap-add of the
@@ -43,6 +43,44 @@
  * fasst_nsgt_fft: out[k] = sum_n in[n] exp(sign 2 pi i n k / N), sign = -1 or
  * +1, no scaling, host pointers, N <= FASST_NSGT_MAX_N (a power of two up to
  * 2^24).
+ *
+ * The sliced transform (the reference's slicq.py, slicing.py, unslicing.py): a
+ * stream of any length is cut into half-overlapping slices of sl_len = 4 hhop
+ * samples under a Tukey window whose transitions of tr_area samples are centred
+ * on hhop and 3 hhop; every slice is one more channel of a plan with
+ * Ls = sl_len, and the inverse adds the overlapping halves back.  A sliced
+ * plan is a plan (fasst_nsgt_coef_len and fasst_nsgt_plan_destroy take it)
+ * plus the slicing window slwnd [sl_len] and, optionally, the synthesis window
+ * recwnd [sl_len] (null: the slices are added as they are), both in stream
+ * order.
+ *
+ * The stream is counted in quarter-blocks of hhop samples: two zero blocks,
+ * the signal (its last block zero-filled), zero blocks behind.  Slice s takes
+ * blocks 2s .. 2s+3.  One call transforms `nslices` consecutive slices of
+ * `nchan` channels from slice first_slice_index on (only its parity matters:
+ * odd and even slices store their quarters, and rotate their bands, in
+ * opposite ways).
+ *   sliced_forward:  blocks: per channel the 2 nslices + 2 quarter-blocks
+ *                    2 first .. 2 (first + nslices) + 1, channel c at
+ *                    blocks + c * blocks_stride (in samples; host arrays are
+ *                    packed: blocks_stride = (2 nslices + 2) hhop)
+ *                    ->  coef [nslices][nchan][coef_len] complex
+ *   sliced_backward: coef  ->  y: per channel the 2 nslices quarter-blocks
+ *                    2 first .. 2 (first + nslices) - 1 of the stream, channel
+ *                    c at y + c * y_stride samples (host: y_stride =
+ *                    2 nslices hhop); real when the plan is, else complex.
+ *                    carry_in_out [nchan][2 hhop] samples holds what the slice
+ *                    before `first` adds to the first two blocks (zeros before
+ *                    slice 0) and returns what slice first + nslices - 1 adds
+ *                    to the two blocks after the last; after the last call it
+ *                    is the stream's last two blocks.  The sums are formed
+ *                    older slice first and each product and sum rounds on its
+ *                    own, so the result does not depend on how the slices are
+ *                    grouped into calls.
+ * Each call launches the kernels of forward / backward plus one, whatever
+ * nslices.  Refused on the host: FASST_ERR_SHAPE for sl_len not a multiple of
+ * 4, tr_area odd, negative or >= sl_len / 2, an M[k] that is no multiple of 4,
+ * a plan that is not sliced, nchan * nslices > 65535, a stride below the run.
  */
 #ifndef FASST_NSGT_H
 #define FASST_NSGT_H
@@ -63,6 +101,17 @@ int fasst_nsgt_coef_len(void *plan, long *out);
 int fasst_nsgt_forward(void *plan, int nch, const double *x, int is_device, double *coef);
 int fasst_nsgt_backward(void *plan, int nch, const double *coef, int is_device, double *y);
 int fasst_nsgt_fft(int device, int n, int sign, const double *in, double *out);
+
+int fasst_nsgt_sliced_plan_create(int device, int sl_len, int tr_area, int nn, int nbands,
+                                  const int *M, const int *Lg, const int *start, const double *g,
+                                  const double *gd, int real, int reducedform, const double *slwnd,
+                                  const double *recwnd, void **plan);
+int fasst_nsgt_sliced_forward(void *plan, int nchan, int nslices, int first_slice_index,
+                              const double *blocks, long blocks_stride, int is_device,
+                              double *coef);
+int fasst_nsgt_sliced_backward(void *plan, int nchan, int nslices, int first_slice_index,
+                               const double *coef, double *carry_in_out, int is_device, double *y,
+                               long y_stride);
 
 /* Kernel launches of this unit since the library was loaded (all threads). */
 int fasst_nsgt_launch_count(long *count);

@@ -265,6 +265,14 @@ SIGNATURES = {
     "fasst_nsgt_forward": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_int, _dp]),
     "fasst_nsgt_backward": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_int, _dp]),
     "fasst_nsgt_fft": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp]),
+    "fasst_nsgt_sliced_plan_create": (ctypes.c_int, [ctypes.c_int] * 5 + [_ip, _ip, _ip, _dp, _dp,
+                                                                          ctypes.c_int, ctypes.c_int,
+                                                                          _dp, _dp,
+                                                                          ctypes.POINTER(_vp)]),
+    "fasst_nsgt_sliced_forward": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 _dp, ctypes.c_long, ctypes.c_int, _dp]),
+    "fasst_nsgt_sliced_backward": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                  _dp, _dp, ctypes.c_int, _dp, ctypes.c_long]),
     "fasst_nsgt_launch_count": (ctypes.c_int, [_lp]),
     "fasst_nsgt_set_timing": (ctypes.c_int, [ctypes.c_int]),
     "fasst_nsgt_last_ms": (ctypes.c_int, [_dp, _dp]),

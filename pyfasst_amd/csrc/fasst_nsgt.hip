@@ -1,6 +1,6 @@
 // The non-stationary Gabor transform on MI355X (gfx950), FP64: the reference's
-// tftransforms/nsgt/nsgtf.py and nsigtf.py, non-sliced (include/fasst_nsgt.h),
-// on an FFT of any length.
+// tftransforms/nsgt/nsgtf.py and nsigtf.py on a whole signal and, sliced,
+// slicq.py (include/fasst_nsgt.h), on an FFT of any length.
 //
 //   k_small     one transform per block, all in LDS: a power-of-two FFT of up
 //               to 4096 points, or Bluestein's convolution of padded size
@@ -22,6 +22,16 @@
 //               the bands that cover it in ascending band order from a
 //               host-built cover table (no atomics), forming mirrored bands
 //               as conjugate reversals on the fly.
+//   k_slice,    the sliced transform (slicing.py, unslicing.py): k_slice cuts
+//   k_unslice   quarter-blocks of a stream into Tukey-windowed slices in the
+//               rotated quarter order, one pass; the plan's forward / backward
+//               then run with every slice as one more channel; k_unslice
+//               gathers the at most two slice quarters over each output sample,
+//               older slice first, the previous call's last slice through a
+//               carry buffer (no atomics).  arrange()'s per-slice rotation of
+//               each band by M/4 or 3M/4 is a factor i^(r m) on the operand of
+//               the band's length-M transform: band_fold and k_ola apply it
+//               as a sign flip and a re/im swap (rot_nch = 0: none).
 //
 // Inverse transforms are conj . forward . conj on the loads and stores, so only
 // forward twiddles exist.  Each pass reads and writes its array once: the
@@ -64,6 +74,22 @@ struct Job {
   double scale;
 };
 
+// v i^k
+__device__ __forceinline__ double2 quarter_turns(double2 v, int k) {
+  k &= 3;
+  if (k == 1) return make_double2(-v.y, v.x);
+  if (k == 2) return make_double2(-v.x, -v.y);
+  if (k == 3) return make_double2(v.y, -v.x);
+  return v;
+}
+
+// Quarter turns per index of a band of slice (rot_first + ch / rot_nch):
+// `even` on even slices, 4 - even on odd ones; rot_nch = 0 (not sliced): none.
+__device__ __forceinline__ int slice_turns(int rot_nch, int rot_first, int ch, int even) {
+  if (!rot_nch) return 0;
+  return ((rot_first + ch / rot_nch) & 1) ? 4 - even : even;
+}
+
 // temp of nsgtf.py:65-83 folded to M points: t[m] = sum_j temp[m col + j],
 // temp[:(Lg+1)//2] = g[:(Lg+1)//2] ft[win[Lg//2:]], temp[-(Lg//2):] =
 // g[-(Lg//2):] ft[win[:Lg//2]], win[j] = (start + j) mod nn
@@ -104,8 +130,12 @@ struct SmallArgs {
   const Job *jobs;
   long long in_chs, out_chs;
   int nn, gather, sign, in_real, out_real;
+  int rot_nch, rot_first;   // the sliced forward's band rotation (0: none)
 };
 
+// kRot: the sliced forward's band rotation; the plain transform's instantiation
+// carries none of it
+template <bool kRot>
 __global__ __launch_bounds__(256) void k_small(const SmallArgs a) {
   extern __shared__ double2 s[];
   const Job jb = a.jobs[blockIdx.x];
@@ -113,11 +143,13 @@ __global__ __launch_bounds__(256) void k_small(const SmallArgs a) {
   const int n = jb.n, P = jb.P, logP = jb.logP;
   const bool blu = P != n;
   const double2 *tw = a.tw + (P > 1 ? P / 2 - 1 : 0);
+  const int turns = kRot ? slice_turns(a.rot_nch, a.rot_first, ch, 3) : 0;
   for (int p = threadIdx.x; p < P; p += blockDim.x) {
     double2 v = make_double2(0.0, 0.0);
     if (p < n) {
       if (a.gather) {
         v = band_fold(a.ft + (long long)ch * a.nn, a.nn, a.g, jb, p);
+        if (kRot) v = quarter_turns(v, turns * (p & 3));
       } else if (p < jb.n_in) {
         const long long idx = jb.in_off + (long long)ch * a.in_chs + p;
         v = a.in_real ? make_double2(a.in[idx], 0.0) : ((const double2 *)a.in)[idx];
@@ -187,15 +219,20 @@ struct PassArgs {
   int src, dst_w, in_real, out_real;
   int lconj, lmul, twid;      // twid: 0 none, 1 on the load, 2 on the store (k_cols)
   int sconj1, smul, sconj2, transpose_out;
+  int rot_nch, rot_first;     // SRC_GATHER: the sliced forward's band rotation (0: none)
 };
 
+template <bool kRot>
 __device__ __forceinline__ double2 pass_ld(const PassArgs &a, const Job &jb, long long wbase,
                                            int ch, int idx) {
   double2 v = make_double2(0.0, 0.0);
   if (a.src == SRC_W) {
     v = a.W[wbase + idx];
   } else if (a.src == SRC_GATHER) {
-    if (idx < jb.n) v = band_fold(a.ft + (long long)ch * a.nn, a.nn, a.g, jb, idx);
+    if (idx < jb.n) {
+      v = band_fold(a.ft + (long long)ch * a.nn, a.nn, a.g, jb, idx);
+      if (kRot) v = quarter_turns(v, slice_turns(a.rot_nch, a.rot_first, ch, 3) * (idx & 3));
+    }
   } else if (idx < jb.n_in) {
     const long long i = jb.in_off + (long long)ch * a.in_chs + idx;
     v = a.in_real ? make_double2(a.in[i], 0.0) : ((const double2 *)a.in)[i];
@@ -241,6 +278,7 @@ __device__ __forceinline__ int xcd_tile() {
   return (nb & 7) ? b : (b & 7) * (nb >> 3) + (b >> 3);
 }
 
+template <bool kRot>
 __global__ __launch_bounds__(256) void k_cols(const PassArgs a) {
   extern __shared__ double2 s[];
   const int j = blockIdx.y, ch = blockIdx.z;
@@ -251,7 +289,7 @@ __global__ __launch_bounds__(256) void k_cols(const PassArgs a) {
   const int cnt = N1 * C;
   for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
     const int r = i / C, c = i - r * C;
-    double2 v = pass_ld(a, jb, wbase, ch, r * N2 + c0 + c);
+    double2 v = pass_ld<kRot>(a, jb, wbase, ch, r * N2 + c0 + c);
     if (a.twid == 1) v = cmul(v, big_twiddle((long long)r * (c0 + c), top));
     s[c * N1 + brev(r, a.logN1)] = v;
   }
@@ -274,7 +312,7 @@ __global__ __launch_bounds__(256) void k_rows(const PassArgs a) {
   const int cnt = R * N2;
   for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
     const int rr = i >> a.logN2, c = i & (N2 - 1);
-    s[rr * N2 + brev(c, a.logN2)] = pass_ld(a, jb, wbase, ch, (r0 + rr) * N2 + c);
+    s[rr * N2 + brev(c, a.logN2)] = pass_ld<false>(a, jb, wbase, ch, (r0 + rr) * N2 + c);
   }
   __syncthreads();
   lds_fft_batch(s, a.tw + (N2 / 2 - 1), N2, a.logN2, R);
@@ -320,15 +358,18 @@ struct OlaArgs {
   const int *cov;      // terms covering each bin, ascending
   long long coef_len;
   int nn, nbins, real;
+  int rot_nch, rot_first;   // the sliced backward's band rotation (0: none)
 };
 
 // nsigtf.py:104-116 as a gather: fr[b] = sum over the covering bands, in
 // ascending band order, of temp[i] gd[i] M
+template <bool kRot>
 __global__ __launch_bounds__(256) void k_ola(const OlaArgs a) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= a.nbins) return;
   const int ch = blockIdx.y;
   const double2 *fc = a.fc + (long long)ch * a.coef_len;
+  const int turns = kRot ? slice_turns(a.rot_nch, a.rot_first, ch, 1) : 0;
   double2 acc = make_double2(0.0, 0.0);
   for (int e = a.cov_ptr[b]; e < a.cov_ptr[b + 1]; ++e) {
     const OlaTerm t = a.terms[a.cov[e]];
@@ -342,9 +383,11 @@ __global__ __launch_bounds__(256) void k_ola(const OlaArgs a) {
     if (t.mirror) {   // fftsymm: conj(c[(M - m) mod M])
       m = m ? t.srcM - m : 0;
       v = fc[t.src_off + m];
+      if (kRot) v = quarter_turns(v, turns * (m & 3));
       v.y = -v.y;
     } else {
       v = fc[t.src_off + m];
+      if (kRot) v = quarter_turns(v, turns * (m & 3));
     }
     const double w = a.gd[t.gd_off + i];
     const double M = (double)t.srcM;
@@ -360,6 +403,100 @@ __global__ __launch_bounds__(256) void k_ola(const OlaArgs a) {
   if (b == 0 || 2 * b == a.nn) acc.y = 0.0;
   spec[b] = acc;
   if (b > 0 && 2 * b != a.nn) spec[a.nn - b] = make_double2(acc.x, -acc.y);
+}
+
+// -------------------------------------------------------- k_slice, k_unslice
+// Quarter i of the four consecutive stream blocks of a slice sits at quarter
+// (i + 3 - 2 k) mod 4 of the slice, k the slice's parity (slicing.py).
+__device__ __forceinline__ int slice_quarter(int i, int k) { return (i + 3 - 2 * k) & 3; }
+
+struct SliceArgs {
+  const double *blocks;   // [nchan] runs of (2 nslices + 2) hhop samples, blk_chs apart
+  double *xs;             // [nslices nchan][4 hhop]
+  const double *wnd;      // [4 hhop] Tukey window, in stream order
+  long long blk_chs;
+  int hhop, nchan, first;
+};
+
+// slice s = blockIdx.y / nchan takes stream blocks 2s .. 2s+3, each times its
+// quarter of the window; one thread per slice sample
+__global__ __launch_bounds__(256) void k_slice(const SliceArgs a) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= 4 * a.hhop) return;
+  const int s = blockIdx.y / a.nchan, c = blockIdx.y - s * a.nchan;
+  const int qp = p / a.hhop, j = p - qp * a.hhop;
+  const int i = (qp + 1 + 2 * ((a.first + s) & 1)) & 3;   // slice_quarter(i, k) == qp
+  const double v = a.blocks[(long long)c * a.blk_chs + (long long)(2 * s + i) * a.hhop + j];
+  a.xs[(long long)blockIdx.y * 4 * a.hhop + p] = v * a.wnd[i * a.hhop + j];
+}
+
+struct UnsliceArgs {
+  const double *y;    // [nslices nchan][4 hhop] slices, real or complex
+  double *out;        // [nchan] runs of 2 nslices hhop samples, out_chs apart
+  double *carry;      // [nchan][2 hhop]: quarters 2, 3 of the slice before; in and out
+  const double *wnd;  // [4 hhop] synthesis window, or null: plain addition
+  long long out_chs;
+  int hhop, nchan, nslices, first;
+};
+
+// Every product and sum rounds on its own: a sum formed through the carry
+// buffer has the bits of the same sum formed inside one call.
+template <typename T>
+__device__ __forceinline__ T uns_term(const T *y, const double *wnd, long long at, int widx);
+template <>
+__device__ __forceinline__ double uns_term<double>(const double *y, const double *wnd,
+                                                   long long at, int widx) {
+#pragma clang fp contract(off)
+  return wnd ? y[at] * wnd[widx] : y[at];
+}
+template <>
+__device__ __forceinline__ double2 uns_term<double2>(const double2 *y, const double *wnd,
+                                                     long long at, int widx) {
+#pragma clang fp contract(off)
+  const double2 v = y[at];
+  if (!wnd) return v;
+  const double w = wnd[widx];
+  return make_double2(v.x * w, v.y * w);
+}
+__device__ __forceinline__ double uns_add(double a, double b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ double2 uns_add(double2 a, double2 b) {
+#pragma clang fp contract(off)
+  return make_double2(a.x + b.x, a.y + b.y);
+}
+
+// Output block b = 2s + i (i = 0, 1) of a call is quarter i + 2 of slice s - 1
+// (the carry when s = 0) plus quarter i of slice s, in that order; the thread
+// that reads a carry element then writes the last slice's quarter i + 2 there.
+template <typename T>
+__global__ __launch_bounds__(256) void k_unslice(const UnsliceArgs a) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= 2LL * a.nslices * a.hhop) return;
+  const int c = blockIdx.y;
+  const int b = (int)(t / a.hhop), j = (int)(t - (long long)b * a.hhop);
+  const int s = b >> 1, i = b & 1, k = (a.first + s) & 1;
+  const long long sl = 4LL * a.hhop;
+  const T *y = (const T *)a.y;
+  T *carry = (T *)a.carry + (long long)c * 2 * a.hhop;
+  const T newer = uns_term<T>(y, a.wnd, ((long long)s * a.nchan + c) * sl +
+                                            (long long)slice_quarter(i, k) * a.hhop + j,
+                              i * a.hhop + j);
+  T older;
+  if (s > 0) {
+    older = uns_term<T>(y, a.wnd, ((long long)(s - 1) * a.nchan + c) * sl +
+                                      (long long)slice_quarter(i + 2, k ^ 1) * a.hhop + j,
+                        (i + 2) * a.hhop + j);
+  } else {
+    const int last = a.nslices - 1, kl = (a.first + last) & 1;
+    older = carry[i * a.hhop + j];
+    carry[i * a.hhop + j] =
+        uns_term<T>(y, a.wnd, ((long long)last * a.nchan + c) * sl +
+                                  (long long)slice_quarter(i + 2, kl) * a.hhop + j,
+                    (i + 2) * a.hhop + j);
+  }
+  ((T *)a.out)[(long long)c * a.out_chs + t] = uns_add(older, newer);
 }
 
 // ------------------------------------------------------------------- host
@@ -463,8 +600,10 @@ struct Tables {
 int launch_pass(hipStream_t st, bool cols, const PassArgs &a, int nch) {
   const dim3 grid(cols ? a.N2 / a.tile : a.N1 / a.tile, a.njobs, nch);
   const size_t lds = sizeof(double2) * (size_t)a.tile * (cols ? a.N1 : a.N2);
-  if (cols)
-    k_cols<<<grid, 256, lds, st>>>(a);
+  if (cols && a.rot_nch)
+    k_cols<true><<<grid, 256, lds, st>>>(a);
+  else if (cols)
+    k_cols<false><<<grid, 256, lds, st>>>(a);
   else
     k_rows<<<grid, 256, lds, st>>>(a);
   FASST_LAUNCH_CHECK();
@@ -571,6 +710,7 @@ struct Io {
   double *out = nullptr;
   int out_real = 0;
   long long out_chs = 0;
+  int rot_nch = 0, rot_first = 0;   // SRC_GATHER of a sliced plan
 };
 
 // `njobs` transforms of one shape, out = sum in exp(sign 2 pi i n k / N) * scale
@@ -594,7 +734,12 @@ int run_batch(hipStream_t st, const Tables &T, const Shape &s, const Job *jobs, 
     a.sign = sign;
     a.in_real = io.in_real;
     a.out_real = io.out_real;
-    k_small<<<dim3(njobs, nch), 256, sizeof(double2) * (size_t)s.P, st>>>(a);
+    a.rot_nch = io.rot_nch;
+    a.rot_first = io.rot_first;
+    if (a.rot_nch)
+      k_small<true><<<dim3(njobs, nch), 256, sizeof(double2) * (size_t)s.P, st>>>(a);
+    else
+      k_small<false><<<dim3(njobs, nch), 256, sizeof(double2) * (size_t)s.P, st>>>(a);
     FASST_LAUNCH_CHECK();
     ++g_launches;
     return FASST_OK;
@@ -609,6 +754,8 @@ int run_batch(hipStream_t st, const Tables &T, const Shape &s, const Job *jobs, 
   a.out = io.out;
   a.out_real = io.out_real;
   a.out_chs = io.out_chs;
+  a.rot_nch = io.rot_nch;
+  a.rot_first = io.rot_first;
   const int conj = sign > 0;
   // columns first, twiddle on the store, into the work array
   a.src = io.src;
@@ -679,6 +826,21 @@ struct Plan {
     if ((e = sig_h.alloc_uninit((size_t)nch * Ls))) return e;
     if ((e = y_h.alloc_uninit((size_t)nch * Ls * 2))) return e;
     nch_cap = nch;
+    return FASST_OK;
+  }
+
+  // a sliced plan (Ls = sl_len = 4 hhop): the slicing and synthesis windows,
+  // and the host route's staging of stream blocks, output and carry
+  int hhop = 0, tr_area = 0;
+  DBuf<double> slwnd, recwnd, blk_h, out_h, carry_h;
+
+  int ensure_sliced(int nchan, int nslices) {
+    int e;
+    const size_t nblk = (size_t)nchan * (2 * (size_t)nslices + 2) * hhop;
+    if (blk_h.n < nblk && (e = blk_h.alloc_uninit(nblk))) return e;
+    if (out_h.n < 2 * nblk && (e = out_h.alloc_uninit(2 * nblk))) return e;
+    const size_t ncar = (size_t)nchan * 4 * hhop;
+    if (carry_h.n < ncar && (e = carry_h.alloc_uninit(ncar))) return e;
     return FASST_OK;
   }
 };
@@ -791,6 +953,81 @@ struct CallTimer {
     return FASST_OK;
   }
 };
+
+// The kernels of one forward on device arrays: x [nch][Ls] -> coef.  rot_nch /
+// rot_first: the band rotation of a sliced plan (0: none).
+int forward_kernels(Plan *p, hipStream_t st, CallTimer &tm, int nch, const double *dx, double *dc,
+                    int rot_nch, int rot_first) {
+  int e;
+  Io io;
+  io.in = dx;
+  io.in_real = 1;
+  io.in_chs = p->Ls;
+  io.out = (double *)p->ft.p;
+  io.out_chs = p->nn;
+  if ((e = run_batch(st, p->T, p->sh_ls, p->job_ls.p, 1, -1, nch, io, p->W.p))) return e;
+  if ((e = tm.mark(st))) return e;
+  Io bio;
+  bio.src = SRC_GATHER;
+  bio.ft = p->ft.p;
+  bio.g = p->g.p;
+  bio.nn = p->nn;
+  bio.out = dc;
+  bio.out_chs = p->coef_len;
+  bio.rot_nch = rot_nch;
+  bio.rot_first = rot_first;
+  return run_groups(st, p, p->fwd, +1, nch, bio);
+}
+
+// The kernels of one backward on device arrays: coef -> y [nch][Ls].
+int backward_kernels(Plan *p, hipStream_t st, CallTimer &tm, int nch, const double *dc, double *dy,
+                     int rot_nch, int rot_first) {
+  int e;
+  Io bio;
+  bio.in = dc;
+  bio.in_chs = p->coef_len;
+  bio.out = (double *)p->fc.p;
+  bio.out_chs = p->coef_len;
+  if ((e = run_groups(st, p, p->bwd, -1, nch, bio))) return e;
+  OlaArgs oa{};
+  oa.fc = p->fc.p;
+  oa.spec = p->spec.p;
+  oa.gd = p->gd.p;
+  oa.terms = p->terms.p;
+  oa.cov_ptr = p->cov_ptr.p;
+  oa.cov = p->cov.p;
+  oa.coef_len = p->coef_len;
+  oa.nn = p->nn;
+  oa.real = p->real;
+  oa.nbins = p->real ? p->nn / 2 + 1 : p->nn;
+  oa.rot_nch = rot_nch;
+  oa.rot_first = rot_first;
+  if (rot_nch)
+    k_ola<true><<<dim3((oa.nbins + 255) / 256, nch), 256, 0, st>>>(oa);
+  else
+    k_ola<false><<<dim3((oa.nbins + 255) / 256, nch), 256, 0, st>>>(oa);
+  FASST_LAUNCH_CHECK();
+  ++g_launches;
+  if ((e = tm.mark(st))) return e;
+  Io io;
+  io.in = (const double *)p->spec.p;
+  io.in_chs = p->nn;
+  io.out = dy;
+  io.out_real = p->real;
+  io.out_chs = p->Ls;
+  return run_batch(st, p->T, p->sh_nn, p->job_nn.p, 1, +1, nch, io, p->W.p);
+}
+
+// what a sliced call refuses before any device call
+int check_sliced(const char *who, Plan *p, int nchan, int nslices, int first) {
+  if (!p) return bad(FASST_ERR_SHAPE, "%s: null plan", who);
+  if (!p->hhop) return bad(FASST_ERR_SHAPE, "%s: the plan is not a sliced plan", who);
+  if (nchan < 1 || nslices < 1 || first < 0 || (long long)nchan * nslices > 65535)
+    return bad(FASST_ERR_SHAPE,
+               "%s: %d channels x %d slices from slice %d (at most 65535 slices x channels a call)",
+               who, nchan, nslices, first);
+  return FASST_OK;
+}
 
 }  // namespace
 }  // namespace fasst
@@ -976,22 +1213,7 @@ int fasst_nsgt_forward(void *plan, int nch, const double *x, int is_device, doub
   }
   CallTimer tm;
   if ((e = tm.start(st))) return e;
-  Io io;
-  io.in = dx;
-  io.in_real = 1;
-  io.in_chs = p->Ls;
-  io.out = (double *)p->ft.p;
-  io.out_chs = p->nn;
-  if ((e = run_batch(st, p->T, p->sh_ls, p->job_ls.p, 1, -1, nch, io, p->W.p))) return e;
-  if ((e = tm.mark(st))) return e;
-  Io bio;
-  bio.src = SRC_GATHER;
-  bio.ft = p->ft.p;
-  bio.g = p->g.p;
-  bio.nn = p->nn;
-  bio.out = dc;
-  bio.out_chs = p->coef_len;
-  if ((e = run_groups(st, p, p->fwd, +1, nch, bio))) return e;
+  if ((e = forward_kernels(p, st, tm, nch, dx, dc, 0, 0))) return e;
   if ((e = tm.finish(st, true))) return e;
   FASST_HIP(hipStreamSynchronize(st));
   if (!is_device) FASST_TRY(p->coef_h.get(coef, (size_t)nch * p->coef_len));
@@ -1017,37 +1239,143 @@ int fasst_nsgt_backward(void *plan, int nch, const double *coef, int is_device, 
   }
   CallTimer tm;
   if ((e = tm.start(st))) return e;
-  Io bio;
-  bio.in = dc;
-  bio.in_chs = p->coef_len;
-  bio.out = (double *)p->fc.p;
-  bio.out_chs = p->coef_len;
-  if ((e = run_groups(st, p, p->bwd, -1, nch, bio))) return e;
-  OlaArgs oa{};
-  oa.fc = p->fc.p;
-  oa.spec = p->spec.p;
-  oa.gd = p->gd.p;
-  oa.terms = p->terms.p;
-  oa.cov_ptr = p->cov_ptr.p;
-  oa.cov = p->cov.p;
-  oa.coef_len = p->coef_len;
-  oa.nn = p->nn;
-  oa.real = p->real;
-  oa.nbins = p->real ? p->nn / 2 + 1 : p->nn;
-  k_ola<<<dim3((oa.nbins + 255) / 256, nch), 256, 0, st>>>(oa);
-  FASST_LAUNCH_CHECK();
-  ++g_launches;
-  if ((e = tm.mark(st))) return e;
-  Io io;
-  io.in = (const double *)p->spec.p;
-  io.in_chs = p->nn;
-  io.out = dy;
-  io.out_real = p->real;
-  io.out_chs = p->Ls;
-  if ((e = run_batch(st, p->T, p->sh_nn, p->job_nn.p, 1, +1, nch, io, p->W.p))) return e;
+  if ((e = backward_kernels(p, st, tm, nch, dc, dy, 0, 0))) return e;
   if ((e = tm.finish(st, false))) return e;
   FASST_HIP(hipStreamSynchronize(st));
   if (!is_device) FASST_TRY(p->y_h.get(y, ny));
+  return FASST_OK;
+}
+
+int fasst_nsgt_sliced_plan_create(int device, int sl_len, int tr_area, int nn, int nbands,
+                                  const int *M, const int *Lg, const int *start, const double *g,
+                                  const double *gd, int real, int reducedform, const double *slwnd,
+                                  const double *recwnd, void **plan) {
+  if (!plan) return bad(FASST_ERR_SHAPE, "nsgt_sliced_plan_create: null plan pointer");
+  *plan = nullptr;
+  if (!M || !slwnd) return bad(FASST_ERR_SHAPE, "nsgt_sliced_plan_create: null argument");
+  if (sl_len < 4 || sl_len % 4)
+    return bad(FASST_ERR_SHAPE, "nsgt_sliced_plan_create: sl_len %d is not a multiple of 4", sl_len);
+  if (tr_area < 0 || tr_area % 2 || sl_len <= 2 * tr_area)
+    return bad(FASST_ERR_SHAPE,
+               "nsgt_sliced_plan_create: tr_area %d must be even, >= 0 and below sl_len / 2 = %d",
+               tr_area, sl_len / 2);
+  for (int k = 0; k < nbands; ++k)
+    if (M[k] % 4)
+      return bad(FASST_ERR_SHAPE,
+                 "nsgt_sliced_plan_create: band %d has M %d, not a multiple of 4: the slices' "
+                 "rotations by M/4 and 3M/4 would not undo each other",
+                 k, M[k]);
+  void *h = nullptr;
+  int e = fasst_nsgt_plan_create(device, sl_len, nn, nbands, M, Lg, start, g, gd, real, reducedform,
+                                 &h);
+  if (e) return e;
+  Plan *p = (Plan *)h;
+  DeviceGuard guard(device);
+  p->hhop = sl_len / 4;
+  p->tr_area = tr_area;
+  if ((e = p->slwnd.upload(slwnd, (size_t)sl_len)) ||
+      (recwnd && (e = p->recwnd.upload(recwnd, (size_t)sl_len)))) {
+    delete p;
+    return e;
+  }
+  *plan = p;
+  return FASST_OK;
+}
+
+int fasst_nsgt_sliced_forward(void *plan, int nchan, int nslices, int first_slice_index,
+                              const double *blocks, long blocks_stride, int is_device,
+                              double *coef) {
+  Plan *p = (Plan *)plan;
+  int e = check_sliced("nsgt_sliced_forward", p, nchan, nslices, first_slice_index);
+  if (e) return e;
+  const long long run = (2LL * nslices + 2) * p->hhop;
+  if (!blocks || !coef || blocks_stride < run || (!is_device && blocks_stride != run))
+    return bad(FASST_ERR_SHAPE,
+               "nsgt_sliced_forward: null argument or a channel stride of %ld under runs of %lld",
+               blocks_stride, run);
+  DeviceGuard guard(p->device);
+  hipStream_t st = nullptr;
+  const int nch = nchan * nslices;
+  if ((e = p->ensure(nch)) || (e = p->ensure_sliced(nchan, nslices))) return e;
+  const double *db = blocks;
+  double *dc = coef;
+  if (!is_device) {
+    FASST_TRY(p->blk_h.put(blocks, (size_t)nchan * run));
+    db = p->blk_h.p;
+    dc = (double *)p->coef_h.p;
+  }
+  CallTimer tm;
+  if ((e = tm.start(st))) return e;
+  SliceArgs sa{};
+  sa.blocks = db;
+  sa.xs = p->sig_h.p;
+  sa.wnd = p->slwnd.p;
+  sa.blk_chs = blocks_stride;
+  sa.hhop = p->hhop;
+  sa.nchan = nchan;
+  sa.first = first_slice_index & 1;
+  k_slice<<<dim3((p->Ls + 255) / 256, nch), 256, 0, st>>>(sa);
+  FASST_LAUNCH_CHECK();
+  ++g_launches;
+  if ((e = forward_kernels(p, st, tm, nch, p->sig_h.p, dc, nchan, first_slice_index & 1))) return e;
+  if ((e = tm.finish(st, true))) return e;
+  FASST_HIP(hipStreamSynchronize(st));
+  if (!is_device) FASST_TRY(p->coef_h.get(coef, (size_t)nch * p->coef_len));
+  return FASST_OK;
+}
+
+int fasst_nsgt_sliced_backward(void *plan, int nchan, int nslices, int first_slice_index,
+                               const double *coef, double *carry_in_out, int is_device, double *y,
+                               long y_stride) {
+  Plan *p = (Plan *)plan;
+  int e = check_sliced("nsgt_sliced_backward", p, nchan, nslices, first_slice_index);
+  if (e) return e;
+  const long long run = 2LL * nslices * p->hhop;
+  if (!coef || !carry_in_out || !y || y_stride < run || (!is_device && y_stride != run))
+    return bad(FASST_ERR_SHAPE,
+               "nsgt_sliced_backward: null argument or a channel stride of %ld under runs of %lld",
+               y_stride, run);
+  DeviceGuard guard(p->device);
+  hipStream_t st = nullptr;
+  const int nch = nchan * nslices;
+  if ((e = p->ensure(nch)) || (e = p->ensure_sliced(nchan, nslices))) return e;
+  const size_t width = p->real ? 1 : 2;   // doubles per sample
+  const size_t ncarry = width * (size_t)nchan * 2 * p->hhop, nout = width * (size_t)nchan * run;
+  const double *dc = coef;
+  double *dcar = carry_in_out, *dout = y;
+  if (!is_device) {
+    FASST_TRY(p->coef_h.put(coef, (size_t)nch * p->coef_len));
+    FASST_TRY(p->carry_h.put(carry_in_out, ncarry));
+    dc = (const double *)p->coef_h.p;
+    dcar = p->carry_h.p;
+    dout = p->out_h.p;
+  }
+  CallTimer tm;
+  if ((e = tm.start(st))) return e;
+  if ((e = backward_kernels(p, st, tm, nch, dc, p->y_h.p, nchan, first_slice_index & 1))) return e;
+  UnsliceArgs ua{};
+  ua.y = p->y_h.p;
+  ua.out = dout;
+  ua.carry = dcar;
+  ua.wnd = p->recwnd.p;
+  ua.out_chs = y_stride;
+  ua.hhop = p->hhop;
+  ua.nchan = nchan;
+  ua.nslices = nslices;
+  ua.first = first_slice_index & 1;
+  const dim3 grid((unsigned)((run + 255) / 256), nchan);
+  if (p->real)
+    k_unslice<double><<<grid, 256, 0, st>>>(ua);
+  else
+    k_unslice<double2><<<grid, 256, 0, st>>>(ua);
+  FASST_LAUNCH_CHECK();
+  ++g_launches;
+  if ((e = tm.finish(st, false))) return e;
+  FASST_HIP(hipStreamSynchronize(st));
+  if (!is_device) {
+    FASST_TRY(p->out_h.get(y, nout));
+    FASST_TRY(p->carry_h.get(carry_in_out, ncarry));
+  }
   return FASST_OK;
 }
 

@@ -7,9 +7,10 @@ The public names and signatures are those of the NSGT package by Thomas Grill
 (after the MATLAB toolbox of NUHAG, University of Vienna) that the reference
 ships; the code here is this project's own, written from the papers' formulas.
 
-Out of scope, each name refusing with NotImplementedError: the sliced
-transforms and the audio file helpers; nothing here is wired into FASST,
-DEMIX or SeparateLeadProcess.
+The sliced transform (NSGT_sliced, CQ_NSGT_sliced, the sliced planner) is
+pyfasst_amd.tftransforms.slicq; the names of this package still refuse with
+NotImplementedError and say so.  Out of scope, refusing likewise: the audio
+file helpers; nothing here is wired into FASST, DEMIX or SeparateLeadProcess.
 """
 from .cq import NSGT, CQ_NSGT
 from .slicq import NSGT_sliced, CQ_NSGT_sliced

@@ -38,14 +38,17 @@ class DevicePlan(object):
         gp = np.ascontiguousarray(np.concatenate(g), dtype=np.float64)
         gdp = np.ascontiguousarray(np.concatenate(gd), dtype=np.float64)
         self._h = ctypes.c_void_p()
-        check(lib.fasst_nsgt_plan_create(self.device, self.Ls, self.nn, nb, iptr(Mi), iptr(Lg),
-                                         iptr(start), dptr(gp), dptr(gdp), int(self.real),
-                                         int(reducedform), ctypes.byref(self._h)),
-              "fasst_nsgt_plan_create")
+        self._create(nb, Mi, Lg, start, gp, gdp, int(reducedform))
         n = ctypes.c_long(0)
         check(lib.fasst_nsgt_coef_len(self._h, ctypes.byref(n)), "fasst_nsgt_coef_len")
         self.coef_len = n.value
         assert self.coef_len == int(self.offsets[-1])
+
+    def _create(self, nb, Mi, Lg, start, gp, gdp, reducedform):
+        check(lib.fasst_nsgt_plan_create(self.device, self.Ls, self.nn, nb, iptr(Mi), iptr(Lg),
+                                         iptr(start), dptr(gp), dptr(gdp), int(self.real),
+                                         reducedform, ctypes.byref(self._h)),
+              "fasst_nsgt_plan_create")
 
     def __del__(self):
         h, self._h = getattr(self, '_h', None), None

@@ -1,6 +1,7 @@
 """Windows of the NSGT for a frequency scale (host NumPy, FP64).  The name
 and signature of nsgfwin are the reference package's; the code is this
-project's.  Only the non-sliced arm exists.
+project's.  Only the non-sliced arm exists here; the sliced planner is
+pyfasst_amd.tftransforms.slicq.nsgfwin_sliced.
 
 The two-sided spectrum of Ls bins gets one band at DC, one per scale
 frequency inside (0, sr/2), one at Nyquist, and the mirror images of the scale
@@ -32,7 +33,8 @@ def nsgfwin(f, q, sr, Ls, sliced=False, min_win=4, Qvar=1, dowarn=True):
     """Returns (g, rfbas, M): the windows, the rounded band positions in bins
     and the window lengths, 2 (len(f) + 1) bands."""
     if sliced:
-        raise NotImplementedError("nsgfwin(sliced=True): the sliced transform is out of scope")
+        raise NotImplementedError("nsgfwin(sliced=True) refuses: the sliced planner is "
+                                  "pyfasst_amd.tftransforms.slicq.nsgfwin_sliced")
     nyquist = sr / 2.
     f, q = _inside_band(np.asarray(f), np.asarray(q), nyquist)
     if len(f) != len(q) or np.any(np.diff(f) <= 0) or np.any(q <= 0):

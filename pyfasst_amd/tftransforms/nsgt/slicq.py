@@ -1,14 +1,14 @@
-"""The sliced NSGT (slicq.py, slicing.py, unslicing.py, reblock.py of the
-reference) is out of scope: the names exist and refuse."""
+"""The sliced NSGT lives in pyfasst_amd.tftransforms.slicq; the names of this
+package refuse and point there."""
 
 
 class NSGT_sliced(object):
     def __init__(self, *args, **kwargs):
-        raise NotImplementedError("NSGT_sliced: the sliced transform is not implemented; use NSGT "
-                                  "on the whole signal")
+        raise NotImplementedError("nsgt.NSGT_sliced refuses: the sliced transform is "
+                                  "pyfasst_amd.tftransforms.slicq.NSGT_sliced")
 
 
 class CQ_NSGT_sliced(NSGT_sliced):
     def __init__(self, *args, **kwargs):
-        raise NotImplementedError("CQ_NSGT_sliced: the sliced transform is not implemented; use "
-                                  "CQ_NSGT on the whole signal")
+        raise NotImplementedError("nsgt.CQ_NSGT_sliced refuses: the sliced transform is "
+                                  "pyfasst_amd.tftransforms.slicq.CQ_NSGT_sliced")

@@ -10,6 +10,19 @@ def hannwin(l):
     return (np.cos(phase) + 1.) * 0.5
 
 
+def blackharr(n):
+    """Blackman-Harris window of n points in FFT order (the 4-term window with
+    coefficients 0.35872, 0.48832, 0.14128, 0.01168 over a period of n rounded
+    down to even): the peak is at index 0, the second half wraps to the front."""
+    period = (n // 2) * 2
+    k = np.arange(n)
+    w = (0.35872 - 0.48832 * np.cos(k * (2 * np.pi / period))
+         + 0.14128 * np.cos(k * (4 * np.pi / period))
+         - 0.01168 * np.cos(k * (6 * np.pi / period)))
+    half = (n + 1) // 2
+    return np.concatenate((w[n - half:], w[:n - half]))
+
+
 def chkM(M, g):
     """Time channels per band as an array: the window lengths when M is None,
     one number repeated for every band, or the given sequence."""

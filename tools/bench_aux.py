@@ -64,6 +64,10 @@
   --workload nsgt   CQ_NSGT (tftransforms/nsgt) of 100 s at 44.1 kHz, 48 bins per
                     octave: forward / backward device ms, the whole-signal FFT's
                     share of the HBM copy rate, against the NumPy restatement.
+  --workload slicq  CQ_NSGT_sliced (tftransforms/slicq) of the same 100 s in
+                    slices of 65536 samples: forward / backward device ms, the
+                    generators' host-inclusive ms, the round trip, the
+                    whole-signal CQ_NSGT alongside (profiles/slicq_bench.jsonl)
   --workload viterbi  melody tracking (_tracking.pyx:11-93) at config 5:
                     S = 1092 F0 states, N = 20000 frames (runViterbi's
                     transitions, stepNotes 16): tracks/s, device time
@@ -1247,12 +1251,138 @@ def bench_nsgt(steps, warmup, fs=44100, Ls=4410000, bins=48, fmin=27.5, fmax=180
                                        "(numpy.fft), once, planning excluded"}}
 
 
+def bench_slicq(steps, warmup, fs=44100, L=4410000, bins=48, fmin=27.5, fmax=18000, sl_len=65536,
+                tr_area=4096, seed=0):
+    """CQ_NSGT_sliced of 100 s of audio, one and two channels: device time of
+    forward and backward (plan resident; events around the kernels of every
+    call, summed over the calls of one transform), host-inclusive time of the
+    generators from and to NumPy arrays, the round trip; alongside, the
+    whole-signal CQ_NSGT of the same signal and the NumPy restatement of the
+    sliced transform on this box's cores."""
+    import warnings
+    from pyfasst_amd.tftransforms.nsgt import CQ_NSGT, _device
+    from pyfasst_amd.tftransforms.slicq import CQ_NSGT_sliced
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import nsgt_ref as NR
+    import slicq_ref as SR
+    rs = np.random.RandomState(seed)
+    x2 = rs.randn(2, L)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        tr = {1: CQ_NSGT_sliced(fmin, fmax, bins, sl_len, tr_area, fs, real=True),
+              2: CQ_NSGT_sliced(fmin, fmax, bins, sl_len, tr_area, fs, real=True,
+                                multichannel=True)}
+        whole = CQ_NSGT(fmin, fmax, bins, fs, L, real=True)
+    sig = {1: x2[0], 2: x2}
+    _device.set_timing(True)
+    coef = {n: list(tr[n].forward((sig[n],))) for n in (1, 2)}    # builds the device plans
+    packed = {1: np.array([[np.concatenate(c)] for c in coef[1]]),
+              2: np.array([[np.concatenate(ch) for ch in it] for it in coef[2]])}
+    nsl = len(coef[1])
+
+    def device_pass(n, d):
+        """One transform through the plan's batched calls: (total, slicing + FFT share) ms."""
+        t, p, tot, part = tr[n], tr[n].plan, 0.0, 0.0
+        if d == "f":
+            for first, run in t._runs((sig[n],)):
+                p.slices_forward(run, first)
+                a, b = _device.last_ms()
+                tot, part = tot + a, part + b
+        else:
+            per = t._per_call(n)
+            carry = np.zeros((n, 2 * t.hhop))
+            for first in range(0, nsl, per):
+                p.slices_backward(packed[n][first:first + per], carry, first)
+                a, b = _device.last_ms()
+                tot, part = tot + a, part + b
+        return tot, part
+
+    acc = {(n, d): {"dev": [], "fft": [], "wall": []} for n in (1, 2) for d in "fb"}
+    for it in range(warmup + steps):
+        for n in (1, 2):
+            for d in "fb":
+                tot, part = device_pass(n, d)
+                t0 = time.perf_counter()
+                if d == "f":
+                    list(tr[n].forward((sig[n],)))
+                else:
+                    y = np.concatenate(list(tr[n].backward(coef[n])), axis=-1)
+                wall = time.perf_counter() - t0
+                if it >= warmup:
+                    a = acc[(n, d)]
+                    a["dev"].append(tot)
+                    a["fft"].append(part)
+                    a["wall"].append(wall * 1e3)
+    err = float(np.max(np.abs(y[:, :L] - x2)) / np.max(np.abs(x2)))
+    p = tr[1].plan
+    cases = []
+    for n in (1, 2):
+        # slicing (stream read once, slices written) and the sl_len-point
+        # four-step FFT (2 passes, read + write, 16 B; its first read is the 8 B slices)
+        fwd_bytes = n * (8 * (2 * nsl + 2) * (sl_len // 4) + nsl * sl_len * (8 + 8 + 16 + 16 + 16))
+        # the nn-point inverse FFT (2 passes, the last write 8 B) and the unslicing
+        bwd_bytes = n * (nsl * sl_len * (16 + 16 + 16 + 8 + 8) + 8 * 2 * nsl * (sl_len // 4))
+        for d, nm, nbytes in (("f", "forward", fwd_bytes), ("b", "backward", bwd_bytes)):
+            a = acc[(n, d)]
+            dev, fft = float(np.median(a["dev"])), float(np.median(a["fft"]))
+            # forward: the share is slicing + slice FFT; backward: the inverse FFT + unslicing
+            gbs = nbytes / (fft * 1e-3) / 1e9
+            cases.append({"case": "%s, %d channel%s" % (nm, n, "s" if n > 1 else ""),
+                          "device_ms": round(dev, 3), "slice_fft_ms": round(fft, 3),
+                          "band_stage_ms": round(dev - fft, 3),
+                          "host_inclusive_ms": round(float(np.median(a["wall"])), 1),
+                          "slice_fft_gb_per_s": round(gbs, 1),
+                          "slice_fft_frac_of_copy": round(gbs / COPY_GBS, 4)})
+    # the whole-signal transform of the same signal, same session
+    wc = whole.forward(x2[0])
+    wacc = {"f": [], "b": []}
+    for it in range(warmup + steps):
+        whole.forward(x2[0])
+        wacc["f"].append(_device.last_ms()[0])
+        whole.backward(wc)
+        wacc["b"].append(_device.last_ms()[0])
+    whole_ms = {"forward_ms": round(float(np.median(wacc["f"][warmup:])), 3),
+                "backward_ms": round(float(np.median(wacc["b"][warmup:])), 3),
+                "coef_len": int(whole.plan.coef_len)}
+    cpu = None
+    if not NO_CPU:
+        f, q = NR.oct_scale(fmin, fmax, bins)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            rp = SR.SlicedPlan(f, q, fs, sl_len, tr_area, real=True)
+        t0 = time.perf_counter()
+        rc = rp.forward_stream(x2[0])
+        cf = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        rp.backward_stream(rc)
+        cb = time.perf_counter() - t0
+        cpu = {"forward_ms": round(cf * 1e3, 1), "backward_ms": round(cb * 1e3, 1)}
+    return {"metric": "CQ_NSGT_sliced forward device ms, 1 channel", "value": cases[0]["device_ms"],
+            "unit": "ms", "ms_per_step": cases[0]["device_ms"], "steps": steps, "warmup": warmup,
+            "dtype": "f64", "data": "synthetic, RandomState(0)",
+            "config": {"workload": "CQ_NSGT_sliced fmin=%g fmax=%g bins=%d sl_len=%d tr_area=%d "
+                                   "fs=%d L=%d real" % (fmin, fmax, bins, sl_len, tr_area, fs, L),
+                       "bands": len(tr[1].g), "coef_len": int(p.coef_len), "slices": nsl,
+                       "slices_per_call": tr[1].slices_per_call},
+            "cases": cases, "round_trip_rel_err": err, "whole_signal_cq_nsgt": whole_ms,
+            "roofline": {"bound": "hbm", "achieved": cases[0]["slice_fft_gb_per_s"],
+                         "peak": COPY_GBS, "unit": "GB/s",
+                         "frac": cases[0]["slice_fft_frac_of_copy"],
+                         "scope": "forward: k_slice and the sl_len-point four-step FFT of every "
+                                  "slice; backward: the inverse FFT and k_unslice; minimal "
+                                  "traffic over the device events of that share"},
+            "cpu_baseline": {"value": cpu["forward_ms"] if cpu else None, "unit": "ms",
+                             "cores": _blas_threads(), "kind": "port", "detail": cpu,
+                             "sample": "tests/slicq_ref.py forward_stream / backward_stream of "
+                                       "one channel (numpy.fft), once, planning excluded"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=("simm", "nmf", "cqt", "viterbi", "wf0", "separate",
                                            "nnls", "spatial", "hmm", "sf", "sfnmf", "sigtools",
                                            "separate_cqt", "filter", "stereo_nmf", "demix",
-                                           "wf0_chirped", "dirdiag", "nsgt"),
+                                           "wf0_chirped", "dirdiag", "nsgt", "slicq"),
                     required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -1270,7 +1400,7 @@ def main():
           "separate_cqt": bench_separate_cqt, "filter": bench_filter,
           "stereo_nmf": bench_stereo_nmf, "demix": bench_demix,
           "wf0_chirped": bench_wf0_chirped, "dirdiag": bench_dirdiag,
-          "nsgt": bench_nsgt}[a.workload]
+          "nsgt": bench_nsgt, "slicq": bench_slicq}[a.workload]
     out = fn(a.steps, a.warmup, sparsity=a.sparsity) if a.workload == "sf" else \
         fn(a.steps, a.warmup)
     if NO_CPU:
