@@ -36,6 +36,13 @@ struct fasst_ctx {
   // the renormalisation's scales and FB / FW / mixing rescale run on the side
   // stream beside the TW contraction (gem_iteration's fused tail)
   hipEvent_t ev_tail = nullptr, ev_scales = nullptr, ev_rows = nullptr;
+  // with the fused tail the mixing update runs on the side stream beside the
+  // FB contraction: ev_mixf forks it at the E-step's
+  // end, ev_mix orders k_fb_update behind it.  FASST_MIX_SIDE=0, read when
+  // the context is created, keeps it on the main stream before the
+  // contraction (the A/B knob: the results are the same bit for bit)
+  int mix_side = 1;
+  hipEvent_t ev_mixf = nullptr, ev_mix = nullptr;
   // observation
   int F = 0, T = 0, Fp = 0, Tp = 0, nft = 0, ntt = 0;
   fasst::DBuf<double> cx;        // 4*Tp*Fp

@@ -23,6 +23,7 @@
 // k_renorm_scales / _rows and the next iteration's W on the side stream inside
 // spectral_update, then launch_renorm_tail (k_renorm_tail); the next iteration
 // of the batch then skips launch_w_old and, with prep, launch_spectral_prep.
+// The fused tail's launch_mix runs on the side stream beside k_fb_contract.
 #include "fasst_em.h"
 #include "fasst_device.h"
 
@@ -366,7 +367,20 @@ static int gem_iteration(fasst_ctx *c, const double *psd_dev, double *ll_dev, do
   // the TW contraction instead, after the FB update: k_mix stretched to 0.18
   // ms and took 23 us from the TW contraction and 14 us from the FB
   // contraction for the 30 us it left the critical path; profiles/r6_ab_mix_side.txt)
-  if ((st = launch_mix(c, c->stream))) return st;
+  // With the fused tail it runs on the side stream beside the HBM-bound FB
+  // contraction, which reads nothing it writes: forked here, launched before
+  // the contraction so its one-wave blocks take their slots first.  The side
+  // stream's k_renorm_scales, the first reader of the new mixing parameters,
+  // follows it in stream order; spectral_update puts k_fb_update, the first
+  // kernel that moves a parameter, behind ev_mix, so a singular solve halts
+  // the iteration's updates as it does on one stream.
+  const bool mix_side = ft && c->mix_side;
+  if (mix_side) {
+    FASST_HIP(hipEventRecord(c->ev_mixf, c->stream));
+    FASST_HIP(hipStreamWaitEvent(c->aux, c->ev_mixf, 0));
+  }
+  if ((st = launch_mix(c, mix_side ? c->aux : c->stream))) return st;
+  if (mix_side) FASST_HIP(hipEventRecord(c->ev_mix, c->aux));
   if ((st = spectral_update(c, omega, ft))) return st;
   if (!ft) return launch_renorm(c, iter);
   const bool prep = c->ftail >= 2 && c->KP <= 64;   // (spectral_update's k_tw_update formed FWHt)
@@ -431,6 +445,7 @@ int fasst_create(int device, int F, int T, fasst_ctx **out) {
   c->nft = c->Fp / kTile;
   c->ntt = c->Tp / kTile;
   if (const char *v = getenv("FASST_FAST_TAIL")) c->ftail = atoi(v);
+  if (const char *v = getenv("FASST_MIX_SIDE")) c->mix_side = atoi(v) != 0;
   if (const char *v = getenv("FASST_ESTEP_IMG"))
     c->eimg = !strcmp(v, "cx") ? 1 : (!strcmp(v, "tw") ? 2 : (!strcmp(v, "0") ? 0 : 3));
   int st = FASST_OK;
@@ -440,7 +455,9 @@ int fasst_create(int device, int F, int T, fasst_ctx **out) {
       hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->ev_scales, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_rows, hipEventDisableTiming) != hipSuccess) {
+      hipEventCreateWithFlags(&c->ev_rows, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_mixf, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_mix, hipEventDisableTiming) != hipSuccess) {
     set_error("hipStreamCreate / hipEventCreate failed");
     st = FASST_ERR_DEVICE;
   }
@@ -530,6 +547,8 @@ int fasst_destroy(fasst_ctx *c) {
     if (c->ev_tail) (void)hipEventDestroy(c->ev_tail);
     if (c->ev_scales) (void)hipEventDestroy(c->ev_scales);
     if (c->ev_rows) (void)hipEventDestroy(c->ev_rows);
+    if (c->ev_mixf) (void)hipEventDestroy(c->ev_mixf);
+    if (c->ev_mix) (void)hipEventDestroy(c->ev_mix);
     if (c->aux) (void)hipStreamDestroy(c->aux);
     if (c->stream) (void)hipStreamDestroy(c->stream);
   }

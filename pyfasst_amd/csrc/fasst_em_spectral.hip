@@ -2109,6 +2109,9 @@ int spectral_update(fasst_ctx *c, double omega, bool tail) {
   tu.twp = prep && estep_twi(c) ? c->twp.p : nullptr;   // (allocated by the iteration's E-step)
   launch_fb_contract(c, b, false, true);
   FASST_LAUNCH_CHECK();
+  // (the mixing update beside the contraction, gem_iteration: its halt flag
+  // is final before the first parameter moves)
+  if (tail && c->mix_side) FASST_HIP(hipStreamWaitEvent(c->stream, c->ev_mix, 0));
   if (int st = launch_fb_update(c, u, tu, true)) return st;
   if (tail)
     if (int st = launch_tail_side(c)) return st;
