@@ -1,10 +1,13 @@
-// Internal interface of the EM engine's five translation units: fasst_em.hip
+// Internal interface of the EM engine's translation units: fasst_em.hip
 // (model configuration, gem_iteration, the C ABI; no kernel) and one unit per
 // phase, fasst_em_estep.hip, fasst_em_mix.hip, fasst_em_spectral.hip and
-// fasst_em_renorm.hip.  Each kernel is named in exactly one unit, which
-// launches it and queries or sets its attributes; the others reach it through
-// the host functions declared here.  Argument structs stay private to their
-// unit.
+// fasst_em_renorm.hip.  The E-step's single-pass kernel is instantiated in
+// eight further units, fasst_em_estep_j1.hip .. _j8.hip, one per source count,
+// which only fasst_em_estep.hip calls (fasst_em_estep_mx.h).  Each kernel, and
+// each of its instantiations, is named in exactly one unit, which launches it
+// and queries or sets its attributes; the others reach it through the host
+// functions declared here.  Argument structs stay private to their unit (the
+// E-step's to its units).
 #pragma once
 #include "fasst_ctx.h"
 

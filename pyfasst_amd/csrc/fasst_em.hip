@@ -10,7 +10,8 @@
 //   launch_w_old          k_w_from_fb: W = FB.FW          fasst_em_spectral.hip
 //   build_inst_A          k_inst_A: 'inst' mixing per bin fasst_em_mix.hip
 //   launch_estep_phase    the operand images, k_estep_mx (J <= 8) or k_egen_*
-//                         (compute_suff_stat :580-764)    fasst_em_estep.hip
+//                         (compute_suff_stat :580-764)    fasst_em_estep.hip,
+//                                                         fasst_em_estep_j<J>.hip
 //   launch_loglik         k_loglik (:660-664)             fasst_em_estep.hip
 //   launch_mix            k_mix, k_mix_inst (update_mix_matrix :766-889)
 //                                                         fasst_em_mix.hip

@@ -1,7 +1,7 @@
 """The single-pass E-step's tile-packed operand images (fasst_em_estep.hip:
-k_cx_image, k_tw_image, the image store of the fused k_tw_update, and the
-CXI / TWI forms of k_estep_mx), selected by FASST_ESTEP_IMG = 0 | cx | tw | 1
-when a context is created.
+k_cx_image, k_tw_image; the image store of the fused k_tw_update; and the
+CXI / TWI forms of k_estep_mx, fasst_em_estep_mx.h), selected by
+FASST_ESTEP_IMG = 0 | cx | tw | 1 when a context is created.
 
 The images change where the operands are read from, not their values nor any
 arithmetic instruction, so every comparison between two image settings here is

@@ -31,13 +31,14 @@ NCHUNK = 3
 def estep_instance(J, K, ranks):
     """The E-step kernel instantiation fasst_run launches for J sources of at
     most K NMF columns each with these spatial ranks.  Restates
-    pyfasst_amd/csrc/fasst_em.hip (configure_model) and fasst_em_estep.hip:
+    pyfasst_amd/csrc/fasst_em.hip (configure_model), fasst_em_estep.hip and
+    fasst_em_estep_mx.h:
       configure_model   KP = K padded to 16 / 32 / 64 / 128 (NKS = KP / 4);
-      launch_estep_phase
+      launch_estep_phase (fasst_em_estep.hip)
                         J > 8 with KP <= 32 -> k_egen_fused<NKS>,
                         J > 8 otherwise -> k_egen_point<NKS> + k_egen_stats,
                         else launch_estep -> k_estep_mx<J, NKS, RKU>;
-      estep_dispatch_r / _j
+      estep_dispatch_r / _j (fasst_em_estep_mx.h)
                         RKU = 1 (every rank 1), 2 (every rank 2) or 0
                         (general ranks); KP = 128 has the general form only.
     A change to those functions must be restated here, and the completeness
