@@ -17,18 +17,25 @@ import numpy as np
 EPS = 10 ** (-20)   # SIMM.py:150, :506
 
 
-def _init(shape, given, rng):
+def _dtype(*arrays):
+    """The working precision: float64, or np.longdouble when the data are
+    given in it (the tests' yardstick run).  Every parameter, scalar and the
+    error vector are kept in it; only the random draws start as float64."""
+    return np.result_type(np.float64, *[np.asarray(a).dtype for a in arrays])
+
+
+def _init(shape, given, rng, dtype=np.float64):
     if given is not None and np.array(given).shape == shape:
-        return np.array(given, copy=True, order='C', dtype=float)
-    return np.abs(rng.randn(*shape))
+        return np.array(given, copy=True, order='C', dtype=dtype)
+    return np.abs(rng.randn(*shape)).astype(dtype)
 
 
-def _init_params(F, N, NF0, P, K, R, HGAMMA0, HPHI0, HF00, WM0, HM0, rng):
-    HGAMMA = _init((P, K), HGAMMA0, rng)
-    HPHI = _init((K, N), HPHI0, rng)
-    HF0 = _init((NF0, N), HF00, rng)
-    HM = _init((R, N), HM0, rng)
-    WM = _init((F, R), WM0, rng)
+def _init_params(F, N, NF0, P, K, R, HGAMMA0, HPHI0, HF00, WM0, HM0, rng, dtype=np.float64):
+    HGAMMA = _init((P, K), HGAMMA0, rng, dtype)
+    HPHI = _init((K, N), HPHI0, rng, dtype)
+    HF0 = _init((NF0, N), HF00, rng, dtype)
+    HM = _init((R, N), HM0, rng, dtype)
+    WM = _init((F, R), WM0, rng, dtype)
     return HGAMMA, HPHI, HF0, HM, WM
 
 
@@ -46,14 +53,15 @@ def simm(SX, WF0, WGAMMA, numberOfFilters=4, numberOfAccompanimentSpectralShapes
     F, N = SX.shape
     NF0 = WF0.shape[1]
     P = WGAMMA.shape[1]
+    dt = _dtype(SX, WF0, WGAMMA)
     HGAMMA, HPHI, HF0, HM, WM = _init_params(F, N, NF0, P, K, R, HGAMMA0, HPHI0, HF00,
-                                             WM0, HM0, rng)
+                                             WM0, HM0, rng, dt)
     WPHI = np.dot(WGAMMA, HGAMMA)
     SF0 = np.dot(WF0, HF0)
     SPHI = np.dot(WPHI, HPHI)
     SM = np.dot(WM, HM)
     hat = SF0 * SPHI + SM
-    recoError = np.zeros([numberOfIterations * 5 * 2 + NF0 * 2 + 1])
+    recoError = np.zeros([numberOfIterations * 5 * 2 + NF0 * 2 + 1], dtype=dt)
     WF0T = np.ascontiguousarray(WF0.T)
     for _ in range(numberOfIterations):
         den = SPHI / np.maximum(hat, EPS)
@@ -127,11 +135,12 @@ def stereo_simm(SXR, SXL, WF0, WGAMMA, numberOfFilters=4, numberOfAccompanimentS
         raise ValueError("Dimension of STFT matrices must be the same.")
     NF0 = WF0.shape[1]
     P = WGAMMA.shape[1]
+    dt = _dtype(SXR, SXL, WF0, WGAMMA)
     HGAMMA, HPHI, HF0, HM, WM = _init_params(F, N, NF0, P, K, R, HGAMMA0, HPHI0, HF00,
-                                             WM0, HM0, rng)
-    aR = 0.5
-    aL = 0.5
-    bR = rng.rand(R)
+                                             WM0, HM0, rng, dt)
+    aR = dt.type(0.5)
+    aL = dt.type(0.5)
+    bR = rng.rand(R).astype(dt)
     bL = 1 - bR
     WPHI = np.dot(WGAMMA, HGAMMA)
     SF0 = np.dot(WF0, HF0)
@@ -141,7 +150,7 @@ def stereo_simm(SXR, SXL, WF0, WGAMMA, numberOfFilters=4, numberOfAccompanimentS
     hR += np.dot(WM * (bR ** 2), HM)
     hL *= (aL ** 2)
     hL += np.dot(WM * (bL ** 2), HM)
-    recoError = np.zeros([numberOfIterations * 5 * 2 + NF0 * 2 + 1])
+    recoError = np.zeros([numberOfIterations * 5 * 2 + NF0 * 2 + 1], dtype=dt)
     if computeError:
         recoError[0] = is_distortion(SXR, hR) + is_distortion(SXL, hL)
     stride = 7 if updateHGAMMA else 6
